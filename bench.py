@@ -2,6 +2,7 @@
 """bench.py -- cells/sec of the cellular message-passing hot path on N x MI355X.
 
     python bench.py --gpus 1 --steps 200 --warmup 20
+    python bench.py --gpus 1 --steps 200 --warmup 20 --full     (+ rooflines, CPU baseline, secondary legs, other workloads)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -19,10 +20,14 @@ One STEP = one pass of the hot path over one batch with the batch already reside
     REDDIT hubs -- run a per-batch cwn_csr_build + grouped GEMM + cwn_aggregate_f32 instead.)
 Unit: cell-updates/s = sum_d N_d x layers x steps / wall time, summed over ranks
 (weak scaling: every rank owns its own batches, no data-path collective).
-The JSON line also carries `roofline` (dominant kernel: layer_kernel<F, load>, csrc/cwn_layer.hip, at the configurations the
-complex-blocked launch serves; aggregate_kernel on the CSR path), `cpu_baseline` (oracle timed on the host cores, rank 0,
-N=1 only) and `secondary` (full model forward, training step, the same three scopes on batches never seen before, other
-workloads).
+
+A plain run does what the headline needs and nothing else: set-up, W warm-up steps, ONE timed region of exactly K steps,
+the line (`ms_per_step` = that region / K).  `--dump-outputs DIR` then writes what the last timed step returned (the last
+layer's propagate outputs) as DIR/<name>.npy; the inputs are seeded, so two builds compare output for output.
+With --full the JSON line also carries `roofline` (dominant kernel: layer_kernel<F, load>, csrc/cwn_layer.hip, at the
+configurations the complex-blocked launch serves; aggregate_kernel on the CSR path), `cpu_baseline` (oracle timed on the host
+cores, rank 0, N=1 only), `secondary` (full model forward, training step, the same three scopes on batches never seen before,
+other workloads) and `timing.repeated_region` (the K steps R times back to back in one region of >= 50 ms).
 
 Environment (exploration and the sub-runs of `secondary.workloads`; the driver sets none of them): CWN_BENCH_SKIP=leg,leg,...
 (eager, concurrent, collate, train, fresh, workloads, roofline, full); CWN_BENCH_ATOMS=lo,hi | zinc (molecule sizes);
@@ -63,7 +68,13 @@ def parse():
     p.add_argument('--no-graph', action='store_true', help='eager launches instead of hipGraph replay')
     p.add_argument('--kernel-reps', type=int, default=100)
     p.add_argument('--only-primary', action='store_true', help='skip secondary / roofline / cpu legs (profiling)')
-    p.add_argument('--brief', action='store_true', help='primary + roofline only (what the default run asks of the other workloads)')
+    p.add_argument('--brief', action='store_true', help='primary + roofline only (what the --full run asks of the other workloads)')
+    p.add_argument('--full', action='store_true',
+                   help='every leg besides the headline: rooflines, CPU baseline, full forward, eager, concurrent, training step, '
+                        'collate, never-seen batches, other workloads, the repeated timed region (a plain run times the headline only)')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32, at most '
+                        '64 MB in all: beyond that a seeded sample of the rows)')
     return p.parse_args()
 
 
@@ -242,6 +253,32 @@ def slim_line(full, detail_path=None):
     return out
 
 
+DUMP_BUDGET = 64 << 20      # bytes: what --dump-outputs may write in all
+
+
+def dump_outputs(path, outs, budget=DUMP_BUDGET):
+    """--dump-outputs: the tensors the timed path returned from its last step -> path/<name>.npy (float64 stays float64,
+    everything else float32).  Beyond `budget` bytes in all, every array keeps the same share of its rows, drawn with a
+    fixed seed per array: identical shapes give identical samples, so two builds compare output for output."""
+    import numpy as np
+    arrs = {}
+    for i, t in enumerate(outs):
+        if t is not None:
+            t = t.detach()
+            arrs[f'propagate_out{i}'] = (t if t.dtype == torch.float64 else t.float()).cpu().numpy()
+    total = sum(a.nbytes for a in arrs.values())
+    if total > budget:
+        share = budget / total
+        for i, (name, a) in enumerate(sorted(arrs.items())):
+            if a.ndim:
+                rows = np.random.default_rng(i).choice(a.shape[0], int(a.shape[0] * share), replace=False)
+                arrs[name] = a[np.sort(rows)]
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrs.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+    return sorted(arrs)
+
+
 def emit(full):
     """Detail to bench_detail.json (beside this file; CWN_BENCH_DETAIL overrides) and to stderr, the slim line to stdout."""
     path = os.environ.get('CWN_BENCH_DETAIL', os.path.join(ROOT, 'bench_detail.json'))
@@ -281,6 +318,8 @@ def self_launch(n):
 
 def main():
     args = parse()
+    if not args.full:       # a plain run: set-up, warm-up, the K timed steps, the line; every other leg is --full's
+        args.only_primary = True
     LEGS = {}
     t_leg = [time.perf_counter()]
 
@@ -489,10 +528,12 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def timed(fn, steps, warmup, use_graph, min_seconds=0.0):
-        """W warm-up steps, then timed regions of exactly K steps (see `region`); times are the max over ranks."""
+    def timed(fn, steps, warmup, use_graph, min_seconds=0.0, repeat=True):
+        """W warm-up steps, then a timed region of exactly K steps (see `region`) and, with `repeat`, a second one of R rounds
+        of K steps; times are the max over ranks.  `last` is what the last step returned."""
         nb = len(batches)
         graphs = None
+        last = [None]
         with torch.no_grad():
             if use_graph:
                 # one hipGraph per distinct batch: the step's launches are captured from the very
@@ -526,28 +567,38 @@ def main():
                     g_big = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(g_big, capture_error_mode=CAPTURE_MODE):
                         keep_big = [fn(bi) for _ in range(rounds) for bi in range(nb)]
+                # the first replay of a captured graph carries one-time costs, and a short warm-up never reaches g_big:
+                # every graph a timed region may replay is replayed once here
+                for g in [g_ for g_, _ in graphs] + [g_all] + ([g_big] if g_big is not None else []):
+                    g.replay()
+                torch.cuda.synchronize()
 
             def run_steps(n_steps, start=0):
                 """exactly n_steps steps, batches cycled"""
                 if not use_graph:
                     for i in range(n_steps):
-                        fn((start + i) % nb)
+                        last[0] = fn((start + i) % nb)
                     return
                 i = 0
                 while i < n_steps and (start + i) % nb != 0:       # align to batch 0
                     graphs[(start + i) % nb][0].replay()
+                    last[0] = graphs[(start + i) % nb][1]
                     i += 1
                 if g_big is not None and n_steps - i >= (rounds + 1) * nb:
                     g_all.replay()                                 # short enqueue: the GPU starts early
+                    last[0] = keep_all[-1]
                     i += nb
                 while g_big is not None and n_steps - i >= rounds * nb:
                     g_big.replay()
+                    last[0] = keep_big[-1]
                     i += rounds * nb
                 while n_steps - i >= nb:
                     g_all.replay()
+                    last[0] = keep_all[-1]
                     i += nb
                 while i < n_steps:
                     graphs[(start + i) % nb][0].replay()
+                    last[0] = graphs[(start + i) % nb][1]
                     i += 1
 
             def region(n_rounds):
@@ -577,43 +628,51 @@ def main():
 
             run_steps(warmup)
             # the contract's literal region: exactly K steps ...
-            k_wall, _ = region(1)
+            k_wall, round_ms = region(1)
             k_wall = max_over_ranks(k_wall)
-            rounds_ = 1
-            if min_seconds > 0:
-                # ... and, because K steps of this path are under a millisecond (one graph launch + one host wake-up
-                # are ~8 % of it: VERDICT r2 weak #10), the same K steps R times back to back in ONE region of at least
-                # `min_seconds`; R is agreed across the ranks (it follows from the slowest rank's K-step time)
-                rounds_ = int(min(4096, max(1, -(-min_seconds // max(k_wall, 1e-6)))))
-            wall, round_ms = region(rounds_)
-            wall = max_over_ranks(wall)
-        return {'dt': wall, 'rounds': rounds_, 'round_ms': round_ms, 'k_region_s': k_wall}
+            rounds_, wall = 1, k_wall
+            if repeat:
+                if min_seconds > 0:
+                    # ... and, because K steps of this path are under a millisecond (one graph launch + one host wake-up
+                    # are ~8 % of it: VERDICT r2 weak #10), the same K steps R times back to back in ONE region of at least
+                    # `min_seconds`; R is agreed across the ranks (it follows from the slowest rank's K-step time)
+                    rounds_ = int(min(4096, max(1, -(-min_seconds // max(k_wall, 1e-6)))))
+                wall, round_ms = region(rounds_)
+                wall = max_over_ranks(wall)
+        return {'dt': wall, 'rounds': rounds_, 'round_ms': round_ms, 'k_region_s': k_wall, 'last': last[0]}
 
     mark('setup')
     use_graph = not args.no_graph
     MIN_REGION_S = float(os.environ.get('CWN_BENCH_MIN_REGION_S', '0.05'))
     try:
-        tm = timed(propagate_scope, args.steps, args.warmup, use_graph, MIN_REGION_S)
+        tm = timed(propagate_scope, args.steps, args.warmup, use_graph, MIN_REGION_S, repeat=args.full)
     except Exception as e:   # capture restrictions differ between ROCm builds: say so, run eager
         if not use_graph:
             raise
         print(f'[bench] hipGraph capture failed ({type(e).__name__}: {e}); running eager', file=sys.stderr)
         use_graph = False
         torch.cuda.synchronize()
-        tm = timed(propagate_scope, args.steps, args.warmup, False, MIN_REGION_S)
-    # the timed region is R rounds of exactly K steps; everything below is per K steps
-    R = tm['rounds']
-    dt = tm['dt'] / R
-    round_ms = sorted(tm['round_ms'])
-    timing = {'rounds': R, 'timed_steps': R * args.steps, 'timed_region_ms': round(tm['dt'] * 1e3, 3),
-              'ms_per_step_round_median': round(round_ms[len(round_ms) // 2] / args.steps, 5),
-              'ms_per_step_round_min': round(round_ms[0] / args.steps, 5),
-              'ms_per_step_round_max': round(round_ms[-1] / args.steps, 5),
-              'ms_per_step_single_K_step_region': round(tm['k_region_s'] / args.steps * 1e3, 5),
-              'note': f'`value` and `ms_per_step` = wall clock over ONE region of {R} rounds x exactly {args.steps} steps '
-                      '(barrier + synchronize on both sides, max over ranks); per-round figures from HIP events behind '
-                      'every round on the launch stream; the single K-step region (the same bracket around K steps '
-                      'only) carries one graph launch and one host wake-up per K steps'}
+        tm = timed(propagate_scope, args.steps, args.warmup, False, MIN_REGION_S, repeat=args.full)
+    # the headline is the region of exactly K steps; everything below is per K steps
+    dt = tm['k_region_s']
+    timing = {'rounds': 1, 'timed_steps': args.steps, 'timed_region_ms': round(dt * 1e3, 3),
+              'note': f'`value` and `ms_per_step` = wall clock over ONE region of exactly {args.steps} steps after '
+                      f'{args.warmup} warm-up steps (barrier + synchronize on both sides, max over ranks): one graph launch '
+                      'and one host wake-up per region'}
+    if args.full:
+        R = tm['rounds']
+        round_ms = sorted(tm['round_ms'])
+        timing['repeated_region'] = {
+            'rounds': R, 'timed_steps': R * args.steps, 'timed_region_ms': round(tm['dt'] * 1e3, 3),
+            'ms_per_step': round(tm['dt'] / (R * args.steps) * 1e3, 5),
+            'ms_per_step_round_median': round(round_ms[len(round_ms) // 2] / args.steps, 5),
+            'ms_per_step_round_min': round(round_ms[0] / args.steps, 5),
+            'ms_per_step_round_max': round(round_ms[-1] / args.steps, 5),
+            'note': f'after the headline region, the same {args.steps} steps {R} times back to back in one region of at least '
+                    'CWN_BENCH_MIN_REGION_S (barrier + synchronize on both sides, max over ranks): one graph launch and one '
+                    'host wake-up per R x K steps; per-round figures from HIP events behind every round on the launch stream'}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tm['last'])
 
     cells_per_step_local = sum(stats[(args.warmup + i) % len(stats)]['cells'] for i in range(args.steps)) * L / args.steps
     cells_total = torch.tensor([cells_per_step_local * args.steps], device=dev, dtype=torch.float64)
@@ -1364,7 +1423,7 @@ def main():
                          'zinc_real_spread_batch2048': ['--workload', 'zinc', '--batch', '2048', '--num-batches', '1']}.get(wl, ['--workload', wl])
                 # (molhiv-512 = BASELINE configs[2] also runs its full forward, training step and the never-seen-batch legs)
                 whole = wl in ('molhiv', 'molhiv_real_tail', 'reddit', 'zinc_cinpp')      # (reddit-32 = BASELINE configs[4]; zinc_cinpp: CIN++ layers)
-                cmd = [sys.executable, os.path.abspath(__file__)] + extra + (['--no-cpu'] if whole else ['--brief']) + [
+                cmd = [sys.executable, os.path.abspath(__file__), '--full'] + extra + (['--no-cpu'] if whole else ['--brief']) + [
                        '--steps', str(max(args.steps, 20)),
                        '--warmup', str(max(args.warmup, 5)), '--kernel-reps', str(min(args.kernel_reps, 50))]
                 env_ = dict(os.environ)

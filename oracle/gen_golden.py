@@ -128,10 +128,33 @@ def randomize_features(batch, F, gen):
         batch.cochains[d].x = torch.randn(n, F, generator=gen)
 
 
+PART_BYTES = 900 << 10      # every committed file stays under 1 MiB: a larger fixture is written as <stem>.npz, <stem>.1.npz, ...
+
+
+def split_parts(out):
+    """Consecutive groups of the arrays of `out`, each under PART_BYTES (counting 512 bytes of zip headers per array);
+    tests/_golden.py:load merges them back."""
+    parts, cur, size = [], {}, 0
+    for k, v in out.items():
+        nb = np.asarray(v).nbytes + 512
+        if cur and size + nb > PART_BYTES:
+            parts.append(cur)
+            cur, size = {}, 0
+        cur[k] = v
+        size += nb
+    return parts + [cur]
+
+
 def save(name, out):
-    path = os.path.join(GOLD, name)
-    np.savez_compressed(path, **out)
-    print(f'{name}: {len(out)} arrays, {os.path.getsize(path) / 1024:.1f} KiB')
+    stem = name[:-len('.npz')]
+    for f in os.listdir(GOLD):
+        if f.startswith(stem + '.') and f[len(stem) + 1:-len('.npz')].isdigit():
+            os.remove(os.path.join(GOLD, f))
+    for i, part in enumerate(split_parts(out)):
+        pname = name if i == 0 else f'{stem}.{i}.npz'
+        path = os.path.join(GOLD, pname)
+        np.savez_compressed(path, **part)
+        print(f'{pname}: {len(part)} arrays, {os.path.getsize(path) / 1024:.1f} KiB')
 
 
 def state_np(module, prefix):

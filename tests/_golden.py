@@ -11,10 +11,20 @@ KEYS = ('x', 'upper_index', 'lower_index', 'shared_boundaries', 'shared_cobounda
         'boundary_index', 'y', 'batch')
 
 
+def parts(name):
+    """<stem>.npz and, for a fixture of more than 1 MiB, <stem>.1.npz, <stem>.2.npz, ... (oracle/gen_golden.py:save)."""
+    stem = name[:-len('.npz')]
+    extra = [f for f in os.listdir(GOLD) if f.startswith(stem + '.') and f[len(stem) + 1:-len('.npz')].isdigit()]
+    return [name] + sorted(extra, key=lambda f: int(f[len(stem) + 1:-len('.npz')]))
+
+
 @lru_cache(maxsize=None)
 def load(name):
-    with np.load(os.path.join(GOLD, name)) as z:
-        return {k: z[k] for k in z.files}
+    out = {}
+    for part in parts(name):
+        with np.load(os.path.join(GOLD, part)) as z:
+            out.update({k: z[k] for k in z.files})
+    return out
 
 
 def T(a):

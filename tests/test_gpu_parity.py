@@ -2848,7 +2848,7 @@ def test_bench_multi_rank_control_flow_on_one_gpu(tmp_path, world, with_train):
                CWN_BENCH_SKIP='concurrent,full,eager' + ('' if with_train else ',train'))
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(world),
            '--master-addr', '127.0.0.1', '--master-port', str(port), os.path.join(root, 'bench.py'),
-           '--gpus', str(world), '--steps', '8', '--warmup', '2', '--no-cpu', '--kernel-reps', '4', '--num-batches', '2']
+           '--gpus', str(world), '--steps', '8', '--warmup', '2', '--full', '--no-cpu', '--kernel-reps', '4', '--num-batches', '2']
     out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{')]

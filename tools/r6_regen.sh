@@ -30,7 +30,7 @@ cp profiles/r6_kernel_avg.json "$OUT/r6_kernel_avg.json"
 bash tools/prof_train.sh 128 200 > /dev/null 2>&1; cp gpurun_out/prof_train_128.md "$OUT/r6_${TAG}_train_step.md"
 head -8 "$OUT/r6_${TAG}_train_step.md" | cut -c1-140
 SECONDS=0
-timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/r6_${TAG}_bench_line.json" 2> "$OUT/r6_${TAG}_bench_zinc.err"; echo "bench wall ${SECONDS}s, line $(wc -c < "$OUT/r6_${TAG}_bench_line.json") bytes"
+timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/r6_${TAG}_bench_line.json" 2> "$OUT/r6_${TAG}_bench_zinc.err"; echo "bench wall ${SECONDS}s, line $(wc -c < "$OUT/r6_${TAG}_bench_line.json") bytes"
 cp bench_detail.json "$OUT/r6_${TAG}_bench_zinc.json"
 python - <<PY
 import json

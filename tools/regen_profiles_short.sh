@@ -8,8 +8,8 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 python -m pytest tests -m gpu -q -rP 2>&1 | grep -E "^\[gate\]|^\[invariance\]| passed| failed|^FAILED|^ERROR" > "$OUT/r2_${TAG}_pytest_gpu.txt"; tail -1 "$OUT/r2_${TAG}_pytest_gpu.txt"
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -1
-python bench.py > "$OUT/r2_${TAG}_bench_zinc.json" 2> /dev/null
-CWN_BENCH_SKIP=eager,concurrent,train python bench.py --batch 8192 --num-batches 1 --steps 20 --warmup 3 --no-cpu > "$OUT/r2_${TAG}_bench_zinc_batch8192.json" 2> /dev/null
+python bench.py --full > "$OUT/r2_${TAG}_bench_zinc.json" 2> /dev/null
+CWN_BENCH_SKIP=eager,concurrent,train python bench.py --full --batch 8192 --num-batches 1 --steps 20 --warmup 3 --no-cpu > "$OUT/r2_${TAG}_bench_zinc_batch8192.json" 2> /dev/null
 for w in zinc zinc_batch8192; do tail -1 "$OUT/r2_${TAG}_bench_$w.json" | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('$w', d['value'], d['ms_per_step'], d['roofline']['kernel'][:16], d['roofline']['frac'], (d.get('roofline_other') or {}).get('frac'), (d.get('roofline_step') or {}).get('frac'), (d.get('cpu_baseline') or {}).get('value'))"; done
