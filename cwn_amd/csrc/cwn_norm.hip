@@ -519,10 +519,12 @@ extern "C" int cwn_norm_bwd_f32(const cwn_norm_desc* descs, int n, int accumulat
 // caller), so the launch is graph-capturable.
 namespace {
 
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                   float* __restrict__ m, float* __restrict__ v, int64_t n,
-                                                   float lr, float b1, float b2, float eps, float wd,
-                                                   const int32_t* __restrict__ step, const int64_t* __restrict__ active) {
+// the body of both launches: hyperparameters as kernel arguments (cwn_adam_f32) or read from a device record
+// (cwn_adam_dev_f32) -- the same values give the same bits
+__device__ __forceinline__ void adam_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                          float* __restrict__ v, int64_t n, float lr, float b1, float b2, float eps,
+                                          float wd, const int32_t* __restrict__ step,
+                                          const int64_t* __restrict__ active) {
     if (active != nullptr && *active <= 0) return;       // (uniform) an empty batch of a static epoch: the step changes nothing
     const float t = (float)*step;
     const float bc1 = 1.0f - powf(b1, t), bc2_sqrt = sqrtf(1.0f - powf(b2, t));
@@ -564,6 +566,24 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     }
 }
 
+__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                   float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                                   float lr, float b1, float b2, float eps, float wd,
+                                                   const int32_t* __restrict__ step, const int64_t* __restrict__ active) {
+    adam_body(p, g, m, v, n, lr, b1, b2, eps, wd, step, active);
+}
+
+// the record is read when the launch RUNS: a replayed graph takes the values the record holds at the replay (the
+// 32-byte record is one scalar load per wave)
+__global__ __launch_bounds__(256) void adam_dev_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                       float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                                       const cwn_adam_hyper* __restrict__ hyper,
+                                                       const int32_t* __restrict__ step,
+                                                       const int64_t* __restrict__ active) {
+    const cwn_adam_hyper h = *hyper;
+    adam_body(p, g, m, v, n, h.lr, h.beta1, h.beta2, h.eps, h.weight_decay, step, active);
+}
+
 }  // namespace
 
 extern "C" int cwn_adam_f32(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
@@ -577,6 +597,19 @@ extern "C" int cwn_adam_f32(float* p, const float* g, float* m, float* v, int64_
     if (blocks >= INT32_MAX) return CWN_ERR_TOO_LARGE;
     adam_kernel<<<dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_>>>(p, g, m, v, n, lr, beta1, beta2,
                                                                                  eps, weight_decay, step, active);
+    return hipGetLastError() == hipSuccess ? CWN_OK : CWN_ERR_LAUNCH;
+}
+
+extern "C" int cwn_adam_dev_f32(float* p, const float* g, float* m, float* v, int64_t n, const cwn_adam_hyper* hyper,
+                                const int32_t* step, const int64_t* active, cwn_stream_t stream_) {
+    if (n < 0) return CWN_ERR_BAD_ARG;
+    if (n == 0) return CWN_OK;
+    if (p == nullptr || g == nullptr || m == nullptr || v == nullptr || hyper == nullptr || step == nullptr)
+        return CWN_ERR_BAD_ARG;
+    if ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v) | ((uintptr_t)hyper)) & 15u) return CWN_ERR_ALIGN;
+    const int64_t threads = (n + 3) / 4, blocks = (threads + 255) / 256;
+    if (blocks >= INT32_MAX) return CWN_ERR_TOO_LARGE;
+    adam_dev_kernel<<<dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_>>>(p, g, m, v, n, hyper, step, active);
     return hipGetLastError() == hipSuccess ? CWN_OK : CWN_ERR_LAUNCH;
 }
 

@@ -65,7 +65,10 @@ class FlatGradBucket:
     def __init__(self, params: Iterable[torch.nn.Parameter], stage_of: Optional[dict] = None,
                  n_stages: int = 1):
         """`stage_of`: {id(parameter): stage in [0, n_stages)} (StagedBackward.stages); missing = stage 0."""
-        ps = [p for p in params if p.requires_grad]
+        # the caller's order (model.parameters()), frozen parameters included: the indices of an optimizer state_dict
+        # (train.FlatAdam) follow it, not the staged layout below
+        self.given = list(params)
+        ps = [p for p in self.given if p.requires_grad]
         if not ps:
             raise ValueError('no trainable parameters')
         if stage_of is None:

@@ -415,7 +415,7 @@ class StaticTrainStep(TrainStep):
             self._graphs[key] = (g, losses)
             self.sb.cursor.copy_(cur)
         g, losses = self._graphs[key]
-        ops.weights_changed()
+        self._before_replay()
         g.replay()
         return losses
 
@@ -630,6 +630,13 @@ class RoutedTrainStep:
         # backward item tables are cut, and StaticBatch.fits() -- the router's test -- knows what one workgroup holds
         self.ta.step()
         self.tb.step()
+
+    def state_dict(self) -> dict:
+        """TrainStep.state_dict of the shared model and optimizer."""
+        return self.ta.state_dict()
+
+    def load_state_dict(self, state: dict) -> None:
+        self.ta.load_state_dict(state)
 
     def run_epoch(self, batches: Sequence[np.ndarray], keep_losses: bool = True) -> List[Optional[torch.Tensor]]:
         a, b, na, nb = self.router.set_epoch(batches)

@@ -5,7 +5,7 @@ out for MI355X:
   * all gradients live in ONE flat fp32 buffer (dist.FlatGradBucket): zeroing them is one fill,
     the weight-gradient kernels accumulate straight into it (ops.ACCUMULATE_INTO_GRAD), and the
     data-parallel collective of a step is a single RCCL all-reduce of that buffer;
-  * the optimiser is Adam over ONE flat parameter buffer (`FlatAdam`, cwn_adam_f32: one launch
+  * the optimiser is Adam over ONE flat parameter buffer (`FlatAdam`, cwn_adam_dev_f32: one launch
     for the whole model; torch's fused multi-tensor Adam needs 8 x 22 us for the 265 tensors);
   * the whole step -- plan reuse, forward, backward, optimiser -- is captured once per distinct batch
     in a hipGraph and replayed (world size 1);
@@ -96,34 +96,63 @@ def fused_loss(task_type: str, pred: torch.Tensor, y: torch.Tensor) -> Optional[
     return _FusedMeanLoss.apply(pred, y, kind)
 
 
-class FlatAdam:
+class FlatAdam(torch.optim.Optimizer):
     """torch.optim.Adam semantics (no amsgrad) on flat buffers: the parameters of `bucket` are
     re-homed into one contiguous fp32 buffer (their `.data` become views of it, so modules keep
     working and state_dicts are unchanged), the moments are two more flat buffers, and `step()` is
     one kernel launch reading the bucket's flat gradient.  Graph-capturable (the step counter
-    lives on the device)."""
+    lives on the device).
+
+    A torch optimizer with ONE param group in torch.optim.Adam's format: learning-rate schedulers drive
+    `param_groups[0]['lr']`, and the launch (cwn_adam_dev_f32) reads lr / betas / eps / weight_decay from a
+    device record (`hyper`) that `sync()` rewrites, stream-ordered, whenever the group has changed -- before
+    every eager step and before every replay of a captured graph that holds one (the step drivers of
+    train.py / static_graph.py), so a replay takes the current values without a re-capture.
+    `state_dict()` / `load_state_dict()` speak torch.optim.Adam's format, indexed in the order of the
+    parameters the bucket was built from."""
 
     def __init__(self, bucket: FlatGradBucket, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 0.0):
-        self.bucket, self.lr, self.betas, self.eps, self.weight_decay = bucket, lr, betas, eps, weight_decay
+                 weight_decay: float = 0.0, amsgrad: bool = False, maximize: bool = False):
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize,
+                        foreach=None, capturable=False, differentiable=False, fused=None, decoupled_weight_decay=False)
+        self.bucket = bucket
+        super().__init__(list(bucket.given), defaults)
         g = bucket.flat
         self.flat_p = torch.empty_like(g)
         self.flat_p.zero_()                     # the pad elements between parameters (bucket.offsets) stay zero
+        self._offset = {}                       # id(parameter) -> its offset in the flat buffers
         with torch.no_grad():
             for p, off in zip(bucket.params, bucket.offsets):
                 view = self.flat_p[off:off + p.numel()].view_as(p)
                 view.copy_(p.data)
                 p.data = view
+                self._offset[id(p)] = off
         self.exp_avg = torch.zeros_like(g)
         self.exp_avg_sq = torch.zeros_like(g)
         self.t = torch.zeros(1, dtype=torch.int32, device=g.device)
+        # cwn_adam_hyper {lr, beta1, beta2, eps, weight_decay, pad[3]}: what the launch reads; `_written` = the values it holds
+        self.hyper = torch.zeros(8, dtype=torch.float32, device=g.device)
+        self._written: Optional[tuple] = None
         # a device int64 (or None): the complexes of the batch this step belongs to -- a step on an EMPTY batch of a static
         # epoch changes nothing (static_graph.StaticTrainStep sets it per slot)
         self.active: Optional[torch.Tensor] = None
         self.counted = False        # the next step()'s count has been taken by the step's opening launch (TrainStep._begin)
-        # what TrainStep snapshots around its warm-up
-        self.param_groups = [{'params': list(bucket.params)}]
-        self.state = {}
+
+    def add_param_group(self, param_group: dict) -> None:
+        if self.param_groups:
+            raise NotImplementedError('FlatAdam: one param group (the flat buffers hold every parameter of the bucket)')
+        for k in ('amsgrad', 'maximize', 'decoupled_weight_decay'):
+            if param_group.get(k, self.defaults.get(k)):
+                raise NotImplementedError(f'FlatAdam: {k}=True')
+        super().add_param_group(param_group)
+
+    # the hyperparameters as attributes (the form of the first FlatAdam): the param group's values
+    lr = property(lambda self: self.param_groups[0]['lr'], lambda self, v: self.param_groups[0].__setitem__('lr', v))
+    betas = property(lambda self: self.param_groups[0]['betas'],
+                     lambda self, v: self.param_groups[0].__setitem__('betas', v))
+    eps = property(lambda self: self.param_groups[0]['eps'], lambda self, v: self.param_groups[0].__setitem__('eps', v))
+    weight_decay = property(lambda self: self.param_groups[0]['weight_decay'],
+                            lambda self, v: self.param_groups[0].__setitem__('weight_decay', v))
 
     def state_tensors(self) -> List[torch.Tensor]:
         return [self.exp_avg, self.exp_avg_sq, self.t]
@@ -131,8 +160,36 @@ class FlatAdam:
     def zero_grad(self, set_to_none: bool = False):
         self.bucket.zero_()
 
+    # ---- the device record ------------------------------------------------------------------------------------------------
+    def _values(self) -> tuple:
+        grp = self.param_groups[0]
+        if grp.get('amsgrad') or grp.get('maximize') or grp.get('decoupled_weight_decay'):
+            raise NotImplementedError('FlatAdam: amsgrad / maximize / decoupled_weight_decay')
+        b1, b2 = grp['betas']
+        return (float(grp['lr']), float(b1), float(b2), float(grp['eps']), float(grp['weight_decay']))
+
+    def sync(self) -> bool:
+        """Write the param group's lr / betas / eps / weight_decay into the device record if they changed since the last
+        write: a copy from pinned memory on the current stream (no host wait), so launches already queued keep the old
+        values and everything behind it -- the next replay -- sees the new ones.  Not inside a capture (the record is what
+        the captured launch reads; a captured copy would bake the values in).  True when it wrote."""
+        vals = self._values()
+        if vals == self._written:
+            return False
+        src = torch.tensor(vals + (0.0, 0.0, 0.0), dtype=torch.float32)
+        if self.hyper.is_cuda:
+            self.hyper.copy_(src.pin_memory(), non_blocking=True)
+        else:
+            self.hyper.copy_(src)
+        self._written = vals
+        return True
+
     @torch.no_grad()
-    def step(self):
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
         if self.counted:                 # (the step's opening launch has advanced the counter: cwn_step_begin)
             self.counted = False
         elif self.active is None:
@@ -140,11 +197,83 @@ class FlatAdam:
         else:
             self.t.add_((self.active > 0).to(torch.int32).view(1))
         g = self.bucket.flat
-        _ffi.check(_ffi.lib().cwn_adam_f32(
+        if not torch.cuda.is_current_stream_capturing():
+            self.sync()
+        _ffi.check(_ffi.lib().cwn_adam_dev_f32(
             self.flat_p.data_ptr(), g.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-            g.numel(), self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay,
-            self.t.data_ptr(), _ffi.ptr(self.active), _ffi.stream_ptr(g.device)), 'cwn_adam_f32')
+            g.numel(), self.hyper.data_ptr(), self.t.data_ptr(), _ffi.ptr(self.active), _ffi.stream_ptr(g.device)),
+            'cwn_adam_dev_f32')
         ops.weights_changed()        # the parameters were written through a raw pointer: tensor versions did not move
+        return loss
+
+    # ---- checkpoints in torch.optim.Adam's format ---------------------------------------------------------------------------
+    def state_dict(self) -> dict:
+        """torch.optim.Adam's state_dict: state[i] = {step, exp_avg, exp_avg_sq} (copies, shaped like parameter i) for every
+        trainable parameter once a step has been taken, i in the order of the parameters the bucket was built from."""
+        grp = self.param_groups[0]
+        t = int(self.t.item())
+        state = {}
+        if t > 0:
+            for i, p in enumerate(grp['params']):
+                off = self._offset.get(id(p))
+                if off is None:                  # frozen: no gradient, no state (as torch's)
+                    continue
+                n = p.numel()
+                state[i] = {'step': torch.tensor(float(t), dtype=torch.float32),
+                            'exp_avg': self.exp_avg[off:off + n].view_as(p).clone(),
+                            'exp_avg_sq': self.exp_avg_sq[off:off + n].view_as(p).clone()}
+        packed = {k: v for k, v in grp.items() if k != 'params'}
+        packed['params'] = list(range(len(grp['params'])))
+        return {'state': state, 'param_groups': [packed]}
+
+    def load_state_dict(self, state_dict: dict) -> None:
+        """Load a state_dict of torch.optim.Adam (or of a FlatAdam) over the same parameters IN PLACE: the moments are
+        copied into the flat buffers, the counter into `t`, the group's hyperparameters into the group (the device record
+        follows at the next sync) -- captured graphs stay valid.  A parameter without state starts from zero moments."""
+        groups = state_dict['param_groups']
+        if len(groups) != 1:
+            raise NotImplementedError(f'FlatAdam: one param group (the state_dict has {len(groups)})')
+        saved = groups[0]
+        params = self.param_groups[0]['params']
+        if len(saved['params']) != len(params):
+            raise ValueError(f'FlatAdam.load_state_dict: {len(saved["params"])} parameters in the state_dict, '
+                             f'{len(params)} here')
+        for k in ('amsgrad', 'maximize', 'decoupled_weight_decay'):
+            if saved.get(k):
+                raise NotImplementedError(f'FlatAdam: {k}=True')
+        states = state_dict['state']
+        found = {}
+        for pos, p in enumerate(params):
+            st = states.get(saved['params'][pos])
+            if not st:
+                continue
+            if self._offset.get(id(p)) is None:
+                raise ValueError(f'FlatAdam.load_state_dict: parameter {pos} is frozen here but has optimizer state')
+            for key in ('exp_avg', 'exp_avg_sq'):
+                if key not in st or st[key].numel() != p.numel():
+                    raise ValueError(f'FlatAdam.load_state_dict: parameter {pos}: {key} of shape '
+                                     f'{tuple(st[key].shape) if key in st else None}, the parameter is {tuple(p.shape)}')
+            found[pos] = st
+        steps = {float(st['step']) for st in found.values()}
+        if len(steps) > 1:
+            raise ValueError('FlatAdam.load_state_dict: the parameters are at different steps '
+                             f'({sorted(steps)}); FlatAdam keeps ONE step counter for the whole model')
+        t = int(round(steps.pop())) if steps else 0
+        with torch.no_grad():
+            for pos, p in enumerate(params):
+                off = self._offset.get(id(p))
+                if off is None:
+                    continue
+                n = p.numel()
+                st = found.get(pos)
+                for buf, key in ((self.exp_avg, 'exp_avg'), (self.exp_avg_sq, 'exp_avg_sq')):
+                    if st is None:
+                        buf[off:off + n].zero_()
+                    else:
+                        buf[off:off + n].copy_(st[key].detach().reshape(-1))
+            self.t.fill_(t)
+        self.param_groups[0].update({k: v for k, v in saved.items() if k != 'params'})
+        self.counted = False
 
 
 class TrainStep:
@@ -500,9 +629,18 @@ class TrainStep:
                 losses = [self._eager(i) for i in seq]
             self._graphs[key] = (g, losses)
         g, losses = self._graphs[key]
-        ops.weights_changed()
+        self._before_replay()
         g.replay()
         return losses
+
+    def _before_replay(self) -> None:
+        """Ahead of a replay that holds optimizer steps: a replay runs no Python -- caches of packed weights / folded BatchNorm
+        must not survive it, the optimizer's device record takes the param group's current values (a scheduler may have
+        moved lr: FlatAdam.sync, stream-ordered), and the optimizer counts as stepped for the scheduler's order check."""
+        ops.weights_changed()
+        if isinstance(self.opt, FlatAdam):
+            self.opt.sync()
+        self.opt._opt_called = True
 
     # ---- the step ----------------------------------------------------------------------------
     def step(self, i: int) -> torch.Tensor:
@@ -511,7 +649,7 @@ class TrainStep:
         if i not in self._graphs:
             self._graphs[i] = self._capture(i)
         pieces, g2, loss = self._graphs[i]
-        ops.weights_changed()        # a replay runs no Python: caches of packed weights / folded BatchNorm must not survive it
+        self._before_replay()
         if g2 is None:
             pieces[0].replay()
             return loss
@@ -526,3 +664,25 @@ class TrainStep:
             self.bucket.finish()
         g2.replay()
         return loss
+
+    # ---- checkpoints ---------------------------------------------------------------------------
+    def state_dict(self) -> dict:
+        """What resuming the training needs (torch.save-able): the model's state_dict (BatchNorm running statistics
+        included), the optimizer's (FlatAdam: torch.optim.Adam's format) and the device dropout record {seed, step} (None
+        when no dropout has run on the device).  Copies: later steps do not change them."""
+        dev = next(self.model.parameters()).device
+        ds = ops._drop_states.get(dev)
+        return {'model': {k: v.detach().clone() for k, v in self.model.state_dict().items()},
+                'optimizer': self.opt.state_dict(),
+                'dropout': None if ds is None else ds.detach().cpu().clone()}
+
+    def load_state_dict(self, state: dict) -> None:
+        """Load a state_dict() IN PLACE -- into a fresh step before its first capture, or into one that has captured (its
+        graphs stay valid: every tensor they read is overwritten, none is replaced)."""
+        with torch.no_grad():
+            self.model.load_state_dict(state['model'])
+        self.opt.load_state_dict(state['optimizer'])
+        if state.get('dropout') is not None:
+            dev = next(self.model.parameters()).device
+            ops.dropout_state(dev).copy_(torch.as_tensor(state['dropout'], dtype=torch.int64))
+        ops.weights_changed()          # prepared launches / packed weights / folded BatchNorm follow the loaded values

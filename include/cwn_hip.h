@@ -1288,6 +1288,21 @@ int cwn_axpy_eps_f32(const cwn_axpy_desc* descs_host, int n, cwn_stream_t stream
 int cwn_adam_f32(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
                  float beta2, float eps, float weight_decay, const int32_t* step, const int64_t* active, cwn_stream_t stream);
 
+/* ... with the hyperparameters in a DEVICE record (cwn_amd/train.py::FlatAdam: the optimizer's param group, written
+ * stream-ordered when a learning-rate scheduler changes it): the launch reads *hyper when it runs, so a captured graph
+ * replays with the values the record holds at the replay, not those of the capture.  Same arithmetic as cwn_adam_f32
+ * (bitwise equal for the same values), same `step` / `active` conventions; hyper 16-B aligned. */
+typedef struct cwn_adam_hyper {
+    float lr;
+    float beta1;
+    float beta2;
+    float eps;
+    float weight_decay;
+    float pad[3];        /* 32 bytes */
+} cwn_adam_hyper;
+int cwn_adam_dev_f32(float* p, const float* g, float* m, float* v, int64_t n, const cwn_adam_hyper* hyper,
+                     const int32_t* step, const int64_t* active, cwn_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Graph -> 2-complex lifting on the HOST (integer preprocessing that produces the path's inputs;
  * the reference does it through graph-tool and gudhi):
