@@ -20,7 +20,7 @@ REDUCE = {'add': 0, 'sum': 0, 'mean': 1, 'max': 2}
 ABI_VERSION = 24
 
 EXPORTS = ('cwn_abi_version', 'cwn_error_string', 'cwn_target_arch', 'cwn_csr_workspace_bytes',
-           'cwn_csr_build', 'cwn_csr_long_rows', 'cwn_gather_rows_f32', 'cwn_aggregate_f32', 'cwn_gemm_f32', 'cwn_gemm_would_split', 'cwn_gemm_packed_weight_bytes', 'cwn_gemm_pack_weights_f32', 'cwn_update_mlp_f32', 'cwn_update_mlp3_f32', 'cwn_update_mlp_max_rows', 'cwn_update_mlp_packed_weight_bytes', 'cwn_update_mlp_pack_weights_f32', 'cwn_update_mlp_pack_weights_many_f32', 'cwn_update_mlp_pack_weights_t_many_f32', 'cwn_update_mlp_pack_weights_both_many_f32', 'cwn_layer_pack_weights_both_many_f32', 'cwn_dense_stage_f32', 'cwn_dense_stage_ex_f32', 'cwn_dense_stage_bwd_f32', 'cwn_layer_fused_f32', 'cwn_layer_fused_lds_bytes', 'cwn_layer_variant_lds_bytes', 'cwn_layer_round_rows', 'cwn_layer_variant_round_rows', 'cwn_layer_items_check', 'cwn_layer_items_build', 'cwn_layer_pack_weights_f32', 'cwn_layer_pack_weights_many_f32', 'cwn_layer_pack_weights_t_many_f32', 'cwn_layer_bwd_f32', 'cwn_layer_bwd_lds_bytes', 'cwn_layer_bwd_items_build', 'cwn_layer_bwd_own_f32', 'cwn_layer_packed_weight_bytes', 'cwn_collate', 'cwn_collate_slots', 'cwn_collate_tables', 'cwn_collate_tables_len', 'cwn_collate_guard', 'cwn_layer_items_build_dev', 'cwn_layer_bwd_items_build_dev',
+           'cwn_csr_build', 'cwn_csr_long_rows', 'cwn_gather_rows_f32', 'cwn_aggregate_f32', 'cwn_gather_rows_f64', 'cwn_aggregate_f64', 'cwn_gemm_f32', 'cwn_gemm_would_split', 'cwn_gemm_packed_weight_bytes', 'cwn_gemm_pack_weights_f32', 'cwn_update_mlp_f32', 'cwn_update_mlp3_f32', 'cwn_update_mlp_max_rows', 'cwn_update_mlp_packed_weight_bytes', 'cwn_update_mlp_pack_weights_f32', 'cwn_update_mlp_pack_weights_many_f32', 'cwn_update_mlp_pack_weights_t_many_f32', 'cwn_update_mlp_pack_weights_both_many_f32', 'cwn_layer_pack_weights_both_many_f32', 'cwn_dense_stage_f32', 'cwn_dense_stage_ex_f32', 'cwn_dense_stage_bwd_f32', 'cwn_layer_fused_f32', 'cwn_layer_fused_lds_bytes', 'cwn_layer_variant_lds_bytes', 'cwn_layer_round_rows', 'cwn_layer_variant_round_rows', 'cwn_layer_items_check', 'cwn_layer_items_build', 'cwn_layer_pack_weights_f32', 'cwn_layer_pack_weights_many_f32', 'cwn_layer_pack_weights_t_many_f32', 'cwn_layer_bwd_f32', 'cwn_layer_bwd_lds_bytes', 'cwn_layer_bwd_items_build', 'cwn_layer_bwd_own_f32', 'cwn_layer_packed_weight_bytes', 'cwn_collate', 'cwn_collate_slots', 'cwn_collate_tables', 'cwn_collate_tables_len', 'cwn_collate_guard', 'cwn_layer_items_build_dev', 'cwn_layer_bwd_items_build_dev',
            'cwn_bn_finalize_f32', 'cwn_step_begin', 'cwn_axpy_eps_f32', 'cwn_dropout_f32', 'cwn_embed_front_bwd_f32', 'cwn_norm_act_f32', 'cwn_norm_bwd_reduce_f32', 'cwn_norm_bwd_apply_f32', 'cwn_norm_bwd_f32',
            'cwn_gemm_tn_f32', 'cwn_gemm_tn_workspace_bytes', 'cwn_adam_f32', 'cwn_adam_dev_f32', 'cwn_loss_f32', 'cwn_loss_cols_f32', 'cwn_embedding_fwd_f32', 'cwn_embedding_bwd_f32', 'cwn_embed_front_f32', 'cwn_head_f32', 'cwn_head_bwd_f32', 'cwn_head_pool_floats', 'cwn_lift_create', 'cwn_lift_size', 'cwn_lift_copy', 'cwn_lift_destroy',
            'cwn_lift_many', 'cwn_lift_many_count', 'cwn_lift_many_lengths', 'cwn_lift_many_copy', 'cwn_lift_many_destroy')
@@ -35,6 +35,7 @@ class CsrDesc(C.Structure):
 
 
 class AggDesc(C.Structure):
+    """cwn_agg_desc and cwn_agg_desc_f64 (include/cwn_hip.h): one layout, every data pointer is a void*."""
     _fields_ = [('rowptr', C.c_void_p), ('ia', C.c_void_p), ('ib', C.c_void_p),
                 ('A', C.c_void_p), ('B', C.c_void_p), ('self_x', C.c_void_p),
                 ('eps', C.c_void_p), ('self_pre', C.c_void_p), ('out', C.c_void_p),
@@ -315,6 +316,10 @@ def lib():
                                       C.c_void_p, C.c_void_p]
     L.cwn_aggregate_f32.restype = C.c_int
     L.cwn_aggregate_f32.argtypes = [C.POINTER(AggDesc), C.c_int, C.c_void_p]
+    L.cwn_gather_rows_f64.restype = C.c_int
+    L.cwn_gather_rows_f64.argtypes = L.cwn_gather_rows_f32.argtypes
+    L.cwn_aggregate_f64.restype = C.c_int
+    L.cwn_aggregate_f64.argtypes = [C.POINTER(AggDesc), C.c_int, C.c_void_p]
     L.cwn_gemm_f32.restype = C.c_int
     L.cwn_gemm_f32.argtypes = [C.POINTER(GemmDesc), C.c_int, C.c_void_p]
     L.cwn_layer_fused_f32.restype = C.c_int
@@ -528,15 +533,23 @@ def require_gpu(t: torch.Tensor, name: str):
                        'Use oracle/ for CPU checks.')
 
 
-def aggregate(descs: Sequence[AggDesc], device) -> None:
-    """One kernel launch for up to MAX_DESCS descriptors; more are split into several calls."""
+FLOAT_DTYPES = (torch.float32, torch.float64)     # what the aggregate and gather kernels compute in
+
+
+def aggregate(descs: Sequence[AggDesc], device, dtype: torch.dtype = torch.float32) -> None:
+    """One kernel launch for up to MAX_DESCS descriptors; more are split into several calls.  Every operand of
+    every descriptor has the one `dtype` (float32 or float64)."""
     L = lib()
     s = stream_ptr(device)
+    if dtype not in FLOAT_DTYPES:
+        raise TypeError(f'aggregate computes in float32 or float64, not {dtype}')
+    name = 'cwn_aggregate_f32' if dtype == torch.float32 else 'cwn_aggregate_f64'
+    fn = getattr(L, name)
     _set_dyn(descs, 'n_dst')
     for i in range(0, len(descs), MAX_DESCS):
         chunk = descs[i:i + MAX_DESCS]
         arr = (AggDesc * len(chunk))(*chunk)
-        check(L.cwn_aggregate_f32(arr, len(chunk), s), 'cwn_aggregate_f32')
+        check(fn(arr, len(chunk), s), name)
 
 
 def gemm(descs: Sequence[GemmDesc], device) -> None:
@@ -556,10 +569,12 @@ def gemm_would_split(descs: Sequence[GemmDesc]) -> bool:
 
 
 def gather_rows(src: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
-    out = torch.empty(idx.numel(), src.size(1), dtype=torch.float32, device=src.device)
-    check(lib().cwn_gather_rows_f32(src.data_ptr(), src.size(0), src.size(1), idx.data_ptr(),
-                                    idx.numel(), out.data_ptr(), stream_ptr(src.device)),
-          'cwn_gather_rows_f32')
+    if src.dtype not in FLOAT_DTYPES:
+        raise TypeError(f'gather_rows takes float32 or float64 rows, not {src.dtype}')
+    name = 'cwn_gather_rows_f32' if src.dtype == torch.float32 else 'cwn_gather_rows_f64'
+    out = torch.empty(idx.numel(), src.size(1), dtype=src.dtype, device=src.device)
+    check(getattr(lib(), name)(src.data_ptr(), src.size(0), src.size(1), idx.data_ptr(),
+                               idx.numel(), out.data_ptr(), stream_ptr(src.device)), name)
     return out
 
 

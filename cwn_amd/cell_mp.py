@@ -69,6 +69,12 @@ def dense(t):
     return t.tensor() if isinstance(t, IndexedRows) else t
 
 
+def _zero_dtype(x) -> torch.dtype:
+    """The dtype of the zero rows that stand for an absent adjacency: that of the cell features when the engine computes
+    in it (float32 / float64), else float32."""
+    return x.dtype if isinstance(x, Tensor) and x.dtype == torch.float64 else torch.float32
+
+
 class CochainMessagePassing(torch.nn.Module):
     """See the module docstring; argument meaning as in mp/cell_mp.py:41-91."""
 
@@ -327,12 +333,12 @@ class CochainMessagePassing(torch.nn.Module):
             for a, width in (('up', self.up_msg_size), ('down', self.down_msg_size),
                              ('boundary', self.boundary_msg_size)):
                 if outs[a] is None and a not in fused_names:
-                    fused.append(ops.Stream(adj=None, n_dst=x.size(0), width=int(width)))
+                    fused.append(ops.Stream(adj=None, n_dst=x.size(0), width=int(width), dtype=_zero_dtype(x)))
                     fused_names.append(a)
         if fused:
             if all(st.adj is None for st in fused):
                 for a, st in zip(fused_names, fused):
-                    outs[a] = ops.zeros_rows(st.n_dst, st.width, x.device)
+                    outs[a] = ops.zeros_rows(st.n_dst, st.width, x.device, _zero_dtype(x))
             else:
                 for a, o in zip(fused_names, ops.aggregate_many(fused)):
                     outs[a] = o
@@ -415,11 +421,11 @@ class CochainMessagePassing(torch.nn.Module):
                boundary_inputs: Optional[Tensor], x: Tensor):
         """mp/cell_mp.py:511-524 (zeros are created on the device directly)."""
         if up_inputs is None:
-            up_inputs = ops.zeros_rows(x.size(0), self.up_msg_size, x.device)
+            up_inputs = ops.zeros_rows(x.size(0), self.up_msg_size, x.device, _zero_dtype(x))
         if down_inputs is None:
-            down_inputs = ops.zeros_rows(x.size(0), self.down_msg_size, x.device)
+            down_inputs = ops.zeros_rows(x.size(0), self.down_msg_size, x.device, _zero_dtype(x))
         if boundary_inputs is None:
-            boundary_inputs = ops.zeros_rows(x.size(0), self.boundary_msg_size, x.device)
+            boundary_inputs = ops.zeros_rows(x.size(0), self.boundary_msg_size, x.device, _zero_dtype(x))
         return up_inputs, down_inputs, boundary_inputs
 
 

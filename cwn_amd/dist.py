@@ -71,6 +71,12 @@ class FlatGradBucket:
         ps = [p for p in self.given if p.requires_grad]
         if not ps:
             raise ValueError('no trainable parameters')
+        for p in ps:
+            # (the flat buffers are read by float32 kernels -- cwn_adam_f32, the weight-gradient launches -- through raw
+            #  pointers: any other dtype would be reinterpreted, not converted)
+            if p.dtype != torch.float32:
+                raise TypeError(f'FlatGradBucket / FlatAdam hold float32 parameters only (got {p.dtype}); a float64 model '
+                                'trains with autograd and a torch.optim optimizer')
         if stage_of is None:
             n_stages, stages = 1, [0] * len(ps)
         else:

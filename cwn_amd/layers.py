@@ -28,7 +28,7 @@ from torch import Tensor
 from torch.nn import BatchNorm1d as BN, Linear, ReLU, Sequential
 
 from . import ops
-from .cell_mp import CochainMessagePassing, CochainMessagePassingParams, IndexedRows, dense
+from .cell_mp import CochainMessagePassing, CochainMessagePassingParams, IndexedRows, _zero_dtype, dense
 from .csr import Adjacency, cached_adjacency
 
 
@@ -359,8 +359,8 @@ class CINCochainConv(CochainMessagePassing):
         groups the plans of all dimensions into one GEMM launch + one aggregation launch), or None
         when the fused path does not apply."""
         x = cochain.x
-        if torch.is_grad_enabled() or x is None or not x.is_cuda:
-            return None
+        if torch.is_grad_enabled() or x is None or not x.is_cuda or x.dtype != torch.float32:
+            return None                  # (the products are fp32 MFMA GEMMs: float64 takes propagate() and the torch modules)
         if (self.aggr_up or 'add') != 'add' or (self.aggr_down or 'add') != 'add':
             return None
         n, F = x.size(0), x.size(1)
@@ -401,7 +401,7 @@ class CINCochainConv(CochainMessagePassing):
             if scale is None:
                 total = total + out
             else:
-                deg = (adj.rowptr[1:] - adj.rowptr[:-1]).to(torch.float32).unsqueeze(1)
+                deg = (adj.rowptr[1:] - adj.rowptr[:-1]).to(out.dtype).unsqueeze(1)
                 total = total + out * scale + deg * shift
         return total
 
@@ -502,7 +502,7 @@ class CINCochainConv(CochainMessagePassing):
             if norm is None:
                 total = total + S
                 continue
-            deg = (adj.rowptr[1:] - adj.rowptr[:-1]).to(torch.float32).unsqueeze(1)
+            deg = (adj.rowptr[1:] - adj.rowptr[:-1]).to(S.dtype).unsqueeze(1)
             w = norm.weight.double() if norm.weight is not None else None
             if norm.training:
                 Q = outs[o]
@@ -653,8 +653,8 @@ class SparseCINCochainConv(CochainMessagePassing):
         adjacency).  SparseCINConv groups the specs of all dimensions into one MFMA launch."""
         x, up_attr = cochain.x, cochain.kwargs.get('up_attr')
         if (cochain.up_index is None or up_attr is None or self._up_kind() != 'cat_linear_relu'
-                or (self.aggr_up or 'add') != 'add'):
-            return []
+                or (self.aggr_up or 'add') != 'add' or x.dtype != torch.float32):
+            return []                    # (float64: _torch_products, behind the same fused stream)
         lin = self.msg_up_nn[1]
         F = x.size(1)
         attr_src, _ = _attr_operand(up_attr)
@@ -675,9 +675,9 @@ class SparseCINCochainConv(CochainMessagePassing):
         if kind == 'cat_linear_relu' and up_attr is not None and (self.aggr_up or 'add') == 'add':
             if ys is None:
                 specs = SparseCINCochainConv.gemm_specs(self, CochainMessagePassingParams(x, adj, up_attr=up_attr))
-                if not specs:
+                ys = ops.gemm_many(specs) if specs else _torch_products(self.msg_up_nn[1], x, up_attr)
+                if ys is None:
                     return None
-                ys = ops.gemm_many(specs)
             _, mode = _attr_operand(up_attr)
             return ops.Stream(adj=adj, n_dst=adj.n_dst, width=int(ys[0].size(1)), A=ys[0], B=ys[1],
                               msg_op=ops.MSG_RELU_A_PLUS_B, ib_mode=mode, self_x=self_x, eps=eps)
@@ -758,6 +758,19 @@ class SparseCINCochainConv(CochainMessagePassing):
             return self.forward_unfused(cochain)
         out_up, out_boundaries = ops.aggregate_many(sts)
         return self.finish(out_up, out_boundaries)
+
+
+def _torch_products(lin, x: Tensor, attr) -> Optional[List[Tensor]]:
+    """Y1 = X W[:, :F]^T + b and Y2 = X_attr W[:, F:]^T of a ReLU(Linear(cat(x_j, attr))) message for features the fp32 MFMA
+    GEMMs do not take (float64): the same split on torch.nn.functional.linear (rocBLAS), so that the message still runs as
+    the fused CWN_MSG_RELU_A_PLUS_B stream -- in float64 -- and no per-entry matrix is materialised.  None when the split
+    does not apply (float32 features reach here only after gemm_specs has refused their shape)."""
+    F = int(x.size(1))
+    src, _ = _attr_operand(attr)
+    if x.dtype != torch.float64 or lin.in_features != F + src.size(1):
+        return None
+    W = lin.weight
+    return [torch.nn.functional.linear(x, W[:, :F], lin.bias), torch.nn.functional.linear(src, W[:, F:])]
 
 
 def _update_mlp(layer_dim, hidden, graph_norm, act_module):
@@ -1090,8 +1103,8 @@ class SparseCINConv(torch.nn.Module):
         folded into the K-concatenation -- with eval-mode BatchNorm folded into the epilogue.
         Inference only (no autograd, running statistics); returns None when it does not apply and
         the caller runs the torch modules instead."""
-        if torch.is_grad_enabled():
-            return None
+        if torch.is_grad_enabled() or any(o.dtype != torch.float32 for o in outs):
+            return None                  # (float64: the torch modules)
         ent = _MLP_CACHE.get(self)
         if ent is not None:
             # the prepared launch of this layer's networks (ops.MlpLaunch): per call only the rows are looked at
@@ -1172,7 +1185,7 @@ class SparseCINConv(torch.nn.Module):
         Returns None when it does not apply (LayerNorm, custom networks, fewer than two cells in
         a dimension) and the caller runs the torch modules instead."""
         from . import dense_train as DT
-        if not torch.is_grad_enabled() or not FUSED_DENSE_TRAINING:
+        if not torch.is_grad_enabled() or not FUSED_DENSE_TRAINING or any(o.dtype != torch.float32 for o in outs):
             return None
         active = list(range(start, len(plans)))
         if not active or any(plans[d] is None for d in active) or len(outs) != 2 * len(active):
@@ -1305,7 +1318,7 @@ class CINppCochainConv(SparseCINCochainConv):
         default) or its network is another form."""
         x, attr = cochain.x, cochain.kwargs.get('down_attr')
         if (not self._down_active(cochain) or attr is None or self._down_kind() != 'cat_linear_relu'
-                or (self.aggr_down or 'add') != 'add'):
+                or (self.aggr_down or 'add') != 'add' or x.dtype != torch.float32):
             return []
         lin, F = self.msg_down_nn[1], x.size(1)
         src, _ = _attr_operand(attr)
@@ -1339,9 +1352,9 @@ class CINppCochainConv(SparseCINCochainConv):
                 yd = list(ys[n_up:]) if ys else []
                 if not yd:
                     specs = self._down_specs(cochain)
-                    if not specs:
+                    yd = ops.gemm_many(specs) if specs else _torch_products(self.msg_down_nn[1], x, attr)
+                    if yd is None:
                         return None
-                    yd = ops.gemm_many(specs)
                 _, mode = _attr_operand(attr)
                 down = ops.Stream(adj=adj, n_dst=adj.n_dst, width=int(yd[0].size(1)), A=yd[0], B=yd[1],
                                   msg_op=ops.MSG_RELU_A_PLUS_B, ib_mode=mode, self_x=x, eps=self.eps2)
@@ -1393,7 +1406,7 @@ class CINppCochainConv(SparseCINCochainConv):
             if cob_index is not None and cob_attr is not None:
                 out_cob = self.propagate_coboundary(cob_index, cob_attr, cochain.x.size(0))
             else:
-                out_cob = ops.zeros_rows(cochain.x.size(0), cochain.x.size(1), cochain.x.device)
+                out_cob = ops.zeros_rows(cochain.x.size(0), cochain.x.size(1), cochain.x.device, _zero_dtype(cochain.x))
             parts.append(self.update_coboundaries_nn(out_cob + (1 + self.eps4) * cochain.x))
         return self.combine_nn(torch.cat(parts, dim=-1))
 
@@ -1487,7 +1500,7 @@ class CINppConv(SparseCINConv):
         eval-mode BatchNorm and the ReLU folded into the epilogue (SparseCINConv._dense_eval's form); torch.cat + combine_nn
         as torch modules."""
         from . import _ffi
-        if torch.is_grad_enabled():
+        if torch.is_grad_enabled() or any(o.dtype != torch.float32 for o in outs):
             return None
         got = self._update_chains(plans, outs, start)
         if got is None:
@@ -1528,7 +1541,8 @@ class CINppConv(SparseCINConv):
         without combine stages, at most _ffi.MAX_DESCS chains per autograd node -- then torch.cat + combine_nn as torch
         modules (mp/layers.py:255-260).  None when it does not apply (LayerNorm, custom networks, fewer than two cells)."""
         from . import _ffi, dense_train as DT
-        if not torch.is_grad_enabled() or not FUSED_DENSE_TRAINING or any(o.size(0) < 2 for o in outs):
+        if (not torch.is_grad_enabled() or not FUSED_DENSE_TRAINING or any(o.size(0) < 2 for o in outs)
+                or any(o.dtype != torch.float32 for o in outs)):
             return None
         got = self._update_chains(plans, outs, start)
         if got is None:
@@ -1624,7 +1638,7 @@ class OrientedConv(CochainMessagePassing):
     def _stream(self, adj: Adjacency, x: Tensor, attr: Tensor, aggr) -> ops.Stream:
         if not self.orient:
             return ops.Stream(adj=adj, n_dst=adj.n_dst, width=int(x.size(1)), A=x, reduce=aggr or 'add')
-        return ops.Stream(adj=adj, n_dst=adj.n_dst, width=int(x.size(1)), A=x, B=dense(attr).to(torch.float32),
+        return ops.Stream(adj=adj, n_dst=adj.n_dst, width=int(x.size(1)), A=x, B=dense(attr).to(x.dtype),
                           msg_op=ops.MSG_A_TIMES_B, ib_mode='perm', reduce=aggr or 'add')
 
     def propagate_both(self, cochain) -> Optional[List[Tensor]]:
@@ -1675,7 +1689,7 @@ class OrientedConv(CochainMessagePassing):
     def _fused(self, adj: Adjacency, x, attr, aggr) -> Tensor:
         if not self.orient:
             return ops.aggregate(adj, adj.n_dst, x, reduce=aggr or 'add')
-        attr = dense(attr).to(torch.float32)
+        attr = dense(attr).to(x.dtype)
         return ops.aggregate(adj, adj.n_dst, x, msg_op=ops.MSG_A_TIMES_B, B=attr, ib_mode='perm',
                              reduce=aggr or 'add')
 

@@ -257,7 +257,7 @@ class _SparseCINStack(torch.nn.Module):
         if self.final_readout not in ('mean', 'sum'):
             raise NotImplementedError
         lins = [self.lin1s[d] for d in self.readout_dims]
-        dense_head = (self.nonlinearity == 'relu' and xs[0].is_cuda
+        dense_head = (self.nonlinearity == 'relu' and xs[0].is_cuda and xs[0].dtype == torch.float32     # (fp32 MFMA GEMMs)
                       and max(l.in_features for l in lins + [self.lin2]) <= ops.GEMM_MAX_K)
         if self.apply_dropout_before == 'lin1':
             xs = [ops.dropout(x, self.dropout_rate, self.training) for x in xs]

@@ -23,12 +23,49 @@ MSG_A, MSG_A_PLUS_B, MSG_A_TIMES_B, MSG_RELU_A_PLUS_B, MSG_A_MASK_RELU, MSG_RELU
 
 
 def _f32c(t: Optional[Tensor], name: str) -> Optional[Tensor]:
+    """An operand of a kernel that exists in fp32 only (the fused layer / MLP / head / stage launches, the GEMMs, the
+    embedding kernels).  The aggregate and the gather also run in float64: `_fc`."""
     if t is None:
         return None
     _ffi.require_gpu(t, name)
     if t.dtype != torch.float32:
-        raise TypeError(f'{name} must be float32 (got {t.dtype}); the engine computes in fp32')
+        raise TypeError(f'{name} must be float32 (got {t.dtype}): this kernel computes in fp32 only '
+                        '(float64 runs through aggregate_many / gather_rows and the torch modules)')
     return t.contiguous()
+
+
+def _fc(t: Optional[Tensor], name: str) -> Optional[Tensor]:
+    """An operand of the aggregate / gather kernels: on the GPU, float32 or float64, contiguous."""
+    if t is None:
+        return None
+    _ffi.require_gpu(t, name)
+    if t.dtype not in _ffi.FLOAT_DTYPES:
+        raise TypeError(f'{name} must be float32 or float64 (got {t.dtype}); the engine computes in fp32 or fp64')
+    return t.contiguous()
+
+
+def _common_dtype(named) -> torch.dtype:
+    """The one dtype of the tensor operands of a stream (`named`: (name, tensor or None) pairs); float32 without any."""
+    first = None
+    for name, t in named:
+        dt = getattr(t, 'dtype', None)
+        if dt is None:
+            continue
+        if first is None:
+            first = (name, dt)
+        elif dt != first[1]:
+            raise TypeError(f'the operands of one stream share one dtype: {first[0]} is {first[1]}, {name} is {dt}')
+    return torch.float32 if first is None else first[1]
+
+
+def require_float32_model(model, what: str) -> None:
+    """The captured / prepared machinery (StaticForward, TrainStep and what they are built of: FlatAdam, the blocked and
+    fused launches, the C-ABI GEMMs) is float32 by construction.  A float64 model runs eagerly: model(batch), autograd and
+    torch.optim, over cwn_aggregate_f64 / cwn_gather_rows_f64 and the torch modules."""
+    for name, t in list(model.named_parameters()) + list(model.named_buffers()):
+        if t.is_floating_point() and t.dtype != torch.float32:
+            raise TypeError(f'{what} runs float32 models only: {name} is {t.dtype}.  A float64 model runs eagerly -- '
+                            'model(batch), autograd and a torch.optim optimizer')
 
 
 AGG_SMALL_OPERANDS = 1      # = CWN_AGG_SMALL_OPERANDS (include/cwn_hip.h)
@@ -38,7 +75,8 @@ ALLOW_SMALL_OPERANDS = os.environ.get('CWN_AGG_WIDE') != '1'
 
 @dataclass
 class AggSpec:
-    """One descriptor of cwn_aggregate_f32.  `ia`/`ib` are int32 tensors in CSR order."""
+    """One descriptor of cwn_aggregate_f32 / cwn_aggregate_f64.  `ia`/`ib` are int32 tensors in CSR order.  `dtype`
+    (float32 / float64) is that of every tensor operand; left None it is taken from A, else (adj=None) from self_x."""
     adj: Optional[Adjacency]
     n_dst: int
     F: int
@@ -54,13 +92,21 @@ class AggSpec:
     out: Optional[Tensor] = None
     self_x2: Optional[Tensor] = None     # second self term: out += (1 + eps2) * self_x2
     eps2: Optional[Tensor] = None
+    dtype: Optional[torch.dtype] = None
+
+    def resolve_dtype(self) -> torch.dtype:
+        if self.dtype is None:
+            self.dtype = _common_dtype([('A', self.A), ('B', self.B), ('self_x', self.self_x), ('self_x2', self.self_x2),
+                                        ('self_pre', self.self_pre), ('out', self.out)])
+        return self.dtype
 
     def desc(self) -> _ffi.AggDesc:
         # an index with E = 0 is legal (mp/test_cell_mp.py:137-176) and behaves like an absent one
         absent = self.adj is None or self.adj.n_entries == 0
         bw = self.F if (self.B is None or self.B.size(1) == self.F) else int(self.B.size(1))
         # gathered operands within 4 GiB of their base pointers: 32-bit row offsets in the kernel
-        small = ALLOW_SMALL_OPERANDS and all(t is None or t.numel() * 4 < (1 << 32) for t in (self.A, self.B))
+        esize = 8 if self.resolve_dtype() == torch.float64 else 4
+        small = ALLOW_SMALL_OPERANDS and all(t is None or t.numel() * esize < (1 << 32) for t in (self.A, self.B))
         return _ffi.AggDesc(
             flags=AGG_SMALL_OPERANDS if small else 0,
             rowptr=None if absent else self.adj.rowptr.data_ptr(),
@@ -76,10 +122,11 @@ class AggSpec:
 
 
 def run_aggregate(specs: Sequence[AggSpec], device) -> List[Tensor]:
-    """Raw launch (no autograd): allocates missing outputs, ONE kernel per <= 8 descriptors."""
+    """Raw launch (no autograd): allocates missing outputs, ONE kernel per <= 8 descriptors of one dtype (the float32 and
+    the float64 descriptors of a call are launched separately)."""
     for s in specs:
         if s.out is None:
-            s.out = torch.empty(s.n_dst, s.F, dtype=torch.float32, device=device)
+            s.out = torch.empty(s.n_dst, s.F, dtype=s.resolve_dtype(), device=device)
     live = [s for s in specs if s.n_dst > 0]
     if live:
         late = [s.adj for s in live if s.adj is not None and not s.adj.built]     # handed out under csr.deferred_builds
@@ -87,7 +134,11 @@ def run_aggregate(specs: Sequence[AggSpec], device) -> List[Tensor]:
             from .csr import build_many
             build_many(late)
         wait_ready([s.adj for s in live])      # plans built on the side stream (csr.build_many)
-        _ffi.aggregate([s.desc() for s in live], device)
+        by_dtype = {}
+        for s in live:
+            by_dtype.setdefault(s.resolve_dtype(), []).append(s.desc())
+        for dt, descs in by_dtype.items():
+            _ffi.aggregate(descs, device, dt)
     return [s.out for s in specs]
 
 
@@ -114,10 +165,17 @@ class Stream:
     ib_mode: str = 'aux'
     self_x: Optional[Tensor] = None
     eps: Optional[Tensor] = None
+    dtype: Optional[torch.dtype] = None      # set by validate(): the one dtype of A, B and self_x
 
     def validate(self):
-        self.A, self.B = _f32c(self.A, 'A'), _f32c(self.B, 'B')
-        self.self_x, self.eps = _f32c(self.self_x, 'self_x'), _f32c(self.eps, 'eps')
+        self.A, self.B = _fc(self.A, 'A'), _fc(self.B, 'B')
+        self.self_x, self.eps = _fc(self.self_x, 'self_x'), _fc(self.eps, 'eps')
+        # one dtype per stream; eps, a device scalar (usually a parameter), follows it
+        named = [('A', self.A), ('B', self.B), ('self_x', self.self_x)]
+        if self.dtype is None or any(t is not None for _, t in named):      # (no tensor at all: zero rows of the given dtype)
+            self.dtype = _common_dtype(named)
+        if self.eps is not None and self.eps.dtype != self.dtype:
+            self.eps = self.eps.to(self.dtype)
         adj = self.adj
         if adj is None:
             self.A = self.B = None
@@ -186,6 +244,11 @@ def _aggregate_backward(streams, tensors, needs, gs, max_outs, device) -> List[O
             if op != MSG_A:
                 raise NotImplementedError("gradient of reduce='max' with a two-operand fused message: "
                                           'route the message through the generic (hook) path')
+            if self_x is not None:
+                # the saved output carries the self term: the bare row maxima again (found by gradcheck: the arg-max test
+                # below compared A with max + (1 + eps) x and selected nothing)
+                out_k, = run_aggregate([AggSpec(adj=adj, n_dst=st.n_dst, F=st.width, A=A, reduce=_ffi.REDUCE['max'],
+                                                ia=adj.col if st.ia_mode == 'col' else adj.perm)], device)
             if need_A:
                 grads[4 * k] = _AggregateMany._max_backward(st, A, out_k, g)
             continue
@@ -193,8 +256,17 @@ def _aggregate_backward(streams, tensors, needs, gs, max_outs, device) -> List[O
             g = g / adj.counts
         F = g.size(1)
         if need_A:
-            if st.ia_mode == 'perm':   # A holds one row per ENTRY: dA[e] = g[dst[e]]
-                grads[4 * k] = _ffi.gather_rows(g, adj.key)
+            if st.ia_mode == 'perm':   # A holds one row per ENTRY: dA[e] = g[dst[e]] (x the message's own derivative)
+                gA = _ffi.gather_rows(g, adj.key)
+                if op not in (MSG_A, MSG_A_PLUS_B):
+                    b_e = B if st.ib_mode == 'perm' else _ffi.gather_rows(B, adj.aux_index)
+                    if op == MSG_A_TIMES_B:
+                        gA = gA * b_e
+                    elif op == MSG_RELU_A_PLUS_B:
+                        gA = gA * ((A + b_e) > 0)
+                    else:
+                        gA = gA * (2 * torch.relu(A + b_e))
+                grads[4 * k] = gA
             else:
                 t = adj.t_src          # rows of A collect from the destinations they fed
                 s = AggSpec(adj=t, n_dst=t.n_dst, F=F, A=g, ia=t.col)
@@ -217,16 +289,19 @@ def _aggregate_backward(streams, tensors, needs, gs, max_outs, device) -> List[O
                     'generic (hook) path if it is trainable')
             if st.ib_mode == 'perm':
                 gB = _ffi.gather_rows(g, adj.key)          # dB[e] = g[dst[e]] ...
+                a_e = (lambda: A if st.ia_mode == 'perm' else _ffi.gather_rows(A, adj.val))
                 if op == MSG_RELU_A_PLUS_B:                # ... where the entry's pre-activation is positive
-                    gB = gB * ((_ffi.gather_rows(A, adj.val) + B) > 0)
+                    gB = gB * ((a_e() + B) > 0)
                 elif op == MSG_RELU_A_PLUS_B_SQ:
-                    gB = gB * (2 * torch.relu(_ffi.gather_rows(A, adj.val) + B))
+                    gB = gB * (2 * torch.relu(a_e() + B))
                 grads[4 * k + 1] = gB
             else:
                 t = adj.t_aux          # keyed on the aux cell: col = destination, aux = source
                 s = AggSpec(adj=t, n_dst=t.n_dst, F=F, A=g, ia=t.col)
                 if op in (MSG_RELU_A_PLUS_B, MSG_RELU_A_PLUS_B_SQ):
-                    s.msg_op, s.B, s.ib, s.self_pre = (MSG_A_MASK_RELU if op == MSG_RELU_A_PLUS_B else MSG_A_TIMES_2RELU), A, t.aux, B
+                    # (A per source cell, or per ENTRY: the transposed plan's perm is the entry id of each of its positions)
+                    s.msg_op, s.B, s.self_pre = (MSG_A_MASK_RELU if op == MSG_RELU_A_PLUS_B else MSG_A_TIMES_2RELU), A, B
+                    s.ib = t.aux if st.ia_mode == 'col' else t.perm
                 gathered.setdefault(ident(B), len(specs))
                 specs.append(s)
                 slots.append(4 * k + 1)
@@ -262,7 +337,7 @@ class _AggregateMany(torch.autograd.Function):
         for k, st in enumerate(streams):
             A, B, self_x, eps = tensors[4 * k: 4 * k + 4]
             s = AggSpec(adj=st.adj, n_dst=st.n_dst, F=st.width, msg_op=st.msg_op,
-                        reduce=_ffi.REDUCE[st.reduce], self_x=self_x, eps=eps)
+                        reduce=_ffi.REDUCE[st.reduce], self_x=self_x, eps=eps, dtype=getattr(st, 'dtype', None))
             if st.adj is not None:
                 s.A = A
                 s.ia = st.adj.col if st.ia_mode == 'col' else st.adj.perm
@@ -359,9 +434,9 @@ def aggregate(adj: Optional[Adjacency], n_dst: int, A: Optional[Tensor], *, msg_
                                   self_x=self_x, eps=eps)])[0]
 
 
-def zeros_rows(n: int, width: int, device) -> Tensor:
+def zeros_rows(n: int, width: int, device, dtype: torch.dtype = torch.float32) -> Tensor:
     """K9: the zero fill for an absent adjacency when nothing else is launched."""
-    return torch.zeros(n, width, dtype=torch.float32, device=device)
+    return torch.zeros(n, width, dtype=dtype, device=device)
 
 
 class _GatherRows(torch.autograd.Function):
@@ -384,7 +459,7 @@ class _GatherRows(torch.autograd.Function):
 def gather_rows(src: Tensor, idx: Tensor, adj_for_idx=None) -> Tensor:
     """Differentiable row gather.  `adj_for_idx` is a zero-argument callable returning an Adjacency
     keyed on `idx` (only called in backward); when omitted one is built on demand."""
-    src = _f32c(src, 'src')
+    src = _fc(src, 'src')
     _ffi.require_gpu(idx, 'idx')
     if idx.dtype != torch.long:
         raise TypeError('index must be int64')
@@ -419,8 +494,8 @@ def embedding_sum(weights: Sequence[Tensor], idx: Tensor) -> Tensor:
         raise ValueError(f'{Cn} index columns for {len(weights)} embedding tables')
     H = int(weights[0].size(1))
     V = sum(int(w.size(0)) for w in weights)
-    if H % 4 != 0 or V * H * 4 > 60 * 1024:
-        # a table too wide / too large for the dedicated kernels: generic aggregation over a plan
+    if H % 4 != 0 or V * H * 4 > 60 * 1024 or weights[0].dtype != torch.float32:
+        # a table too wide / too large for the dedicated kernels (or not float32): generic aggregation over a plan
         W = weights[0] if Cn == 1 else torch.cat(list(weights), 0)
         offs = torch.tensor([sum(int(w.size(0)) for w in weights[:c]) for c in range(Cn)],
                             dtype=torch.long, device=idx.device)
@@ -1323,7 +1398,8 @@ def _rowmajor(t: Tensor, name: str) -> Tensor:
     """2-D fp32 GPU tensor whose rows are contiguous (column slices of a Linear weight qualify)."""
     _ffi.require_gpu(t, name)
     if t.dtype != torch.float32 or t.dim() != 2:
-        raise TypeError(f'{name} must be a 2-D float32 tensor')
+        raise TypeError(f'{name} must be a 2-D float32 tensor (got {t.dtype}, {t.dim()}-D): the GEMM kernels are fp32 MFMA '
+                        'only; float64 products run on torch.nn.Linear')
     if t.size(1) > 1 and t.stride(1) != 1:
         t = t.contiguous()
     if t.size(0) > 1 and t.stride(0) < t.size(1):

@@ -190,6 +190,7 @@ class StaticForward:
     a parameter (or, through ops.STATE_EPOCH, a raw-pointer writer such as a TrainStep) has changed them."""
 
     def __init__(self, model: torch.nn.Module, static: StaticBatch):
+        ops.require_float32_model(model, 'StaticForward')
         refuse_unsupported_layers(model, 'StaticForward', static)
         self.model, self.sb = model, static
         # one captured graph per number of slots it runs (round 6): S for the body of an epoch, a power of two below it for its

@@ -112,6 +112,38 @@ def induced_cycles(n: int, bonds: Sequence[Tuple[int, int]], max_k: int) -> List
     return [found[k] for k in sorted(found)]
 
 
+def rook_4x4() -> Tuple[int, List[Tuple[int, int]]]:
+    """The 4 x 4 rook's graph, one of the two strongly regular graphs SR(16, 6, 2, 2): vertices (i, j), adjacent when they
+    share a row or a column.  (num_vertices, sorted list of edges (u < v))."""
+    cells = [(i, j) for i in range(4) for j in range(4)]
+    return 16, sorted((a, b) for a in range(16) for b in range(a + 1, 16)
+                      if cells[a][0] == cells[b][0] or cells[a][1] == cells[b][1])
+
+
+def shrikhande() -> Tuple[int, List[Tuple[int, int]]]:
+    """The Shrikhande graph, the other SR(16, 6, 2, 2): vertices in Z4 x Z4, adjacent when their difference is +-(1, 0),
+    +-(0, 1) or +-(1, 1).  1-WL (and 3-WL) cannot tell it from the rook's graph; the ring lift can."""
+    cells = [(i, j) for i in range(4) for j in range(4)]
+    steps = {(1, 0), (3, 0), (0, 1), (0, 3), (1, 1), (3, 3)}
+    return 16, sorted((a, b) for a in range(16) for b in range(a + 1, 16)
+                      if ((cells[a][0] - cells[b][0]) % 4, (cells[a][1] - cells[b][1]) % 4) in steps)
+
+
+def relabel(n: int, bonds: Sequence[Tuple[int, int]], perm: Sequence[int]) -> Tuple[int, List[Tuple[int, int]]]:
+    """The same graph with vertex v renamed perm[v]: an isomorphic copy."""
+    return n, sorted((min(int(perm[u]), int(perm[v])), max(int(perm[u]), int(perm[v]))) for u, v in bonds)
+
+
+def sr_lift(n: int, bonds: Sequence[Tuple[int, int]], max_k: int = 6, dtype=torch.float64) -> Complex:
+    """The ring lift of a featureless graph as the strongly-regular-graph experiments feed it: constant vertex features,
+    every higher cell the sum of its vertices' (edges 2, a k-ring k), in `dtype`."""
+    cx = ring_lift(n, bonds, torch.ones(n, 1, dtype=dtype), torch.full((len(bonds), 1), 2.0, dtype=dtype), max_k=max_k)
+    if cx.dimension >= 2:
+        sizes = torch.bincount(cx.cochains[2].boundary_index[1]).to(dtype).unsqueeze(1)
+        cx.cochains[2].x = sizes
+    return cx
+
+
 # ------------------------------------------------------------------------------------------------
 # ring lift
 # ------------------------------------------------------------------------------------------------

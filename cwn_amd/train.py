@@ -292,7 +292,13 @@ class TrainStep:
         dist.StagedBackward.stages) falls back to 1."""
         if task_type not in _LOSSES:
             raise NotImplementedError('Training on task type {} not yet supported.'.format(task_type))
+        ops.require_float32_model(model, type(self).__name__)
         self.model, self.batches = model.train(), list(batches)
+        for b in self.batches:
+            for c in self._cochains(b):
+                if c.x is not None and c.x.dtype == torch.float64:
+                    raise TypeError(f'{type(self).__name__} runs float32 features only (got torch.float64); a float64 batch '
+                                    'trains eagerly with autograd and a torch.optim optimizer')
         self.loss_fn = _LOSSES[task_type]
         self.task_type = task_type
         live = dist.is_available() and dist.is_initialized()

@@ -1,0 +1,55 @@
+"""The strongly-regular-graph isomorphism experiment of the reference (exp/scripts/cwn-sr.sh, exp/run_sr_exp.py,
+exp/test_sr.py:81-128) on the two graphs of the family SR(16, 6, 2, 2), which need no data file: the 4 x 4 rook's graph and
+the Shrikhande graph.  An UNTRAINED SparseCIN (hidden 16, ELU, no normalisation, sum readouts, coboundary features) embeds
+the ring lift (rings up to 6) of each graph and of a vertex-relabelled copy, in float64 -- the experiment sets
+torch.set_default_dtype(torch.float64) because sum aggregation reaches 1e8 without a norm layer, and two isomorphic complexes
+must land within 0.01 of each other (torch.pdist) while non-isomorphic ones are told apart.
+
+Every gather and segmented reduce of the float64 model is a launch of csrc/cwn_aggregate_f64.hip; the dense parts are
+torch.nn.Linear (rocBLAS dgemm).
+
+    python examples/sr_isomorphism.py [seed]        (needs an MI355X)
+"""
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from cwn_amd.complex import ComplexBatch                                   # noqa: E402
+from cwn_amd.models import SparseCIN                                       # noqa: E402
+from cwn_amd.synthetic import relabel, rook_4x4, shrikhande, sr_lift       # noqa: E402
+
+EPS = 0.01                   # the reference's criterion (exp/test_sr.py:82)
+
+
+def main():
+    seed = int(sys.argv[1]) if len(sys.argv) > 1 else 0
+    dev = torch.device('cuda', 0)
+    torch.set_default_dtype(torch.float64)
+    rng = np.random.default_rng(43)
+    graphs = {'rook 4x4': rook_4x4(), 'Shrikhande': shrikhande()}
+    batch, names = [], []
+    for name, g in graphs.items():
+        batch += [sr_lift(*g, max_k=6), sr_lift(*relabel(*g, rng.permutation(16)), max_k=6)]
+        names += [name, name + ' (relabelled)']
+    for num_layers in (3, 5):
+        torch.manual_seed(seed)
+        model = SparseCIN(num_input_features=1, num_classes=16, num_layers=num_layers, hidden=16, dropout_rate=0.0, max_dim=2,
+                          use_coboundaries=True, nonlinearity='elu', graph_norm='id', readout='sum', final_readout='sum',
+                          readout_dims=(0, 1, 2)).to(dev).eval()
+        with torch.no_grad():
+            emb = model(ComplexBatch.from_complex_list(batch, max_dim=2).to(dev))
+        apex = float(emb.abs().max())
+        print(f'{num_layers} layers: embeddings {tuple(emb.shape)} {emb.dtype}, max |embedding| = {apex:.4g} '
+              f'({"below" if apex < 5e8 else "NOT below"} 5e8)')
+        for i in (0, 2):
+            d = float(torch.pdist(emb[i:i + 2], p=2))
+            print(f'  {names[i]:<12} vs its relabelled copy: {d:.3e}  ({"isomorphic: within" if d <= EPS else "ABOVE"} {EPS})')
+        d = float(torch.pdist(emb[[0, 2]], p=2))
+        print(f'  rook 4x4 vs Shrikhande:              {d:.3e}  ({"told apart" if d > EPS else "NOT told apart"})')
+
+
+if __name__ == '__main__':
+    main()

@@ -209,6 +209,47 @@ typedef struct cwn_agg_desc {
 int cwn_aggregate_f32(const cwn_agg_desc* descs_host, int n, cwn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The same two kernels in float64 (the strongly-regular-graph isomorphism experiments run under
+ * torch.set_default_dtype(torch.float64), exp/run_exp.py:40-43: untrained sum aggregation reaches
+ * 5e8 and isomorphic complexes must agree to 0.01).  cwn_agg_desc_f64 is cwn_agg_desc field by
+ * field with double in place of float -- the same layout, every pointer being 8 bytes -- and
+ * cwn_aggregate_f64 / cwn_gather_rows_f64 mean exactly what their f32 forms mean: all seven
+ * messages, add / mean / max, absent adjacency, both self terms, m_dev, the long-row pass, the same
+ * error codes.  What differs: data pointers (eps and eps2 included) must be 8-byte aligned
+ * (CWN_ERR_ALIGN), a lane's 16-byte slice is two doubles (pointers 16-byte aligned and F even, else
+ * one), and CWN_AGG_SMALL_OPERANDS vouches for rows_a * F * 8 and rows_b * b_width * 8 below 2^32.
+ * Sums run sequentially in CSR order in double (bit-identical to a sequential float64 index_add_),
+ * except rows above CWN_LONG_ROW and, for F <= 14, rows above 16 entries (fixed-order partials).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct cwn_agg_desc_f64 {
+    const int32_t* rowptr;
+    const int32_t* ia;
+    const int32_t* ib;
+    const double* A;
+    const double* B;
+    const double* self_x;
+    const double* eps;
+    const double* self_pre;
+    double* out;
+    const int32_t* long_rows;
+    const int32_t* n_long;
+    int64_t n_dst;
+    int32_t F;
+    int32_t b_width;
+    int32_t msg_op;
+    int32_t reduce;
+    int32_t long_cap;
+    int32_t flags;
+    const double* self_x2;
+    const double* eps2;
+    const int64_t* m_dev;
+} cwn_agg_desc_f64;
+
+int cwn_aggregate_f64(const cwn_agg_desc_f64* descs_host, int n, cwn_stream_t stream);
+int cwn_gather_rows_f64(const double* src, int64_t n_src, int64_t F, const int64_t* idx,
+                        int64_t n_idx, double* out, cwn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * A whole SparseCIN propagate step of one layer in ONE launch (inference / no-grad):
  * everything SparseCINConv.forward does before the update networks (mp/layers.py:333-342 ->
  * :184-192 per dimension -> CochainMessagePassing.propagate, mp/cell_mp.py:357-392), for all
