@@ -22,6 +22,7 @@ ABI_VERSION = 24
 EXPORTS = ('cwn_abi_version', 'cwn_error_string', 'cwn_target_arch', 'cwn_csr_workspace_bytes',
            'cwn_csr_build', 'cwn_csr_long_rows', 'cwn_gather_rows_f32', 'cwn_aggregate_f32', 'cwn_gather_rows_f64', 'cwn_aggregate_f64', 'cwn_gemm_f32', 'cwn_gemm_would_split', 'cwn_gemm_packed_weight_bytes', 'cwn_gemm_pack_weights_f32', 'cwn_update_mlp_f32', 'cwn_update_mlp3_f32', 'cwn_update_mlp_max_rows', 'cwn_update_mlp_packed_weight_bytes', 'cwn_update_mlp_pack_weights_f32', 'cwn_update_mlp_pack_weights_many_f32', 'cwn_update_mlp_pack_weights_t_many_f32', 'cwn_update_mlp_pack_weights_both_many_f32', 'cwn_layer_pack_weights_both_many_f32', 'cwn_dense_stage_f32', 'cwn_dense_stage_ex_f32', 'cwn_dense_stage_bwd_f32', 'cwn_layer_fused_f32', 'cwn_layer_fused_lds_bytes', 'cwn_layer_variant_lds_bytes', 'cwn_layer_round_rows', 'cwn_layer_variant_round_rows', 'cwn_layer_items_check', 'cwn_layer_items_build', 'cwn_layer_pack_weights_f32', 'cwn_layer_pack_weights_many_f32', 'cwn_layer_pack_weights_t_many_f32', 'cwn_layer_bwd_f32', 'cwn_layer_bwd_lds_bytes', 'cwn_layer_bwd_items_build', 'cwn_layer_bwd_own_f32', 'cwn_layer_packed_weight_bytes', 'cwn_collate', 'cwn_collate_slots', 'cwn_collate_tables', 'cwn_collate_tables_len', 'cwn_collate_guard', 'cwn_layer_items_build_dev', 'cwn_layer_bwd_items_build_dev',
            'cwn_bn_finalize_f32', 'cwn_step_begin', 'cwn_axpy_eps_f32', 'cwn_dropout_f32', 'cwn_embed_front_bwd_f32', 'cwn_norm_act_f32', 'cwn_norm_bwd_reduce_f32', 'cwn_norm_bwd_apply_f32', 'cwn_norm_bwd_f32',
+           'cwn_layernorm_act_f32', 'cwn_layernorm_bwd_workspace_bytes', 'cwn_layernorm_bwd_f32',
            'cwn_gemm_tn_f32', 'cwn_gemm_tn_workspace_bytes', 'cwn_adam_f32', 'cwn_adam_dev_f32', 'cwn_loss_f32', 'cwn_loss_cols_f32', 'cwn_embedding_fwd_f32', 'cwn_embedding_bwd_f32', 'cwn_embed_front_f32', 'cwn_head_f32', 'cwn_head_bwd_f32', 'cwn_head_pool_floats', 'cwn_lift_create', 'cwn_lift_size', 'cwn_lift_copy', 'cwn_lift_destroy',
            'cwn_lift_many', 'cwn_lift_many_count', 'cwn_lift_many_lengths', 'cwn_lift_many_copy', 'cwn_lift_many_destroy')
 
@@ -270,6 +271,15 @@ class NormDesc(C.Structure):
                 ('m_dev', C.c_void_p), ('bn', BnLive), ('drop', Dropout), ('dy_out', C.c_void_p), ('lddy_out', C.c_int64)]
 
 
+class LnDesc(C.Structure):
+    """cwn_ln_desc: one LayerNorm (+ ReLU) over the rows of a matrix, forward and backward operands."""
+    _fields_ = [('z', C.c_void_p), ('gamma', C.c_void_p), ('beta', C.c_void_p), ('out', C.c_void_p),
+                ('mean', C.c_void_p), ('rstd', C.c_void_p), ('dy', C.c_void_p), ('dz', C.c_void_p),
+                ('dgamma', C.c_void_p), ('dbeta', C.c_void_p), ('M', C.c_int64), ('ldz', C.c_int64),
+                ('ldout', C.c_int64), ('lddy', C.c_int64), ('lddz', C.c_int64), ('N', C.c_int32), ('relu', C.c_int32),
+                ('eps', C.c_float), ('accumulate', C.c_int32), ('m_dev', C.c_void_p)]
+
+
 class GemmTnDesc(C.Structure):
     _fields_ = [('dZ', C.c_void_p), ('X', C.c_void_p), ('X2', C.c_void_p), ('in_scale', C.c_void_p),
                 ('in_shift', C.c_void_p), ('in_scale2', C.c_void_p), ('in_shift2', C.c_void_p),
@@ -412,6 +422,12 @@ def lib():
         getattr(L, name).argtypes = [C.POINTER(NormDesc), C.c_int, C.c_void_p]
     L.cwn_norm_bwd_f32.restype = C.c_int
     L.cwn_norm_bwd_f32.argtypes = [C.POINTER(NormDesc), C.c_int, C.c_int, C.c_void_p]
+    L.cwn_layernorm_act_f32.restype = C.c_int
+    L.cwn_layernorm_act_f32.argtypes = [C.POINTER(LnDesc), C.c_int, C.c_void_p]
+    L.cwn_layernorm_bwd_workspace_bytes.restype = C.c_size_t
+    L.cwn_layernorm_bwd_workspace_bytes.argtypes = [C.POINTER(LnDesc), C.c_int]
+    L.cwn_layernorm_bwd_f32.restype = C.c_int
+    L.cwn_layernorm_bwd_f32.argtypes = [C.POINTER(LnDesc), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
     L.cwn_gemm_tn_f32.restype = C.c_int
     L.cwn_gemm_tn_f32.argtypes = [C.POINTER(GemmTnDesc), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
     L.cwn_gemm_tn_workspace_bytes.restype = C.c_size_t
@@ -617,6 +633,29 @@ def norm_bwd(descs: Sequence[NormDesc], device, accumulate: bool) -> None:
         chunk = descs[i:i + MAX_NORM_DESCS]
         arr = (NormDesc * len(chunk))(*chunk)
         check(L.cwn_norm_bwd_f32(arr, len(chunk), int(bool(accumulate)), s), 'cwn_norm_bwd_f32')
+
+
+LN_MAX_N = 1024                    # widest row cwn_layernorm_* holds in a wave's registers
+
+
+def layer_norm_act(descs: Sequence['LnDesc'], device) -> None:
+    """out = act(LayerNorm(z)) for every descriptor: one launch per MAX_NORM_DESCS."""
+    _chunked('cwn_layernorm_act_f32', LnDesc, descs, device, MAX_NORM_DESCS)
+
+
+def layer_norm_bwd(descs: Sequence['LnDesc'], device) -> None:
+    """dz, dgamma, dbeta of every descriptor: per MAX_NORM_DESCS one launch for the rows and one that sums the workgroups'
+    column partials (a torch buffer the stream's ordering keeps alive until they have run)."""
+    L = lib()
+    s = stream_ptr(device)
+    _set_dyn(descs)
+    for i in range(0, len(descs), MAX_NORM_DESCS):
+        chunk = descs[i:i + MAX_NORM_DESCS]
+        arr = (LnDesc * len(chunk))(*chunk)
+        nbytes = int(L.cwn_layernorm_bwd_workspace_bytes(arr, len(chunk)))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes else None
+        check(L.cwn_layernorm_bwd_f32(arr, len(chunk), None if ws is None else ws.data_ptr(), nbytes, s),
+              'cwn_layernorm_bwd_f32')
 
 
 # False: the row bands of a weight gradient are added with fp32 atomics (fastest: 1.48 ms ZINC training

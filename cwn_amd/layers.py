@@ -1213,6 +1213,27 @@ class SparseCINConv(torch.nn.Module):
         self._out_dropped = p > 0.0              # (the combine stage's activation launch applies it: dense_train._Plan.out_drop)
         return DT.dense_train(DT._Plan(ups, bds, cbs, out_drop=p), outs)
 
+    def _ln_chains(self, plans, outs, start: int):
+        """([dim][branch] -> stages, [dim] -> combine stages) of the active dimensions, or None."""
+        active = list(range(start, len(plans)))
+        if not active or any(plans[d] is None for d in active) or len(outs) != 2 * len(active):
+            return None
+        levels = [self.mp_levels[d] for d in active]
+        return ([[_mlp_stages(lvl.update_up_nn), _mlp_stages(lvl.update_boundaries_nn)] for lvl in levels],
+                [_mlp_stages(lvl.combine_nn) for lvl in levels])
+
+    def _dense_ln(self, plans, outs, start: int = 0) -> Optional[List[Tensor]]:
+        """The same networks built with graph_norm='ln', in inference and in training: one grouped GEMM and one LayerNorm +
+        ReLU launch per stage over all dimensions and branches (cwn_amd/dense_ln.py).  None when it does not apply (another
+        normalisation, custom networks, float64 or CPU features) and the caller runs the torch modules instead."""
+        from . import dense_ln as DL
+        if not DL.FUSED_LN or not outs or any(o.dtype != torch.float32 or not o.is_cuda for o in outs):
+            return None
+        got = self._ln_chains(plans, outs, start)
+        if got is None or not DL.supported(*got):
+            return None
+        return DL.run(got[0], got[1], outs)
+
     # the caller's dropout of this layer's OUTPUT (OGBEmbedSparseCIN: after every conv, mp/molec_models.py:298-300), handed in
     # so that the fused training path applies it inside its last launch: forward(..., out_dropout=p).  _dense_train sets
     # _out_dropped when it has; every other path gets ops.dropout (one launch per dimension, no mask tensor).
@@ -1234,6 +1255,8 @@ class SparseCINConv(torch.nn.Module):
         dense = self._dense_eval(plans, outs, start_to_process)
         if dense is None:
             dense = self._dense_train(plans, outs, start_to_process)
+        if dense is None:
+            dense = self._dense_ln(plans, outs, start_to_process)
         if dense is not None:
             it = iter(dense)
             return self._finish_dropout([cochain_params[dim].x if dim < start_to_process else next(it) for dim in range(n)],
@@ -1495,6 +1518,12 @@ class CINppConv(SparseCINConv):
             return None
         return active, nb, chains
 
+    def _ln_chains(self, plans, outs, start: int):
+        got = self._update_chains(plans, outs, start)
+        if got is None:
+            return None
+        return got[2], [_mlp_stages(self.mp_levels[d].combine_nn) for d in got[0]]
+
     def _dense_eval(self, plans, outs, start: int = 0) -> Optional[List[Tensor]]:
         """Inference: the update networks of every stream and dimension as grouped MFMA launches, one per stage, with
         eval-mode BatchNorm and the ReLU folded into the epilogue (SparseCINConv._dense_eval's form); torch.cat + combine_nn
@@ -1600,6 +1629,8 @@ class CINppConv(SparseCINConv):
         dense = self._dense_eval(plans, outs, start_to_process)
         if dense is None:
             dense = self._dense_train(plans, outs, start_to_process)
+        if dense is None:
+            dense = self._dense_ln(plans, outs, start_to_process)
         if dense is not None:
             it = iter(dense)
             return self._finish_dropout([c.x if dim < start_to_process else next(it) for dim, c in enumerate(cochain_params)],

@@ -1705,6 +1705,143 @@ def gemm_many(gemms: Sequence[Gemm]) -> List[Tensor]:
 
 
 # ------------------------------------------------------------------------------------------------
+# LayerNorm (+ ReLU) over the rows of several matrices: graph_norm='ln' (csrc/cwn_layernorm.hip)
+# ------------------------------------------------------------------------------------------------
+def _ln_ld(t: Tensor) -> int:
+    return t.stride(0) if t.size(0) > 1 else t.size(1)
+
+
+def _ln_descs(zs, gammas, betas, outs, epss, relu: bool, stats=None) -> List['_ffi.LnDesc']:
+    descs, off = [], 0
+    for k, (z, out) in enumerate(zip(zs, outs)):
+        M, N = z.shape
+        if M:
+            d = _ffi.LnDesc(z=z.data_ptr(), gamma=_ffi.ptr(gammas[k]), beta=_ffi.ptr(betas[k]), out=out.data_ptr(),
+                            M=M, ldz=_ln_ld(z), ldout=_ln_ld(out), N=N, relu=int(relu), eps=float(epss[k]))
+            if stats is not None:
+                d.mean, d.rstd = stats[0, off:].data_ptr(), stats[1, off:].data_ptr()
+            descs.append(d)
+        off += M
+    return descs
+
+
+class _LayerNormActMany(torch.autograd.Function):
+    """tensors = (z, gamma, beta) per matrix (gamma / beta None without the affine).  The forward is one
+    cwn_layernorm_act_f32 launch and keeps z, out and the rows' mean / rstd; the backward is one cwn_layernorm_bwd_f32
+    call (dz, and the column sums dgamma / dbeta without atomics)."""
+
+    @staticmethod
+    def forward(ctx, relu: bool, epss: Tuple[float, ...], *tensors):
+        n = len(tensors) // 3
+        zs = [_rowmajor(tensors[3 * k], 'z') for k in range(n)]
+        gammas = [None if tensors[3 * k + 1] is None else tensors[3 * k + 1].contiguous() for k in range(n)]
+        betas = [None if tensors[3 * k + 2] is None else tensors[3 * k + 2].contiguous() for k in range(n)]
+        dev = zs[0].device
+        outs = [torch.empty(z.size(0), z.size(1), dtype=torch.float32, device=dev) for z in zs]
+        stats = torch.empty(2, max(sum(z.size(0) for z in zs), 1), dtype=torch.float32, device=dev)
+        descs = _ln_descs(zs, gammas, betas, outs, epss, relu, stats)
+        if descs:
+            _ffi.layer_norm_act(descs, dev)
+        ctx.relu, ctx.epss, ctx.n = relu, epss, n
+        ctx.params = [(tensors[3 * k + 1], tensors[3 * k + 2]) for k in range(n)]     # (the Parameters: their .grad is the target)
+        ctx.save_for_backward(stats, *zs, *outs, *[g for g in gammas if g is not None])
+        return tuple(outs)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *gs):
+        n, relu = ctx.n, ctx.relu
+        saved = ctx.saved_tensors
+        stats, zs, outs = saved[0], saved[1:1 + n], saved[1 + n:1 + 2 * n]
+        gsaved = iter(saved[1 + 2 * n:])
+        needs = ctx.needs_input_grad[2:]
+        grads: List[Optional[Tensor]] = [None] * (3 * n)
+        dev = stats.device
+        descs, live, off = [], [], 0
+        for k in range(n):
+            z, out = zs[k], outs[k]
+            M, N = z.shape
+            gamma_p, beta_p = ctx.params[k]
+            gamma = next(gsaved) if gamma_p is not None else None
+            g = gs[k]
+            row0, off = off, off + M
+            if g is None:
+                continue
+            want_g = gamma_p is not None and needs[3 * k + 1]
+            want_b = beta_p is not None and needs[3 * k + 2]
+            # the column sums go straight into the parameters' .grad where both wanted ones have one (accumulate_into_grad())
+            tg = _grad_target(gamma_p) if want_g else None
+            tb = _grad_target(beta_p) if want_b else None
+            acc = (want_g or want_b) and (tg is not None or not want_g) and (tb is not None or not want_b)
+            dgamma = dbeta = None
+            if want_g:
+                dgamma = tg if acc else torch.zeros(N, dtype=torch.float32, device=dev)
+                grads[3 * k + 1] = None if acc else dgamma
+            if want_b:
+                dbeta = tb if acc else torch.zeros(N, dtype=torch.float32, device=dev)
+                grads[3 * k + 2] = None if acc else dbeta
+            dy = _rowmajor(g, 'grad')
+            dz = torch.empty(M, N, dtype=torch.float32, device=dev)
+            if needs[3 * k]:
+                grads[3 * k] = dz
+            live += [dy, dz, dgamma, dbeta]
+            if M:
+                descs.append(_ffi.LnDesc(
+                    z=z.data_ptr(), gamma=_ffi.ptr(gamma), out=out.data_ptr(), mean=stats[0, row0:].data_ptr(),
+                    rstd=stats[1, row0:].data_ptr(), dy=dy.data_ptr(), dz=dz.data_ptr(), dgamma=_ffi.ptr(dgamma),
+                    dbeta=_ffi.ptr(dbeta), M=M, ldz=_ln_ld(z), ldout=_ln_ld(out), lddy=_ln_ld(dy), lddz=_ln_ld(dz), N=N,
+                    relu=int(relu), eps=float(ctx.epss[k]), accumulate=int(bool(acc))))
+        if descs:
+            _ffi.layer_norm_bwd(descs, dev)
+        return (None, None) + tuple(grads)
+
+
+def _ln_on_kernel(z: Tensor, norm) -> bool:
+    """Does cwn_layernorm_* take this matrix?  float32 rows of at most _ffi.LN_MAX_N columns on the GPU, normalised over the
+    last dimension; float64, CPU tensors and wider rows run torch.nn.functional.layer_norm."""
+    for t in (z, norm.weight, norm.bias):
+        if t is not None and t.dtype in (torch.float16, torch.bfloat16):
+            raise TypeError(f'layer_norm_act_many computes in float32 (or float64 through torch): got {t.dtype}')
+    return (z.is_cuda and z.dtype == torch.float32 and z.dim() == 2 and tuple(norm.normalized_shape) == (z.size(1),)
+            and 1 <= z.size(1) <= _ffi.LN_MAX_N
+            and all(p is None or (p.is_cuda and p.dtype == torch.float32) for p in (norm.weight, norm.bias)))
+
+
+def layer_norm_act_many(zs: Sequence[Tensor], norms: Sequence[torch.nn.LayerNorm], relu: bool = True) -> List[Tensor]:
+    """act(norm_k(z_k)) for every matrix of a stage in ONE launch (per <= 16), act = ReLU or nothing; differentiable
+    w.r.t. z, weight and bias.  Inside accumulate_into_grad() the weight / bias gradients are added into their .grad."""
+    if len(zs) != len(norms):
+        raise ValueError('one LayerNorm per matrix')
+    res: List[Optional[Tensor]] = [None] * len(zs)
+    take = []
+    for k, (z, norm) in enumerate(zip(zs, norms)):
+        if _ln_on_kernel(z, norm):
+            take.append(k)
+        else:
+            y = torch.nn.functional.layer_norm(z, norm.normalized_shape, norm.weight, norm.bias, norm.eps)
+            res[k] = torch.relu(y) if relu else y
+    if not take:
+        return res
+    flat: List[Optional[Tensor]] = []
+    for k in take:
+        flat += [zs[k], norms[k].weight, norms[k].bias]
+    epss = tuple(float(norms[k].eps) for k in take)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in flat):
+        outs = _LayerNormActMany.apply(bool(relu), epss, *flat)
+    else:
+        zc = [_rowmajor(zs[k], 'z') for k in take]
+        gammas = [None if norms[k].weight is None else norms[k].weight.detach().contiguous() for k in take]
+        betas = [None if norms[k].bias is None else norms[k].bias.detach().contiguous() for k in take]
+        outs = [torch.empty(z.size(0), z.size(1), dtype=torch.float32, device=z.device) for z in zc]
+        descs = _ln_descs(zc, gammas, betas, outs, epss, bool(relu))
+        if descs:
+            _ffi.layer_norm_act(descs, zc[0].device)
+    for k, o in zip(take, outs):
+        res[k] = o
+    return res
+
+
+# ------------------------------------------------------------------------------------------------
 # gemm_many + aggregate_many of one propagate step as ONE autograd node
 # ------------------------------------------------------------------------------------------------
 FUSED_PROPAGATE_NODE = os.environ.get('CWN_FUSED_PROPAGATE_NODE') != '0'     # A/B: '0' keeps the two nodes

@@ -390,3 +390,35 @@ def reddit_like_complexes(num: int = 32, seed: int = 0, n_lo: int = 200, n_hi: i
         y = torch.from_numpy(rng.integers(0, 2, size=1))
         out.append(clique_lift(n, edges, vx, max_dim=2, init_method=init_method, y=y))
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# CSL: circulant skip-link graphs (the reference's CSL dataset, exp/scripts/cwn-csl.sh)
+# ------------------------------------------------------------------------------------------------
+CSL_NODES = 41
+CSL_SKIPS = (2, 3, 4, 5, 6, 9, 11, 12, 13, 16)        # one isomorphism class per skip length: ten classes
+
+
+def csl_graph(skip: int, n: int = CSL_NODES) -> Tuple[int, List[Tuple[int, int]]]:
+    """C_{n, skip}: the cycle 0 - 1 - ... - (n - 1) - 0 plus a link from every vertex to the one `skip` further.  Regular of
+    degree 4, so 1-WL sees one graph in all of them; the rings tell them apart.  (num_vertices, sorted edges (u < v))."""
+    edges = set()
+    for v in range(n):
+        for w in ((v + 1) % n, (v + skip) % n):
+            edges.add((min(v, w), max(v, w)))
+    return n, sorted(edges)
+
+
+def csl_graphs(num: int = 150, seed: int = 0, max_ring: int = 8) -> List[Complex]:
+    """`num` ring-lifted CSL complexes: graph k is a randomly relabelled copy of C_{41, CSL_SKIPS[k % 10]} with the class
+    k % 10 as its target (int64), featureless as the reference feeds them (data/datasets/csl.py: atom type 0 on every
+    vertex, bond type 0 on every edge -- [N, 1] floats, the form EmbedSparseCIN expects).  max_ring 8 is cwn-csl.sh's."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for k in range(num):
+        cls = k % len(CSL_SKIPS)
+        n, edges = csl_graph(CSL_SKIPS[cls])
+        n, edges = relabel(n, edges, rng.permutation(n))
+        out.append(ring_lift(n, edges, torch.zeros(n, 1), torch.zeros(len(edges), 1), max_k=max_ring,
+                             y=torch.tensor([cls], dtype=torch.long)))
+    return out

@@ -995,6 +995,38 @@ int cwn_norm_bwd_apply_f32(const cwn_norm_desc* descs_host, int n, cwn_stream_t 
 #define CWN_NORM_BWD_FUSED_MAX_ROWS 4096
 int cwn_norm_bwd_f32(const cwn_norm_desc* descs_host, int n, int accumulate, cwn_stream_t stream);
 
+/* torch.nn.LayerNorm((N,), eps, elementwise_affine) + ReLU (relu = 1) or nothing (relu = 0) over the rows of up to
+ * CWN_MAX_NORM_DESCS matrices per launch, in fp32 (graph_norm='ln', mp/nn.py:39-47; csrc/cwn_layernorm.hip).  The
+ * statistics are per ROW, so this is a launch of its own behind the GEMM, not a GEMM prologue / epilogue.  1 <= N <= 1024
+ * (a wave holds a row in registers); a descriptor whose data pointers are 16-byte aligned, whose strides are multiples
+ * of 4 and whose N is a multiple of 4 moves 16 bytes per lane, any other takes the element-wise form (per descriptor).
+ * The column sums of the backward are bit-reproducible: per-workgroup partials in the caller's workspace, summed in
+ * workgroup order by a second launch of the same call -- no floating-point atomics. */
+typedef struct cwn_ln_desc {
+    const float* z;      /* [M, N] pre-normalisation rows, row stride ldz */
+    const float* gamma;  /* [N] or NULL (= 1): elementwise_affine=False */
+    const float* beta;   /* [N] or NULL (= 0) */
+    float* out;          /* forward: act(LN(z) * gamma + beta), row stride ldout; must not alias z.
+                            backward: the SAME matrix, read for the ReLU mask (out > 0) */
+    float* mean;         /* [M] forward: written when non-NULL (training); backward: read */
+    float* rstd;         /* [M] 1 / sqrt(biased row variance + eps), same rule */
+    const float* dy;     /* backward: [M, N] gradient w.r.t. out, row stride lddy */
+    float* dz;           /* backward: [M, N] out, row stride lddz; may alias dy, not z */
+    float* dgamma;       /* backward, or NULL: [N] written (accumulate == 0) or added to (accumulate != 0: the parameter's .grad) */
+    float* dbeta;        /* same */
+    int64_t M, ldz, ldout, lddy, lddz;
+    int32_t N; int32_t relu; float eps; int32_t accumulate;
+    const int64_t* m_dev; /* or NULL: rows that exist (M = capacity). Rows >= *m_dev are neither read nor written and are not
+                             in dgamma / dbeta; *m_dev < 1: nothing but dgamma / dbeta = 0 (accumulate == 0) */
+} cwn_ln_desc;
+/* out = act((z - mean) * rstd * gamma + beta) per row; n <= CWN_MAX_NORM_DESCS.  CWN_ERR_BAD_ARG: n > 16, N < 1, N > 1024. */
+int cwn_layernorm_act_f32(const cwn_ln_desc* descs_host, int n, cwn_stream_t stream);
+/* Bytes of the partial column sums cwn_layernorm_bwd_f32 needs for these descriptors (0 when none asks for dgamma / dbeta). */
+size_t cwn_layernorm_bwd_workspace_bytes(const cwn_ln_desc* descs_host, int n);
+/* dz = rstd * (g - mean_N(g) - xhat * mean_N(g * xhat)) with g = dy * [out > 0] * gamma, and dbeta = sum_m dy * [out > 0],
+ * dgamma = sum_m dy * [out > 0] * xhat.  Two launches; CWN_ERR_BAD_ARG also for a workspace smaller than asked for. */
+int cwn_layernorm_bwd_f32(const cwn_ln_desc* descs_host, int n, void* workspace, size_t workspace_bytes, cwn_stream_t stream);
+
 /* Weight gradient of a Linear layer on the matrix cores, accumulated:
  *     dW[n, k] += sum_m dZ[m, n] * prologue([X | X2])[m, k]          db[n] += sum_m dZ[m, n]
  * dW is [N, K + K2] (row stride lddw, torch Linear layout) and is ADDED to (the M rows are split
