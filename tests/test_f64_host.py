@@ -53,9 +53,9 @@ def _desc(**kw):
     return (_ffi.AggDesc * 1)(_ffi.AggDesc(**base))
 
 
-def test_f64_bad_arguments_are_refused_before_any_launch():
-    lib = _ffi.lib()
-    agg = lib.cwn_aggregate_f64
+def _check_refusals(agg, gat, off):
+    """The descriptors and gather arguments both element types refuse (one validity rule: csrc/cwn_aggregate_body.h);
+    `off` is a byte offset that breaks the type's alignment."""
     assert agg(None, 1, None) == BAD_ARG
     assert agg(_desc(), 0, None) == BAD_ARG
     nine = (_ffi.AggDesc * 9)(*[_ffi.AggDesc(n_dst=4, F=8, out=0x1000) for _ in range(9)])
@@ -71,18 +71,28 @@ def test_f64_bad_arguments_are_refused_before_any_launch():
     assert agg(_desc(rowptr=0x3000), 1, None) == BAD_ARG
     assert agg(_desc(rowptr=0x3000, ia=0x4000, A=0x5000, msg_op=1), 1, None) == BAD_ARG
     assert agg(_desc(rowptr=0x3000, ia=0x4000, A=0x5000, msg_op=4, ib=0x6000, B=0x7000, b_width=8), 1, None) == BAD_ARG
-    # doubles lie on 8 bytes: a pointer that is only 4-byte aligned
-    assert agg(_desc(out=0x1004), 1, None) == ALIGN
-    assert agg(_desc(self_x=0x2004), 1, None) == ALIGN
-    assert agg(_desc(eps=0x2004), 1, None) == ALIGN
+    assert agg(_desc(out=0x1000 + off), 1, None) == ALIGN
+    assert agg(_desc(self_x=0x2000 + off), 1, None) == ALIGN
     assert agg(_desc(n_dst=0), 1, None) == 0                # nothing to do
-    gat = lib.cwn_gather_rows_f64
     assert gat(None, 0, 0, None, 0, None, None) == BAD_ARG
     assert gat(None, 5, 4, None, 3, None, None) == BAD_ARG
     assert gat(0x1000, 5, 4, 0x2000, -1, 0x3000, None) == BAD_ARG
-    assert gat(0x1004, 5, 4, 0x2000, 3, 0x3000, None) == ALIGN
-    assert gat(0x1000, 5, 4, 0x2000, 3, 0x3004, None) == ALIGN
+    assert gat(0x1000 + off, 5, 4, 0x2000, 3, 0x3000, None) == ALIGN
+    assert gat(0x1000, 5, 4, 0x2000, 3, 0x3000 + off, None) == ALIGN
     assert gat(None, 5, 4, None, 0, None, None) == 0        # an empty index
+
+
+def test_f64_bad_arguments_are_refused_before_any_launch():
+    lib = _ffi.lib()
+    # doubles lie on 8 bytes: a pointer that is only 4-byte aligned
+    _check_refusals(lib.cwn_aggregate_f64, lib.cwn_gather_rows_f64, off=4)
+    assert lib.cwn_aggregate_f64(_desc(eps=0x2004), 1, None) == ALIGN
+
+
+def test_f32_bad_arguments_are_refused_before_any_launch():
+    lib = _ffi.lib()
+    # floats lie on 4 bytes; the f32 entry does not look at eps
+    _check_refusals(lib.cwn_aggregate_f32, lib.cwn_gather_rows_f32, off=2)
 
 
 def test_small_operand_flag_follows_the_element_size():
