@@ -283,11 +283,13 @@ __global__ __launch_bounds__(kThreads, (KP <= 128 && RT == 2 && !(CWN_GEMM_NOSPI
     const int nblk = B.blk_start[di + 1] - B.blk_start[di];
     const int tiles_n = B.n_tiles_n[di];
     int tiles = B.n_tiles[di];
+    int64_t Mst = D.M;               // rows that are STORED (D.M bounds the addresses of the loads)
     if (D.m_dev != nullptr) {        // (uniform) a static batch: the row tiles below the rows that exist -- a PREFIX of the tile numbers
         const int64_t mv = *D.m_dev;
         const int64_t live = (mv < 0 ? 0 : (mv < D.M ? mv : D.M));
         const int64_t t = (live + BM - 1) / BM * tiles_n;
         tiles = t < tiles ? (int)t : tiles;
+        Mst = live;                  // the tile the count ends in stores its live rows only: the rows behind are never written
     }
     const bool vec = FAST;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -594,7 +596,7 @@ __global__ __launch_bounds__(kThreads, (KP <= 128 && RT == 2 && !(CWN_GEMM_NOSPI
             const int64_t rb = m_base + wm * (16 * RT) + rt * 16 + (lo ? j + 8 : j);
             const int n0 = n_base + (lo ? 0 : 16) + 4 * g;
             const bool full = n0 + 3 < N;
-            if (ra < M && n0 < N) {
+            if (ra < Mst && n0 < N) {
                 float* yp = D.Y + ra * ldy + n0;
                 if (add_out) {      // Y += : this launch is the only writer of Y (host contract), a plain read-modify-write
 if (full && vec) {
@@ -611,7 +613,7 @@ if (full && vec) {
                     for (int r = 0; r < 4; ++r)
                         if (n0 + r < N) yp[r] = va[r];
             }
-            if (rb < M && n0 < N) {
+            if (rb < Mst && n0 < N) {
                 float* yp = D.Y + rb * ldy + n0;
                 if (add_out) {
 if (full && vec) {

@@ -61,11 +61,13 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_split_kernel(SplitBatch B) {
     const int blk = blockIdx.x - B.blk_start[di];
     const int nblk = B.blk_start[di + 1] - B.blk_start[di];
     int tiles = B.n_tiles[di];
+    int64_t Mst = D.M;                       // rows that are STORED (D.M bounds the addresses of the loads)
     if (D.m_dev != nullptr) {                // (uniform) a static batch: the 64-row tiles below the rows that exist
         const int64_t mv = *D.m_dev;
         const int64_t live = (mv < 0 ? 0 : (mv < D.M ? mv : D.M));
         const int64_t t = (live + TM - 1) / TM;
         tiles = t < tiles ? (int)t : tiles;
+        Mst = live;                          // the tile the count ends in stores its live rows only
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int l15 = lane & 15, kq = lane >> 4;
@@ -155,7 +157,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_split_kernel(SplitBatch B) {
 #pragma unroll
         for (int rt = 0; rt < 4; ++rt) {
             const int64_t row = row0 + rt * 16 + l15;
-            if (row < D.M) {
+            if (row < Mst) {
 #pragma unroll
                 for (int ct = 0; ct < 2; ++ct) {
                     // (epilogue constants are re-read per tile from L1/L2: held in registers across

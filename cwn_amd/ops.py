@@ -1458,6 +1458,15 @@ class Gemm:
         if X2 is not None and X2.size(0) != X.size(0):
             raise ValueError('X and X2 must have the same number of rows')
         cs = self.col_stats
+        m_dev = _ffi.dyn(X.size(0))
+        if m_dev is not None and (cs is not None or self.bnb is not None):
+            # (cwn_gemm_f32 refuses m_dev with col_sum / col_sumsq / bnb; WITHOUT it the statistics epilogue sums, and the
+            #  BatchNorm-backward prologue divides by, the capacity rows of a static batch -- stale rows of an earlier batch in
+            #  every BatchNorm of every step.  cwn_dense_stage_f32 / cwn_dense_stage_bwd_f32 carry the count.)
+            raise RuntimeError('cwn_gemm_f32 takes no device-side row count together with BatchNorm statistics or the '
+                               'BatchNorm-backward prologue: inside a static batch these launches run on the stage kernels '
+                               '(cwn_dense_stage_f32 / cwn_dense_stage_bwd_f32: hidden width 64 or 128, and not with '
+                               'CWN_STAGE_KERNEL=0 / ops.STAGE_KERNEL = False)')
         return _ffi.GemmDesc(
             X=X.data_ptr(), X2=_ffi.ptr(X2), W=self.w_packed.data_ptr() if packed else W.data_ptr() + 4 * (self.w_col0 or 0),
             bias=_ffi.ptr(self.bias),
@@ -1472,7 +1481,7 @@ class Gemm:
             N=W.size(1 if self.w_trans else 0), K=K, K2=K2, relu=int(self.relu), in_relu=int(self.in_relu),
             w_trans=int(self.w_trans), bnb=None if self.bnb is None else C.pointer(self.bnb),
             # (a static batch: the rows that exist -- the launch walks the row tiles below the device-side count only)
-            m_dev=_ffi.dyn(X.size(0)) if (cs is None and self.bnb is None) else None,
+            m_dev=m_dev,
             flags=(_ffi.GEMM_EXACT if (self.exact or GEMM_EXACT) else 0) | (_ffi.GEMM_W_PACKED if packed else 0)
             | (_ffi.GEMM_ADD_OUT if self.add_out else 0) | (int(self.debug) << 8))
 

@@ -298,6 +298,12 @@ class StaticTrainStep(TrainStep):
     def __init__(self, model: torch.nn.Module, static: StaticBatch, task_type: str = 'regression', lr: float = 1e-3,
                  use_graph: bool = True, optimizer=None, share: Optional[TrainStep] = None):
         refuse_unsupported_layers(model, 'StaticTrainStep', static, training=True)
+        if not ops.STAGE_KERNEL:
+            # (without the stage kernels the BatchNorm(train) statistics are cwn_gemm_f32's epilogue, which has no device-side
+            #  row count: they would be taken over the capacity rows of a slot -- ops.Gemm.desc refuses such a launch too)
+            raise NotImplementedError('StaticTrainStep: CWN_STAGE_KERNEL=0 (ops.STAGE_KERNEL = False) is not served: the '
+                                      'BatchNorm statistics of a static batch need the row count of cwn_dense_stage_f32; use '
+                                      'collated batches with TrainStep under that switch')
         self.sb = static
         static.build_backward = True                  # (mode 'csr': the fill also builds the transposed plans)
         static.fill()                                 # the buffers hold real batches from here on (warm-up)

@@ -26,6 +26,14 @@
  *     any shape up to the capacity; the item-table kernels (cwn_layer_fused_f32, cwn_layer_bwd_own_f32) have always
  *     worked this way (their sizes live in the item table).  cwn_collate_tables / cwn_layer_items_build_dev /
  *     cwn_layer_bwd_items_build_dev produce the per-batch tables on the device.
+ *     Who checks "*m_dev <= capacity": cwn_gemm_f32 (both kernels), cwn_gemm_tn_f32, cwn_layernorm_*, cwn_dropout_f32,
+ *     cwn_loss_f32 / cwn_loss_cols_f32, cwn_csr_long_rows, cwn_embedding_bwd_f32, cwn_embed_front_f32 and
+ *     cwn_embed_front_bwd_f32 CLAMP the count to the capacity (a larger count behaves as the capacity); cwn_dense_stage_f32 /
+ *     _ex / _bwd, cwn_bn_finalize_f32, cwn_norm_*, cwn_update_mlp_f32 / cwn_update_mlp3_f32 and cwn_aggregate_f32 / _f64 take
+ *     the count AS IT IS -- there the caller's vouching is what keeps the stores inside the buffers (the collate guard,
+ *     cwn_collate_guard, zeroes the counts of a batch beyond its capacities before any of them is read).
+ *     tests/test_gpu_row_counts.py pins the contract per entry point at counts of 0, 1, the capacity and around every tile
+ *     height.
  */
 #ifndef CWN_HIP_H
 #define CWN_HIP_H
@@ -881,7 +889,8 @@ typedef struct cwn_gemm_desc {
     const cwn_gemm_bnb* bnb;  /* HOST pointer or NULL, see the struct above: w_trans launches with 16-byte aligned operands and
                                K <= 128 (the launch's tile shapes for K <= 128: any N); CWN_ERR_BAD_ARG otherwise */
     const int64_t* m_dev;     /* (ABI 23) or NULL: the rows that exist (M = capacity, see "Conventions"): the workgroups walk the
-                               * row tiles below *m_dev only -- a static batch's message products used to be taken over the
+                               * row tiles below *m_dev only, and the tile the count ends in stores its rows below the count
+                               * only (ADD_OUT: adds onto) -- a static batch's message products used to be taken over the
                                * CAPACITY of its buffers (REDDIT-32: 1.46 x the batch).  Not with col_sum / col_sumsq or bnb
                                * (CWN_ERR_BAD_ARG): those launches have cwn_dense_stage_f32's own count */
 } cwn_gemm_desc;

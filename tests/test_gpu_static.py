@@ -301,6 +301,98 @@ def test_static_train_step_matches_the_per_batch_step(variant):
             assert torch.equal(a, b), n_
 
 
+
+def _static_steps_against_per_batch_steps(check=True):
+    """StaticTrainStep replayed on batches of 48, 20 and 1 complexes (capacity 48: from the second step on the padding rows of
+    every buffer hold the rows of an earlier, larger batch, and the live row counts are no multiples of a 32-row band) against
+    TrainStep's eager step on the collated batches from the same state, under whatever switches the caller has set: loss, flat
+    gradient and BatchNorm running statistics inside the bounds of test_static_train_step_matches_the_per_batch_step.  The lone
+    complex of the last batch is the first unused one of the pool with two rings (two rows per BatchNorm: torch defines no
+    training statistic over one).  Every figure is printed before it is asserted; returns the largest distance of a BatchNorm
+    running statistic from the per-batch step's."""
+    from cwn_amd import csr
+    from cwn_amd.static_batch import StaticBatch
+    from cwn_amd.static_graph import StaticTrainStep
+    from cwn_amd.train import TrainStep
+    pool, p = _packed(n_hi=28)
+    B = 48
+    m1, m2 = _model(128, 2, seed=4), _model(128, 2, seed=4)
+    m2.load_state_dict(m1.state_dict())
+    batches = _batches(len(pool), B, 13, sizes=[B, 20])
+    used = set(int(i) for b in batches for i in b)
+    lone = next(i for i in range(len(pool)) if i not in used and pool[i].cochains[2].num_cells >= 2)
+    batches.append(np.array([lone]))
+    sb = StaticBatch(p, B)
+    sb.set_batch(batches[0])
+    st = StaticTrainStep(m1, sb, lr=1e-3)
+    ref = TrainStep(m2, [p.collate(idx) for idx in batches], lr=1e-3, use_graph=False)
+    worst_stat = 0.0
+    for j, idx in enumerate(batches):
+        l1 = st.step_on([idx])[0].clone()
+        l2 = ref.step(j)
+        torch.cuda.synchronize()
+        g1, g2 = st.bucket.flat, ref.bucket.flat
+        rel = float((g1 - g2).norm() / g2.norm())
+        print(f'[static train] step {j} ({len(idx)} complexes): loss {float(l1):.6f} vs {float(l2):.6f}, relative L2 distance of '
+              f'the gradient {rel:.2e}')
+        bad = []
+        for (n_, a), (_, b) in zip(m1.named_buffers(), m2.named_buffers()):
+            if a.dtype.is_floating_point:            # BatchNorm running statistics: the batch's own rows only
+                dist = float((a - b).abs().max())
+                worst_stat = max(worst_stat, dist)
+                if not torch.allclose(a, b, rtol=5e-3, atol=2e-3):
+                    bad.append((n_, dist))
+            elif not torch.equal(a, b):
+                bad.append((n_, 'counter'))
+        print(f'[static train] step {j}: largest distance of a BatchNorm running statistic {worst_stat:.3e}; outside rtol 5e-3 / '
+              f'atol 2e-3: {bad[:4]}{" ..." if len(bad) > 4 else ""}')
+        if check:
+            assert abs(float(l1) - float(l2)) <= 1e-5 * max(1.0, abs(float(l2))), (j, float(l1), float(l2))
+            assert rel < 2e-5, (j, rel)
+            assert not bad, (j, bad)
+        # every step starts from ONE state (see test_static_train_step_matches_the_per_batch_step)
+        ref.opt.flat_p.copy_(st.opt.flat_p)
+        ref.opt.exp_avg.copy_(st.opt.exp_avg)
+        ref.opt.exp_avg_sq.copy_(st.opt.exp_avg_sq)
+        for (_, a), (_, b) in zip(m1.named_buffers(), m2.named_buffers()):
+            b.copy_(a)
+    csr.check_errors(DEV)
+    assert len(st._graphs) == 1
+    return worst_stat
+
+
+def test_static_train_step_with_the_stage_kernel_off_is_refused_by_name():
+    """CWN_STAGE_KERNEL=0 (ops.STAGE_KERNEL = False): the BatchNorm(train) statistics then come from the epilogue of
+    cwn_gemm_f32, which takes no device-side row count (include/cwn_hip.h: cwn_gemm_desc.m_dev) -- ops.Gemm.desc used to DROP the
+    count for such a launch, so a static step summed the statistics over the capacity rows of its buffers: up to 31 stale rows
+    of an earlier batch in the last band of every BatchNorm, a forward and a gradient that are slightly wrong in every step.
+    The outcome is pinned: StaticTrainStep refuses the switch by name (and ops.Gemm.desc refuses the launch, see
+    test_gpu_row_counts.py); should the statistics epilogue ever learn the count, the step must match the per-batch step
+    under the same switch inside the bounds of test_static_train_step_matches_the_per_batch_step.  Never a silent
+    capacity-wide statistic."""
+    from cwn_amd import ops
+    prev, ops.STAGE_KERNEL = ops.STAGE_KERNEL, False
+    try:
+        try:
+            _static_steps_against_per_batch_steps()
+        except NotImplementedError as e:
+            assert 'CWN_STAGE_KERNEL' in str(e) and 'StaticTrainStep' in str(e), str(e)
+    finally:
+        ops.STAGE_KERNEL = prev
+
+
+def test_static_train_step_without_live_batchnorm_matches_the_per_batch_step():
+    """CWN_LIVE_BN=0 (dense_train.LIVE_BN = LIVE_BN_BWD = False): the statistics are the per-band sums of cwn_dense_stage_f32
+    reduced by cwn_bn_finalize_f32 -- both carry the device-side count -- on batches of 48, 20 and 1 complexes."""
+    from cwn_amd import dense_train as DT
+    prev = DT.LIVE_BN, DT.LIVE_BN_BWD
+    DT.LIVE_BN = DT.LIVE_BN_BWD = False
+    try:
+        _static_steps_against_per_batch_steps()
+    finally:
+        DT.LIVE_BN, DT.LIVE_BN_BWD = prev
+
+
 def test_a_complex_beyond_a_workgroup_is_refused_by_fits_and_flagged_by_the_device():
     """A 60-atom molecule does not fit one workgroup at width 128 (48 atoms + 48 bonds are the 96 staged rows): fits() says so for the batches that hold it (the caller
     routes them to PackedComplexes.collate), and pushing such a batch through anyway sets the sticky UNFIT bit."""
