@@ -24,7 +24,11 @@ EXPORTS = ('cwn_abi_version', 'cwn_error_string', 'cwn_target_arch', 'cwn_csr_wo
            'cwn_bn_finalize_f32', 'cwn_step_begin', 'cwn_axpy_eps_f32', 'cwn_dropout_f32', 'cwn_embed_front_bwd_f32', 'cwn_norm_act_f32', 'cwn_norm_bwd_reduce_f32', 'cwn_norm_bwd_apply_f32', 'cwn_norm_bwd_f32',
            'cwn_layernorm_act_f32', 'cwn_layernorm_bwd_workspace_bytes', 'cwn_layernorm_bwd_f32',
            'cwn_gemm_tn_f32', 'cwn_gemm_tn_workspace_bytes', 'cwn_adam_f32', 'cwn_adam_dev_f32', 'cwn_loss_f32', 'cwn_loss_cols_f32', 'cwn_embedding_fwd_f32', 'cwn_embedding_bwd_f32', 'cwn_embed_front_f32', 'cwn_head_f32', 'cwn_head_bwd_f32', 'cwn_head_pool_floats', 'cwn_lift_create', 'cwn_lift_size', 'cwn_lift_copy', 'cwn_lift_destroy',
-           'cwn_lift_many', 'cwn_lift_many_count', 'cwn_lift_many_lengths', 'cwn_lift_many_copy', 'cwn_lift_many_destroy')
+           'cwn_lift_many', 'cwn_lift_many_count', 'cwn_lift_many_lengths', 'cwn_lift_many_copy', 'cwn_lift_many_destroy',
+           # the evaluation pass (csrc/cwn_metrics.hip)
+           'cwn_metric_rank_workspace_bytes', 'cwn_metric_rank_f32', 'cwn_metric_abs_err_workspace_bytes', 'cwn_metric_abs_err_f32',
+           'cwn_metric_argmax_hits_workspace_bytes', 'cwn_metric_argmax_hits_f32', 'cwn_metric_pdist_below_workspace_bytes',
+           'cwn_metric_pdist_below_f64', 'cwn_loss_segments_f32')
 
 
 class CsrDesc(C.Structure):
@@ -442,6 +446,29 @@ def lib():
     L.cwn_loss_f32.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.cwn_loss_cols_f32.restype = C.c_int
     L.cwn_loss_cols_f32.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cwn_loss_segments_f32.restype = C.c_int
+    L.cwn_loss_segments_f32.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                        C.c_void_p]
+    L.cwn_metric_rank_workspace_bytes.restype = C.c_size_t
+    L.cwn_metric_rank_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
+    L.cwn_metric_rank_f32.restype = C.c_int
+    L.cwn_metric_rank_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p]
+    L.cwn_metric_abs_err_workspace_bytes.restype = C.c_size_t
+    L.cwn_metric_abs_err_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
+    L.cwn_metric_abs_err_f32.restype = C.c_int
+    L.cwn_metric_abs_err_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]
+    L.cwn_metric_argmax_hits_workspace_bytes.restype = C.c_size_t
+    L.cwn_metric_argmax_hits_workspace_bytes.argtypes = [C.c_int64]
+    L.cwn_metric_argmax_hits_f32.restype = C.c_int
+    L.cwn_metric_argmax_hits_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p,
+                                             C.c_void_p]
+    L.cwn_metric_pdist_below_workspace_bytes.restype = C.c_size_t
+    L.cwn_metric_pdist_below_workspace_bytes.argtypes = [C.c_int64]
+    L.cwn_metric_pdist_below_f64.restype = C.c_int
+    L.cwn_metric_pdist_below_f64.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_size_t, C.c_void_p,
+                                             C.c_void_p]
     L.cwn_embedding_fwd_f32.restype = C.c_int
     L.cwn_embedding_fwd_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                         C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]

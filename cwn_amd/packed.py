@@ -322,6 +322,23 @@ class PackedComplexes:
         batch._collate_tables = tab     # keep the tables alive until the launch has consumed them
         return batch
 
+    def labels(self, idx: Sequence[int]) -> torch.Tensor:
+        """The labels of the complexes `idx`, in that order: equal to `collate(idx).y`, as one gather from the packed `y`
+        (the source positions come from the host's metadata: one small upload, no collate launch, no synchronisation)."""
+        if self.y is None:
+            raise ValueError('the packed complexes carry no labels')
+        idx = np.asarray(idx, dtype=np.int64).reshape(-1)
+        if idx.size and (idx.min() < 0 or idx.max() >= self.num):
+            raise IndexError(f'complex numbers outside 0 .. {self.num - 1}')
+        pk = self.y
+        ln, st = np.asarray(pk.length, dtype=np.int64)[idx], np.asarray(pk.start, dtype=np.int64)[idx]
+        if ln.size and (ln == 1).all():
+            src = st
+        else:
+            src = np.repeat(st, ln) + (np.arange(int(ln.sum()), dtype=np.int64) - np.repeat(np.cumsum(ln) - ln, ln))
+        src_dev = torch.from_numpy(np.ascontiguousarray(src)).to(self.device, non_blocking=True)
+        return pk.data.reshape(-1).index_select(0, src_dev)
+
 
 class PackedLoader:
     """The reference's DataLoader (data/data_loading.py:84-111: `for batch in loader` of exp/train_utils.py:35)

@@ -1335,6 +1335,55 @@ int cwn_loss_f32(int32_t kind, const float* pred, const float* y, int64_t n, flo
 int cwn_loss_cols_f32(int32_t kind, const float* pred, const float* y, int64_t n, int64_t cols, float* loss, float* grad,
                       const int64_t* n_dev, cwn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The evaluation pass (exp/train_utils.py:92-211: eval() and the Evaluator's metrics), csrc/cwn_metrics.hip.
+ * Additive to ABI 24.  The caller owns every buffer; `workspace` (8-byte aligned) holds at least what the matching
+ * *_workspace_bytes function returns (0 = arguments no launch accepts) and may be reused by the next call on the same
+ * stream.  No entry point allocates, frees or synchronises; none uses atomics: every sum is per-workgroup partials added
+ * in a fixed order, so all results, the float64 ones included, are bit-identical from run to run.
+ * ------------------------------------------------------------------------------------------ */
+#define CWN_METRIC_TILE 256            /* rows of a tile of the rank kernel (= its workgroup) */
+#define CWN_METRIC_PDIST_TILE 64       /* rows of a tile of the pair-distance kernel */
+#define CWN_METRIC_FLAG_NONFINITE 1    /* *flag bit: a NaN / +-inf prediction at a labeled entry */
+#define CWN_METRIC_FLAG_LABEL 2        /* *flag bit: a label that is neither 0, 1 nor NaN (counted nowhere) */
+
+/* The integer rank counts behind ROC-AUC and average precision, per column t of pred [n, cols] (fp32) against y [n, cols]
+ * (fp32: 1 positive, 0 negative, NaN unlabeled and ignored).  For every labeled positive row i, over the labeled rows j of
+ * the column: lt_i = negatives with s_j < s_i, eq_i = negatives with s_j == s_i, ge_i = positives with s_j >= s_i; scores
+ * compare as exact fp32 values.  counts [cols, 4] = n_pos, n_neg, sum_i lt_i, sum_i eq_i;
+ * ap_sum [cols] = sum_i ge_i / (ge_i + n_neg - lt_i) in float64.  Then
+ *     auc_t = (sum lt + 0.5 sum eq) / (n_pos n_neg),    ap_t = ap_sum / n_pos
+ * restate sklearn.metrics.roc_auc_score and average_precision_score, ties included.  *flag = CWN_METRIC_FLAG_* bits over
+ * all columns (0: clean).  n <= INT32_MAX, cols <= 65535 (CWN_ERR_TOO_LARGE).  Cost n_pos * n per column. */
+size_t cwn_metric_rank_workspace_bytes(int64_t n, int64_t cols);
+int cwn_metric_rank_f32(const float* pred, const float* y, int64_t n, int64_t cols, void* workspace, size_t workspace_bytes,
+                        int64_t* counts, double* ap_sum, int32_t* flag, cwn_stream_t stream);
+
+/* sum [cols] = sum over the labeled rows of |pred - y| with both operands promoted to float64 first, count [cols] = the
+ * labeled rows (y not NaN) of the column: MAE = sum / count. */
+size_t cwn_metric_abs_err_workspace_bytes(int64_t n, int64_t cols);
+int cwn_metric_abs_err_f32(const float* pred, const float* y, int64_t n, int64_t cols, void* workspace, size_t workspace_bytes,
+                           double* sum, int64_t* count, cwn_stream_t stream);
+
+/* *hits = the rows of pred [n, C] whose FIRST maximal column equals y[row] (int64): numpy's argmax, a NaN counting as
+ * maximal. */
+size_t cwn_metric_argmax_hits_workspace_bytes(int64_t n);
+int cwn_metric_argmax_hits_f32(const float* pred, const int64_t* y, int64_t n, int64_t C, void* workspace, size_t workspace_bytes,
+                               int64_t* hits, cwn_stream_t stream);
+
+/* *count = the pairs i < j of the rows of x [n, d] (float64) with sqrt(sum_c (x_ic - x_jc)^2) < eps: the failures
+ * Evaluator._isomorphism counts through torch.pdist at p = 2.  n <= 65535 * CWN_METRIC_PDIST_TILE. */
+size_t cwn_metric_pdist_below_workspace_bytes(int64_t n);
+int cwn_metric_pdist_below_f64(const double* x, int64_t n, int64_t d, double eps, void* workspace, size_t workspace_bytes,
+                               int64_t* count, cwn_stream_t stream);
+
+/* The criterion of every batch of an epoch in ONE launch, value only: out[b] = mean over the labeled entries of rows
+ * ptr[b] .. ptr[b + 1] (device int64 [n_batches + 1], clamped to [0, n_rows]) of pred [n_rows, cols].  kind, y and the NaN /
+ * ignore conventions are those of the training loss above (CWN_LOSS_CE: y = one int64 class per row); a batch without a
+ * labeled entry gives NaN, as torch's criteria do on an empty selection.  One workgroup per batch. */
+int cwn_loss_segments_f32(int32_t kind, const float* pred, const float* y, const int64_t* ptr, int64_t n_batches, int64_t n_rows,
+                          int64_t cols, float* out, cwn_stream_t stream);
+
 /* The start of a training step in ONE launch (optimizer.zero_grad() of exp/train_utils.py:61 + what the step's own kernels
  * need zero on entry + the optimizer's step counter): a[0 .. a_bytes) = 0 (the flat gradient buffer), b[0 .. b_bytes) = 0 (the
  * step arena of cwn_amd/ops.py: slot sums of the live BatchNorms), and *step += 1 -- only when active == NULL or *active > 0
