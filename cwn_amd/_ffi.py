@@ -23,6 +23,7 @@ EXPORTS = ('cwn_abi_version', 'cwn_error_string', 'cwn_target_arch', 'cwn_csr_wo
            'cwn_csr_build', 'cwn_csr_long_rows', 'cwn_gather_rows_f32', 'cwn_aggregate_f32', 'cwn_gather_rows_f64', 'cwn_aggregate_f64', 'cwn_gemm_f32', 'cwn_gemm_would_split', 'cwn_gemm_packed_weight_bytes', 'cwn_gemm_pack_weights_f32', 'cwn_update_mlp_f32', 'cwn_update_mlp3_f32', 'cwn_update_mlp_max_rows', 'cwn_update_mlp_packed_weight_bytes', 'cwn_update_mlp_pack_weights_f32', 'cwn_update_mlp_pack_weights_many_f32', 'cwn_update_mlp_pack_weights_t_many_f32', 'cwn_update_mlp_pack_weights_both_many_f32', 'cwn_layer_pack_weights_both_many_f32', 'cwn_dense_stage_f32', 'cwn_dense_stage_ex_f32', 'cwn_dense_stage_bwd_f32', 'cwn_layer_fused_f32', 'cwn_layer_fused_lds_bytes', 'cwn_layer_variant_lds_bytes', 'cwn_layer_round_rows', 'cwn_layer_variant_round_rows', 'cwn_layer_items_check', 'cwn_layer_items_build', 'cwn_layer_pack_weights_f32', 'cwn_layer_pack_weights_many_f32', 'cwn_layer_pack_weights_t_many_f32', 'cwn_layer_bwd_f32', 'cwn_layer_bwd_lds_bytes', 'cwn_layer_bwd_items_build', 'cwn_layer_bwd_own_f32', 'cwn_layer_packed_weight_bytes', 'cwn_collate', 'cwn_collate_slots', 'cwn_collate_tables', 'cwn_collate_tables_len', 'cwn_collate_guard', 'cwn_layer_items_build_dev', 'cwn_layer_bwd_items_build_dev',
            'cwn_bn_finalize_f32', 'cwn_step_begin', 'cwn_axpy_eps_f32', 'cwn_dropout_f32', 'cwn_embed_front_bwd_f32', 'cwn_norm_act_f32', 'cwn_norm_bwd_reduce_f32', 'cwn_norm_bwd_apply_f32', 'cwn_norm_bwd_f32',
            'cwn_layernorm_act_f32', 'cwn_layernorm_bwd_workspace_bytes', 'cwn_layernorm_bwd_f32',
+           'cwn_oriented_layer_f32', 'cwn_oriented_dz_f32',
            'cwn_gemm_tn_f32', 'cwn_gemm_tn_workspace_bytes', 'cwn_adam_f32', 'cwn_adam_dev_f32', 'cwn_loss_f32', 'cwn_loss_cols_f32', 'cwn_embedding_fwd_f32', 'cwn_embedding_bwd_f32', 'cwn_embed_front_f32', 'cwn_head_f32', 'cwn_head_bwd_f32', 'cwn_head_pool_floats', 'cwn_lift_create', 'cwn_lift_size', 'cwn_lift_copy', 'cwn_lift_destroy',
            'cwn_lift_many', 'cwn_lift_many_count', 'cwn_lift_many_lengths', 'cwn_lift_many_copy', 'cwn_lift_many_destroy',
            # the evaluation pass (csrc/cwn_metrics.hip)
@@ -284,6 +285,24 @@ class LnDesc(C.Structure):
                 ('eps', C.c_float), ('accumulate', C.c_int32), ('m_dev', C.c_void_p)]
 
 
+ACT_ID, ACT_RELU, ACT_ELU, ACT_TANH, ACT_SIGMOID = range(5)      # = CWN_ACT_*
+ORIENTED_MAX_WIDTH = 128       # widest x / out row of cwn_oriented_layer_f32
+
+
+def oriented_tm(w: int) -> int:
+    """= CWN_ORIENTED_TM(w): destination rows per workgroup of cwn_oriented_layer_f32."""
+    return 128 if w <= 16 else 32
+
+
+class OrientedDesc(C.Structure):
+    """cwn_oriented_desc (include/cwn_hip.h): one OrientedConv layer, or its data gradient (w_trans)."""
+    _fields_ = [('x', C.c_void_p), ('up_rowptr', C.c_void_p), ('up_col', C.c_void_p), ('up_perm', C.c_void_p),
+                ('up_orient', C.c_void_p), ('w_up', C.c_void_p), ('dn_rowptr', C.c_void_p), ('dn_col', C.c_void_p),
+                ('dn_perm', C.c_void_p), ('dn_orient', C.c_void_p), ('w_dn', C.c_void_p), ('w_self', C.c_void_p),
+                ('out', C.c_void_p), ('agg_out', C.c_void_p), ('n', C.c_int64), ('ldx', C.c_int64), ('ldout', C.c_int64),
+                ('w', C.c_int32), ('H', C.c_int32), ('act', C.c_int32), ('w_trans', C.c_int32), ('m_dev', C.c_void_p)]
+
+
 class GemmTnDesc(C.Structure):
     _fields_ = [('dZ', C.c_void_p), ('X', C.c_void_p), ('X2', C.c_void_p), ('in_scale', C.c_void_p),
                 ('in_shift', C.c_void_p), ('in_scale2', C.c_void_p), ('in_shift2', C.c_void_p),
@@ -432,6 +451,11 @@ def lib():
     L.cwn_layernorm_bwd_workspace_bytes.argtypes = [C.POINTER(LnDesc), C.c_int]
     L.cwn_layernorm_bwd_f32.restype = C.c_int
     L.cwn_layernorm_bwd_f32.argtypes = [C.POINTER(LnDesc), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.cwn_oriented_layer_f32.restype = C.c_int
+    L.cwn_oriented_layer_f32.argtypes = [C.POINTER(OrientedDesc), C.c_void_p]
+    L.cwn_oriented_dz_f32.restype = C.c_int
+    L.cwn_oriented_dz_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
+                                      C.c_int32, C.c_void_p, C.c_void_p]
     L.cwn_gemm_tn_f32.restype = C.c_int
     L.cwn_gemm_tn_f32.argtypes = [C.POINTER(GemmTnDesc), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
     L.cwn_gemm_tn_workspace_bytes.restype = C.c_size_t
@@ -683,6 +707,22 @@ def layer_norm_bwd(descs: Sequence['LnDesc'], device) -> None:
         ws = torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes else None
         check(L.cwn_layernorm_bwd_f32(arr, len(chunk), None if ws is None else ws.data_ptr(), nbytes, s),
               'cwn_layernorm_bwd_f32')
+
+
+def oriented_layer(desc: 'OrientedDesc', device) -> None:
+    """One OrientedConv layer (or its data gradient) in one launch; m_dev from `dynamic_rows` by the row count."""
+    if DYN_ROWS:
+        desc.m_dev = DYN_ROWS.get(int(desc.n))
+    check(lib().cwn_oriented_layer_f32(C.byref(desc), stream_ptr(device)), 'cwn_oriented_layer_f32')
+
+
+def oriented_dz(dout: torch.Tensor, out: torch.Tensor, act: int) -> torch.Tensor:
+    """dz = dout * act'(out) over [n, H] row-major matrices (rows past a `dynamic_rows` count stay unwritten)."""
+    n, H = out.shape
+    dz = torch.empty(n, H, dtype=torch.float32, device=out.device)
+    check(lib().cwn_oriented_dz_f32(dout.data_ptr(), out.data_ptr(), dz.data_ptr(), n, H, dout.stride(0), out.stride(0), H, int(act),
+                                    dyn(n), stream_ptr(out.device)), 'cwn_oriented_dz_f32')
+    return dz
 
 
 # False: the row bands of a weight gradient are added with fp32 atomics (fastest: 1.48 ms ZINC training

@@ -1651,9 +1651,31 @@ class CINppConv(SparseCINConv):
 # ------------------------------------------------------------------------------------------------
 # OrientedConv, InitReduceConv, embedding front-ends
 # ------------------------------------------------------------------------------------------------
+FUSED_ORIENTED = os.environ.get('CWN_FUSED_ORIENTED') != '0'    # False: OrientedConv as one aggregation launch + torch Linear / add / activation
+
+
+def identity(x):
+    """The 'id' nonlinearity (mp/nn.py:16-17) as ONE function object, so that a layer can recognise it."""
+    return x
+
+
+# what models.get_nonlinearity(name, return_module=False) returns -> the activation of cwn_oriented_layer_f32
+ACT_FUNCTIONS = ((identity, 'id'), (torch.nn.functional.relu, 'relu'), (torch.nn.functional.elu, 'elu'), (torch.tanh, 'tanh'),
+                 (torch.sigmoid, 'sigmoid'))
+
+
+class ZeroUpdate(torch.nn.Module):
+    """An update map that discards its input: the recognisable, parameter-free form of the reference's
+    `update_up = lambda x: 0` (EdgeMPNN, mp/models.py:569-570)."""
+
+    def forward(self, x):
+        return 0
+
+
 class OrientedConv(CochainMessagePassing):
-    """mp/layers.py:430-470: messages x_j * orientation (a +-1 scalar per adjacency entry).
-    Fused as CWN_MSG_A_TIMES_B with a width-1 per-entry attribute."""
+    """mp/layers.py:430-470: messages x_j * orientation (a +-1 scalar per adjacency entry).  With bias-free Linear update
+    maps (EdgeOrient, EdgeMPNN) the whole layer is one launch, ops.oriented_layer; otherwise the two aggregations are one
+    CWN_MSG_A_TIMES_B launch with a width-1 per-entry attribute and the maps run as the modules they are."""
 
     def __init__(self, dim: int, up_msg_size: int, down_msg_size: int,
                  update_up_nn: Optional[Callable], update_down_nn: Optional[Callable],
@@ -1676,24 +1698,62 @@ class OrientedConv(CochainMessagePassing):
         """(out_up, out_down) of mp/layers.py:441-446 in ONE aggregation launch (one autograd node in training) instead of
         one per adjacency; None when a subclass has replaced the hooks (forward then runs propagate())."""
         x = cochain.x
-        if (not isinstance(x, Tensor) or not x.is_cuda or type(self).message_up is not OrientedConv.message_up
-                or type(self).message_down is not OrientedConv.message_down
-                or type(self).message_and_aggregate_up is not OrientedConv.message_and_aggregate_up
-                or type(self).message_and_aggregate_down is not OrientedConv.message_and_aggregate_down
-                or self._overrides['aggregate_up'] or self._overrides['aggregate_down'] or self._overrides['update']):
+        if not isinstance(x, Tensor) or not x.is_cuda or not self._own_hooks():
             return None
         up_attr, down_attr = cochain.upper_orient.view(-1, 1), cochain.lower_orient.view(-1, 1)
-        kw = dict(x=x, up_attr=up_attr, down_attr=down_attr)
+        up_adj, down_adj = self._plans(cochain, up_attr, down_attr)
+        sts = [self._stream(up_adj, x, up_attr, self.aggr_up), self._stream(down_adj, x, down_attr, self.aggr_down)]
+        return ops.aggregate_many(sts)
+
+    def _own_hooks(self) -> bool:
+        """Are the message / aggregate / update hooks the class's own (a subclass may have replaced any of them)?"""
+        return not (type(self).message_up is not OrientedConv.message_up
+                    or type(self).message_down is not OrientedConv.message_down
+                    or type(self).message_and_aggregate_up is not OrientedConv.message_and_aggregate_up
+                    or type(self).message_and_aggregate_down is not OrientedConv.message_and_aggregate_down
+                    or self._overrides['aggregate_up'] or self._overrides['aggregate_down'] or self._overrides['update'])
+
+    def _plans(self, cochain, up_attr, down_attr):
+        """The cached plans of the upper and the lower adjacency (the checks of propagate(), mp/cell_mp.py:146-193)."""
+        kw = dict(x=cochain.x, up_attr=up_attr, down_attr=down_attr)
         up_size = self.__check_input_separately__(cochain.upper_index, None)
         down_size = self.__check_input_separately__(cochain.lower_index, None)
         self.__check_input_together__(cochain.upper_index, cochain.lower_index, up_size, down_size)
-        sts = [self._stream(self._adjacency(cochain.upper_index, 'up', up_size, kw), x, up_attr, self.aggr_up),
-               self._stream(self._adjacency(cochain.lower_index, 'down', down_size, kw), x, down_attr, self.aggr_down)]
-        return ops.aggregate_many(sts)
+        return (self._adjacency(cochain.upper_index, 'up', up_size, kw),
+                self._adjacency(cochain.lower_index, 'down', down_size, kw))
+
+    def fused_operands(self, x):
+        """(w_self, w_up, w_down, activation name) when the whole layer is ONE cwn_oriented_layer_f32 launch, else None: x
+        float32 on the GPU, the class's own hooks, 'add' reduces, every update map a bias-free torch.nn.Linear of matching
+        widths (<= 128) or a ZeroUpdate, the activation one of the five of models.get_nonlinearity.  A Linear with a
+        bias, a user callable, float64, CPU tensors, another reduce: the path below, unchanged."""
+        if (not FUSED_ORIENTED or not isinstance(x, Tensor) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2
+                or not self._own_hooks() or (self.aggr_up or 'add') != 'add' or (self.aggr_down or 'add') != 'add'):
+            return None
+        act = next((name for fn, name in ACT_FUNCTIONS if self.act_fn is fn), None)
+        if act is None:
+            return None
+        ws = []
+        for nn in (self.update_nn, self.update_up_nn, self.update_down_nn):
+            if type(nn) is ZeroUpdate:
+                ws.append(None)
+            elif type(nn) is torch.nn.Linear and nn.bias is None:
+                ws.append(nn.weight)
+            else:
+                return None
+        if not ops.oriented_layer_applies(x, ws):
+            return None
+        return ws[0], ws[1], ws[2], act
 
     def forward(self, cochain):
         assert len(cochain.upper_orient) == cochain.upper_index.size(1)
         assert len(cochain.lower_orient) == cochain.lower_index.size(1)
+        fused = self.fused_operands(cochain.x)
+        if fused is not None:
+            w_self, w_up, w_down, act = fused
+            up_adj, down_adj = self._plans(cochain, cochain.upper_orient.view(-1, 1), cochain.lower_orient.view(-1, 1))
+            return ops.oriented_layer(cochain.x, up_adj, cochain.upper_orient if self.orient else None,
+                                      down_adj, cochain.lower_orient if self.orient else None, w_self, w_up, w_down, act)
         both = self.propagate_both(cochain)
         if both is not None:
             out_up, out_down = both

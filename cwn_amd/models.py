@@ -40,7 +40,7 @@ def _one_check(forward):
 def get_nonlinearity(nonlinearity, return_module=True):
     """mp/nn.py:7-28."""
     table = {'relu': (torch.nn.ReLU, F.relu), 'elu': (torch.nn.ELU, F.elu),
-             'id': (torch.nn.Identity, lambda x: x), 'sigmoid': (torch.nn.Sigmoid, torch.sigmoid),
+             'id': (torch.nn.Identity, layers.identity), 'sigmoid': (torch.nn.Sigmoid, torch.sigmoid),
              'tanh': (torch.nn.Tanh, torch.tanh)}
     if nonlinearity not in table:
         raise NotImplementedError(f'Nonlinearity {nonlinearity} is not currently supported.')
@@ -658,6 +658,61 @@ class EdgeOrient(torch.nn.Module):
             w = num_input_features if i == 0 else hidden
             self.convs.append(layers.OrientedConv(
                 dim=1, up_msg_size=w, down_msg_size=w, update_up_nn=Linear(w, hidden, bias=False),
+                update_down_nn=Linear(w, hidden, bias=False), update_nn=Linear(w, hidden, bias=False),
+                act_fn=get_nonlinearity(nonlinearity, return_module=False), orient=not fully_invar))
+        self.lin1 = Linear(hidden, hidden)
+        self.lin2 = Linear(hidden, num_classes)
+
+    def reset_parameters(self):
+        for conv in self.convs:
+            conv.reset_parameters()
+        self.lin1.reset_parameters()
+        self.lin2.reset_parameters()
+
+    @_one_check
+    def forward(self, data, include_partial=False):
+        if self.fully_invar:
+            data.x = torch.abs(data.x)
+        x = data.x
+        for conv in self.convs:
+            x = conv(data)
+            data.x = x
+        cell_pred = x
+        if not self.fully_invar:
+            x = torch.abs(x)
+        n = getattr(data, 'num_cochains', None)
+        if n is None:
+            n = int(data.batch.max()) + 1
+        x = global_pool(x, data.batch, int(n), mean=self.readout == 'mean')
+        x = torch.relu(self.lin1(x))
+        x = ops.dropout(x, self.dropout_rate, self.training)
+        x = self.lin2(x)
+        return (x, cell_pred) if include_partial else x
+
+    def __repr__(self):
+        return self.__class__.__name__
+
+
+class EdgeMPNN(torch.nn.Module):
+    """mp/models.py:549-615: an MPNN on the line graph -- EdgeOrient's stack without the upper adjacency.  Every layer is
+    an OrientedConv whose upper map discards its input (the reference passes `lambda x: 0`; here layers.ZeroUpdate, which
+    holds no parameters: the state_dict has `convs.{i}.update_down_nn.weight`, `convs.{i}.update_nn.weight`, `lin1.*`,
+    `lin2.*` and no `update_up_nn` entries, as the reference's).  `fully_invar=True` by default: |x| in front, no
+    orientation signs in the messages."""
+
+    def __init__(self, num_input_features, num_classes, num_layers, hidden, dropout_rate: float = 0.0, jump_mode=None,
+                 nonlinearity='relu', readout='sum', fully_invar=True):
+        super().__init__()
+        self.max_dim = 1
+        self.fully_invar, self.dropout_rate, self.jump_mode = fully_invar, dropout_rate, jump_mode
+        self.nonlinearity, self.readout = nonlinearity, readout
+        if readout not in ('sum', 'mean'):
+            raise NotImplementedError(f'Readout {readout} is not currently supported.')
+        self.convs = torch.nn.ModuleList()
+        for i in range(num_layers):
+            w = num_input_features if i == 0 else hidden
+            self.convs.append(layers.OrientedConv(
+                dim=1, up_msg_size=w, down_msg_size=w, update_up_nn=layers.ZeroUpdate(),
                 update_down_nn=Linear(w, hidden, bias=False), update_nn=Linear(w, hidden, bias=False),
                 act_fn=get_nonlinearity(nonlinearity, return_module=False), orient=not fully_invar))
         self.lin1 = Linear(hidden, hidden)

@@ -1851,6 +1851,143 @@ def layer_norm_act_many(zs: Sequence[Tensor], norms: Sequence[torch.nn.LayerNorm
 
 
 # ------------------------------------------------------------------------------------------------
+# OrientedConv as one launch (csrc/cwn_oriented.hip)
+# ------------------------------------------------------------------------------------------------
+ACTS = {'id': _ffi.ACT_ID, 'relu': _ffi.ACT_RELU, 'elu': _ffi.ACT_ELU, 'tanh': _ffi.ACT_TANH, 'sigmoid': _ffi.ACT_SIGMOID}
+
+
+def _oriented_launch(x: Tensor, up, dn, w_self, w_up, w_dn, act: int, H: int, agg_out: Optional[Tensor] = None,
+                     trans: bool = False) -> Tensor:
+    """One cwn_oriented_layer_f32 call.  `up` / `dn`: (built plan, orient [E] float32 or None), or None for an absent
+    stream (its weight is then not passed either)."""
+    n, w = x.shape
+    out = torch.empty(n, H, dtype=torch.float32, device=x.device)
+    if n == 0:
+        return out
+    d = _ffi.OrientedDesc(x=x.data_ptr(), w_self=_ffi.ptr(w_self), out=out.data_ptr(), agg_out=_ffi.ptr(agg_out), n=n,
+                          ldx=x.stride(0), ldout=H, w=w, H=H, act=int(act), w_trans=int(bool(trans)))
+    if up is not None:
+        d.up_rowptr, d.up_col, d.up_perm = up[0].rowptr.data_ptr(), up[0].col.data_ptr(), up[0].perm.data_ptr()
+        d.up_orient, d.w_up = _ffi.ptr(up[1]), w_up.data_ptr()
+    if dn is not None:
+        d.dn_rowptr, d.dn_col, d.dn_perm = dn[0].rowptr.data_ptr(), dn[0].col.data_ptr(), dn[0].perm.data_ptr()
+        d.dn_orient, d.w_dn = _ffi.ptr(dn[1]), w_dn.data_ptr()
+    _ffi.oriented_layer(d, x.device)
+    return out
+
+
+class _OrientedLayer(torch.autograd.Function):
+    """out = act(x W^T + (A_up o x) W_up^T + (A_dn o x) W_dn^T): one launch forward; backward dZ = g * act'(out) (one launch,
+    none for 'id'), dx through the same kernel over the transposed plans (one launch, skipped when x needs no gradient) and
+    the weight gradients as ONE cwn_gemm_tn_f32 call over dZ against x and the two halves of the stored aggregates."""
+
+    @staticmethod
+    def forward(ctx, x, w_self, w_up, w_dn, up, dn, act, H):
+        need = ctx.needs_input_grad
+        n, w = x.shape
+        agg = None
+        if (need[2] and up is not None) or (need[3] and dn is not None):
+            agg = torch.empty(n, 2 * w, dtype=torch.float32, device=x.device)
+        out = _oriented_launch(x, up, dn, w_self, w_up if up is not None else None, w_dn if dn is not None else None, act, H,
+                               agg_out=agg)
+        ctx.up, ctx.dn, ctx.act = up, dn, act
+        ctx.save_for_backward(x, out, agg, w_self, w_up, w_dn)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, out, agg, w_self, w_up, w_dn = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        up, dn, act = ctx.up, ctx.dn, ctx.act
+        n, w = x.shape
+        H = out.size(1)
+        dev = x.device
+        g = g.contiguous()
+        dz = g if act == _ffi.ACT_ID or n == 0 else _ffi.oriented_dz(g, out, act)
+        dx = None
+        if need[0]:
+            t_up = None if up is None else (up[0].t_src, up[1])       # (perm of a transposed plan: the ORIGINAL entry)
+            t_dn = None if dn is None else (dn[0].t_src, dn[1])
+            wait_ready([t[0] for t in (t_up, t_dn) if t is not None])
+            dx = _oriented_launch(dz, t_up, t_dn, w_self, w_up if up is not None else None, w_dn if dn is not None else None,
+                                  _ffi.ACT_ID, w, trans=True)
+        grads, descs = [None, None, None], []
+        for k, (W, X, ldx) in enumerate(((w_self, x, x.stride(0)), (w_up, agg, 2 * w),
+                                         (w_dn, None if agg is None else agg[:, w:], 2 * w))):
+            if W is None or not need[1 + k]:
+                continue
+            dW = torch.zeros(H, w, dtype=torch.float32, device=dev)
+            grads[k] = dW
+            if n == 0 or (k == 1 and up is None) or (k == 2 and dn is None):
+                continue                                              # (an absent stream: its aggregate is zero)
+            descs.append(_ffi.GemmTnDesc(dZ=dz.data_ptr(), X=X.data_ptr(), X2=None, in_scale=None, in_shift=None, in_scale2=None,
+                                         in_shift2=None, dW=dW.data_ptr(), db=None, M=n, lddz=H, ldx=ldx, ldx2=0, lddw=w,
+                                         N=H, K=w, K2=0, in_relu=0))
+        if descs:
+            _ffi.gemm_tn(descs, dev, keep=[dz, x, agg, grads])
+        return (dx, grads[0], grads[1], grads[2], None, None, None, None)
+
+
+def oriented_layer_applies(x: Tensor, weights: Sequence[Optional[Tensor]]) -> bool:
+    """Does cwn_oriented_layer_f32 take these operands?  float32 on the GPU, rows of 1 .. 128 columns in and out."""
+    ws = [t for t in weights if t is not None]
+    if not ws or not (isinstance(x, Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2):
+        return False
+    H, w = ws[0].shape
+    return (1 <= w <= _ffi.ORIENTED_MAX_WIDTH and 1 <= H <= _ffi.ORIENTED_MAX_WIDTH and x.size(1) == w
+            and all(t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == (H, w) for t in ws))
+
+
+def oriented_layer(x: Tensor, up_adj: Optional[Adjacency], up_orient: Optional[Tensor], dn_adj: Optional[Adjacency],
+                   dn_orient: Optional[Tensor], w_self: Optional[Tensor], w_up: Optional[Tensor], w_dn: Optional[Tensor],
+                   act='id') -> Tensor:
+    """A whole OrientedConv layer (mp/layers.py:441-454 with bias-free Linear maps) in ONE launch:
+
+        out = act(x w_self^T + (A_up o_up x) w_up^T + (A_dn o_dn x) w_dn^T)
+
+    `up_adj` / `dn_adj` are destination-sorted plans over the rows of x (None or without entries: the stream is absent),
+    `up_orient` / `dn_orient` one multiplier per original entry (None: 1, OrientedConv(orient=False)), the weights
+    `[H, w]` as torch.nn.Linear holds them (None: the map is absent -- EdgeMPNN's upper map).  `act`: 'id', 'relu', 'elu',
+    'tanh', 'sigmoid'.  Differentiable w.r.t. x and the weights (the orientations get no gradient, as in the reference's
+    data); float32, widths up to 128 (`oriented_layer_applies`) -- anything else is an error, not a fallback."""
+    act = ACTS[act] if isinstance(act, str) else int(act)
+    x = _f32c(x, 'x')
+    w_self, w_up, w_dn = _f32c(w_self, 'w_self'), _f32c(w_up, 'w_up'), _f32c(w_dn, 'w_dn')
+    if not oriented_layer_applies(x, (w_self, w_up, w_dn)):
+        raise ValueError('oriented_layer takes float32 x [n, w] and weights [H, w] of one shape with 1 <= w, H <= '
+                         f'{_ffi.ORIENTED_MAX_WIDTH}, at least one of them given')
+    H = next(int(t.size(0)) for t in (w_self, w_up, w_dn) if t is not None)
+    n = x.size(0)
+    streams = []
+    for adj, orient, W in ((up_adj, up_orient, w_up), (dn_adj, dn_orient, w_dn)):
+        if adj is None or adj.n_entries == 0 or W is None:
+            streams.append(None)
+            continue
+        if adj.n_dst != n or adj.n_val != n:
+            raise ValueError(f'adjacency over {adj.n_val} -> {adj.n_dst} rows, x has {n}')
+        if orient is not None:
+            orient = _f32c(orient.detach().reshape(-1), 'orient')
+            if orient.numel() != adj.n_entries:
+                raise ValueError(f'one orientation per entry ({adj.n_entries}), got {orient.numel()}')
+        streams.append((adj, orient))
+    up, dn = streams
+    grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, w_self, w_up, w_dn))
+    from .csr import build_many
+    todo = [s[0] for s in streams if s is not None and not s[0].built]
+    if grad and x.requires_grad:
+        for s in streams:
+            if s is not None:
+                s[0].transposes()
+                todo += [a for a in (s[0]._t_src,) if a is not None and not a.built]
+    if todo:
+        build_many(todo)
+    wait_ready([s[0] for s in streams if s is not None])
+    if not grad:
+        return _oriented_launch(x, up, dn, w_self, w_up if up is not None else None, w_dn if dn is not None else None, act, H)
+    return _OrientedLayer.apply(x, w_self, w_up, w_dn, up, dn, act, H)
+
+
+# ------------------------------------------------------------------------------------------------
 # gemm_many + aggregate_many of one propagate step as ONE autograd node
 # ------------------------------------------------------------------------------------------------
 FUSED_PROPAGATE_NODE = os.environ.get('CWN_FUSED_PROPAGATE_NODE') != '0'     # A/B: '0' keeps the two nodes

@@ -422,3 +422,134 @@ def csl_graphs(num: int = 150, seed: int = 0, max_ring: int = 8) -> List[Complex
         out.append(ring_lift(n, edges, torch.zeros(n, 1), torch.zeros(len(edges), 1), max_k=max_ring,
                              y=torch.tensor([cls], dtype=torch.long)))
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# edge flows on a triangulated grid (the FLOW experiments of the reference)
+# ------------------------------------------------------------------------------------------------
+_HOLES = ((0.2, 0.2, 0.4, 0.4), (0.6, 0.6, 0.8, 0.8))          # (x0, y0, x1, y1), closed rectangles
+_START, _END = (0.0, 0.8, 0.2, 1.0), (0.8, 0.0, 1.0, 0.2)      # the two opposite corner regions of a path
+_CHECKPOINTS = ((0.0, 0.0, 0.2, 0.2), (0.8, 0.8, 1.0, 1.0))    # class 0 passes below the first hole, class 1 above the second
+
+
+def _in_rect(points: np.ndarray, rect) -> np.ndarray:
+    x0, y0, x1, y1 = rect
+    t = 1e-9
+    return (points[:, 0] >= x0 - t) & (points[:, 0] <= x1 + t) & (points[:, 1] >= y0 - t) & (points[:, 1] <= y1 + t)
+
+
+def adjacency_from_boundary(B: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """(index [2, P] int64, orient [P] float32) of the columns of B that meet: the off-diagonal entries of B^T B (each +-1 for
+    a simplicial complex).  Pair (i, j), j < i, is stored as the two consecutive entries i -> j, j -> i with ONE sign, pairs
+    in row-major order of (i, j) -- the layout of data/datasets/flow_utils.py:199-230."""
+    A = np.rint(B.T.astype(np.float32) @ B.astype(np.float32)).astype(np.int64)      # (small integers: exact in fp32)
+    ii, jj = np.nonzero(np.tril(A, -1))
+    v = A[ii, jj]
+    assert np.all(np.abs(v) == 1), 'columns that share more than one row: not a simplicial complex'
+    index = np.empty((2, 2 * ii.size), dtype=np.int64)
+    index[0, 0::2], index[1, 0::2] = ii, jj
+    index[0, 1::2], index[1, 1::2] = jj, ii
+    return index, np.repeat(v, 2).astype(np.float32)
+
+
+def edge_flow_mesh(side: int, holes: bool = True) -> dict:
+    """A `side` x `side` grid of points on the unit square, every grid cell cut into two triangles, without the triangles
+    whose centroid lies in one of the two rectangular holes (`holes`).  Returns the points [V, 2], the edges [E, 2] (u < v,
+    lexicographic), the triangles [T, 3] (sorted vertices), the boundary matrices B1 [V, E] and B2 [E, T] in the
+    orientation "from the smaller to the larger vertex" (B1 B2 = 0), and the lower / upper adjacency of the edges with
+    their relative orientations (`adjacency_from_boundary` of B1 and of B2^T)."""
+    if side < 2:
+        raise ValueError('edge_flow_mesh needs side >= 2')
+    g = np.arange(side) / (side - 1)
+    pts = np.stack(np.meshgrid(g, g, indexing='ij'), -1).reshape(-1, 2)
+    vid = lambda i, j: i * side + j
+    tris = []
+    for i in range(side - 1):
+        for j in range(side - 1):
+            a, b, c, d = vid(i, j), vid(i + 1, j), vid(i, j + 1), vid(i + 1, j + 1)
+            tris += [(a, b, d), (a, c, d)] if (i + j) % 2 == 0 else [(a, b, c), (b, c, d)]
+    tris = np.array(tris, dtype=np.int64)
+    if holes:                                                    # a triangle belongs to a hole when its centroid does
+        mid = pts[tris].mean(1)
+        tris = tris[~(_in_rect(mid, _HOLES[0]) | _in_rect(mid, _HOLES[1]))]
+    if len(tris) == 0:
+        raise ValueError(f'side={side}: the holes leave no triangle')
+    used = np.unique(tris)                                       # vertices that lost every triangle go too
+    renum = np.full(side * side, -1, dtype=np.int64)
+    renum[used] = np.arange(used.size)
+    pts, tris = pts[used], np.sort(renum[tris], 1)
+    edges = np.unique(np.concatenate([tris[:, [0, 1]], tris[:, [0, 2]], tris[:, [1, 2]]]), axis=0)
+    V, E, T = len(pts), len(edges), len(tris)
+    eid = {(int(u), int(v)): k for k, (u, v) in enumerate(edges)}
+    B1 = np.zeros((V, E), dtype=np.int8)
+    B1[edges[:, 0], np.arange(E)] = -1
+    B1[edges[:, 1], np.arange(E)] = 1
+    B2 = np.zeros((E, T), dtype=np.int8)
+    for t, (a, b, c) in enumerate(tris):                         # boundary of [a, b, c], a < b < c: [b, c] - [a, c] + [a, b]
+        B2[eid[(int(b), int(c))], t] = 1
+        B2[eid[(int(a), int(c))], t] = -1
+        B2[eid[(int(a), int(b))], t] = 1
+    lower_index, lower_orient = adjacency_from_boundary(B1)
+    upper_index, upper_orient = adjacency_from_boundary(B2.T)
+    nbrs = [[] for _ in range(V)]
+    for u, v in edges:
+        nbrs[int(u)].append(int(v))
+        nbrs[int(v)].append(int(u))
+    return dict(points=pts, edges=edges, triangles=tris, B1=B1, B2=B2, edge_id=eid, neighbours=nbrs,
+                lower_index=lower_index, lower_orient=lower_orient, upper_index=upper_index, upper_orient=upper_orient)
+
+
+def _flow_path(mesh: dict, cls: int, rng: np.random.Generator) -> List[int]:
+    """A vertex path from the start corner through the class's checkpoint region to the end corner: greedy towards the
+    current target over unvisited neighbours, one step in ten random (data/datasets/flow_utils.py:142-196, restated)."""
+    pts, nbrs = mesh['points'], mesh['neighbours']
+    pick = lambda rect: int(rng.choice(np.nonzero(_in_rect(pts, rect))[0]))
+    for _ in range(1000):
+        start, end, ckpt = pick(_START), pick(_END), pick(_CHECKPOINTS[cls])
+        path, seen, v, reached = [start], set(), start, False
+        while v != end:
+            seen.add(v)
+            reached = reached or v == ckpt
+            cand = [u for u in nbrs[v] if u not in seen]
+            if not cand:
+                break                                            # walked into a dead end: draw another path
+            if rng.random() < 0.1:
+                v = cand[int(rng.integers(len(cand)))]
+            else:
+                d = ((pts[cand] - pts[end if reached else ckpt]) ** 2).sum(1)
+                v = cand[int(np.argmin(d))]
+            path.append(v)
+        if v == end:
+            return path
+    raise RuntimeError('no path found: the mesh is too coarse for the corner regions')
+
+
+def edge_flows(n_complexes: int, side: int, seed: int, holes: bool = True, flip=None) -> List[Cochain]:
+    """`n_complexes` edge-flow cochains on one `edge_flow_mesh(side, holes)`: the FLOW task of the reference
+    (data/datasets/flow_utils.py:93-252) restated.  x [E, 1] is +-1 on the edges of a path from one corner region of the
+    square to the opposite one (the sign: along or against the edge's orientation) and 0 elsewhere; y says around which
+    of the two holes the path went (the first half of the list is class 0).  Every cochain gets its own random change of
+    edge orientations T = diag(t), t in {+-1}^E: B1 -> B1 T, B2 -> T B2, x -> T x, hence for the adjacencies
+    orient_ij -> t_i t_j orient_ij -- which is how it is applied here, once per cochain, to the mesh's adjacency.
+    `flip`: an explicit t ([E] of +-1) for every cochain instead (the draws of the paths do not depend on it).
+    Deterministic per (n_complexes, side, seed, holes)."""
+    mesh = edge_flow_mesh(side, holes)
+    E = len(mesh['edges'])
+    rng_path, rng_flip = np.random.default_rng([int(seed), 0]), np.random.default_rng([int(seed), 1])
+    lo, up = mesh['lower_index'], mesh['upper_index']
+    lower_index, upper_index = torch.from_numpy(lo), torch.from_numpy(up)
+    out = []
+    for k in range(n_complexes):
+        cls = 0 if k < n_complexes // 2 or n_complexes == 1 else 1
+        path = _flow_path(mesh, cls, rng_path)
+        x = np.zeros((E, 1), dtype=np.float32)
+        for a, b in zip(path[:-1], path[1:]):
+            x[mesh['edge_id'][(min(a, b), max(a, b))], 0] = 1.0 if a < b else -1.0
+        t = rng_flip.integers(0, 2, size=E) * 2 - 1 if flip is None else np.asarray(flip).reshape(E)
+        t = t.astype(np.float32)
+        out.append(Cochain(dim=1, x=torch.from_numpy(x * t[:, None]),
+                           lower_index=lower_index.clone(), upper_index=upper_index.clone(),
+                           lower_orient=torch.from_numpy(mesh['lower_orient'] * t[lo[0]] * t[lo[1]]),
+                           upper_orient=torch.from_numpy(mesh['upper_orient'] * t[up[0]] * t[up[1]]),
+                           y=torch.tensor([cls])))
+    return out

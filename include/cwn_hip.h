@@ -27,8 +27,8 @@
  *     worked this way (their sizes live in the item table).  cwn_collate_tables / cwn_layer_items_build_dev /
  *     cwn_layer_bwd_items_build_dev produce the per-batch tables on the device.
  *     Who checks "*m_dev <= capacity": cwn_gemm_f32 (both kernels), cwn_gemm_tn_f32, cwn_layernorm_*, cwn_dropout_f32,
- *     cwn_loss_f32 / cwn_loss_cols_f32, cwn_csr_long_rows, cwn_embedding_bwd_f32, cwn_embed_front_f32 and
- *     cwn_embed_front_bwd_f32 CLAMP the count to the capacity (a larger count behaves as the capacity); cwn_dense_stage_f32 /
+ *     cwn_loss_f32 / cwn_loss_cols_f32, cwn_csr_long_rows, cwn_embedding_bwd_f32, cwn_embed_front_f32,
+ *     cwn_embed_front_bwd_f32 and cwn_oriented_layer_f32 / cwn_oriented_dz_f32 CLAMP the count to the capacity (a larger count behaves as the capacity); cwn_dense_stage_f32 /
  *     _ex / _bwd, cwn_bn_finalize_f32, cwn_norm_*, cwn_update_mlp_f32 / cwn_update_mlp3_f32 and cwn_aggregate_f32 / _f64 take
  *     the count AS IT IS -- there the caller's vouching is what keeps the stores inside the buffers (the collate guard,
  *     cwn_collate_guard, zeroes the counts of a batch beyond its capacities before any of them is read).
@@ -1064,6 +1064,71 @@ typedef struct cwn_gemm_tn_desc {
 size_t cwn_gemm_tn_workspace_bytes(const cwn_gemm_tn_desc* descs_host, int n);
 int cwn_gemm_tn_f32(const cwn_gemm_tn_desc* descs_host, int n, void* workspace, size_t workspace_bytes,
                     cwn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * OrientedConv as one launch (csrc/cwn_oriented.hip).
+ *
+ * Replaces the whole of OrientedConv.forward, mp/layers.py:441-454 -- the two oriented aggregations, the three
+ * bias-free Linear maps, the two adds and the activation of an EdgeOrient / EdgeMPNN layer (mp/models.py:476-615):
+ *
+ *     out = act( x W^T + (A_up o_up x) W_up^T + (A_dn o_dn x) W_dn^T )
+ *
+ * with (A_s o_s x)[i, :] = sum over the entries p of row i of stream s, in CSR order, of orient_s[perm_s[p]] * x[col_s[p], :].
+ * A workgroup owns CWN_ORIENTED_TM(w) destination rows: it reduces their two streams into an LDS panel next to x and
+ * multiplies the panel with the stacked weights on v_mfma_f32_16x16x4_f32 (exact fp32), so the aggregates never reach
+ * memory.  A row's entries are added one after the other in CSR order, whatever its length, except where
+ * cwn_aggregate_f32 itself does otherwise without long-row lists (w <= 16 and more than 16 entries: interleaved partial
+ * sums and a fixed tree): `agg_out` is bit-identical to what that entry point gives for a contiguous x at the same
+ * address (CWN_MSG_A_TIMES_B, ib = perm).
+ *
+ *   - 1 <= w <= 128 and 1 <= H <= 128, any value.  n == 0: nothing is launched.
+ *   - a stream is its destination-sorted plan (rowptr, col, perm of cwn_csr_build), its `orient` -- one float per ORIGINAL
+ *     entry, read through perm; NULL: multiplier 1, OrientedConv(orient=False) -- and its weight.  rowptr == NULL and
+ *     weight == NULL together: the stream is absent (EdgeMPNN's upper map `lambda x: 0`; a batch without upper cells).
+ *   - weights are row-major [H, w] with row stride w, as torch.nn.Linear holds them.  w_trans != 0: they are [w, H] and
+ *     read transposed -- the data gradient of a layer whose forward weights they are:
+ *         dx = dZ W + (A_up^T o_up dZ) W_up + (A_dn^T o_dn dZ) W_dn
+ *     is this launch with x = dZ, the plans of the TRANSPOSED adjacencies (whose perm still indexes the original orient),
+ *     the forward's weight pointers, w and H exchanged, act = CWN_ACT_ID.
+ *   - agg_out, when given, receives the two reduced streams ([n, 2w]: up in columns [0, w), down in [w, 2w); an absent
+ *     stream's half is zeros) -- the operands of the weight gradients, one cwn_gemm_tn_f32 call over dZ.
+ *   - m_dev: see "Conventions"; the count is CLAMPED to n.  Rows in [*m_dev, n) are never written (out, agg_out), their
+ *     rowptr entries and their rows of x are never read.
+ * CWN_ERR_BAD_ARG: a width outside [1, 128], n < 0, an unknown act, a stream with a weight but no plan or a plan but no
+ * weight, a plan without col (or with orient but without perm), and for n > 0 a NULL x / out, ldx < w, ldout < H, out
+ * aliasing x or agg_out.  CWN_ERR_ALIGN: a pointer off 4 bytes (m_dev: 8).  All checks precede the first HIP call.
+ * ------------------------------------------------------------------------------------------ */
+enum { CWN_ACT_ID = 0, CWN_ACT_RELU = 1, CWN_ACT_ELU = 2 /* alpha = 1 */, CWN_ACT_TANH = 3, CWN_ACT_SIGMOID = 4 };   /* mp/nn.py:7-27 */
+#define CWN_ORIENTED_TM(w) ((w) <= 16 ? 128 : 32)   /* destination rows per workgroup */
+
+typedef struct cwn_oriented_desc {
+    const float* x;            /* [n, w] row stride ldx */
+    const int32_t* up_rowptr;  /* [n + 1], or NULL: no upper stream */
+    const int32_t* up_col;     /* [E_up] source row per CSR position */
+    const int32_t* up_perm;    /* [E_up] original entry per CSR position (needed with up_orient) */
+    const float* up_orient;    /* [E_up] per ORIGINAL entry, or NULL (= 1) */
+    const float* w_up;         /* [H, w] (w_trans: [w, H]) */
+    const int32_t* dn_rowptr;  /* the lower stream, likewise */
+    const int32_t* dn_col;
+    const int32_t* dn_perm;
+    const float* dn_orient;
+    const float* w_dn;
+    const float* w_self;       /* [H, w] (w_trans: [w, H]), or NULL: no self map */
+    float* out;                /* [n, H] row stride ldout */
+    float* agg_out;            /* [n, 2w] contiguous, or NULL */
+    int64_t n, ldx, ldout;
+    int32_t w, H;
+    int32_t act;               /* CWN_ACT_* */
+    int32_t w_trans;
+    const int64_t* m_dev;      /* or NULL: rows that exist (n = capacity) */
+} cwn_oriented_desc;
+int cwn_oriented_layer_f32(const cwn_oriented_desc* desc_host, cwn_stream_t stream);
+
+/* dz[r, c] = dout[r, c] * act'(z[r, c]) for r < n (or *m_dev, clamped), c < H <= 128: act' of all five activations as a
+ * function of out = act(z) (relu: out > 0; elu: out > 0 ? 1 : out + 1; tanh: 1 - out^2; sigmoid: out (1 - out)).  The first
+ * step of the layer's backward; dz may alias dout.  Same error codes. */
+int cwn_oriented_dz_f32(const float* dout, const float* out, float* dz, int64_t n, int32_t H, int64_t lddout, int64_t ldout,
+                        int64_t lddz, int32_t act, const int64_t* m_dev, cwn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Device-side batching (collate): build the arrays of a ComplexBatch from a dataset that is
