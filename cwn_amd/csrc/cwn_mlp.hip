@@ -28,20 +28,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
-#include <mutex>
 #include "../../include/cwn_hip.h"
-#include "cwn_split.h"
-#include "cwn_mem.h"
+#include "cwn_tile.h"
 
 namespace {
 
-using cwn::frag_cd;
+constexpr int kThreads = cwn::kTileThreads;
 
-constexpr int kThreads = 512;
-
-// F = the width of every Linear (64 or 128).  A workgroup takes TM = 4096 / F rows (32 / 64): 8 waves x two 16 x 16 tiles
-// (RT = 2) cover its TM x F output -- wave w owns column tile w % (F / 16) and the row tiles 2 (w / (F / 16)), + 1.
-// Two schedules of the same arithmetic (bit-identical results):
+// The workgroup design -- tile shape, planes, weight streaming, barrier, epilogue -- is csrc/cwn_tile.h's.  F = the width of
+// every Linear (64 or 128); RT = 2.  Two schedules of the same arithmetic (bit-identical results):
 //   SEQ = false (rounds 2 - 4): the two branches ALTERNATE, the epilogue of a stage under the other branch's MFMAs; five
 //     plane buffers, 130 - 138 KB of LDS: the workgroup owns its CU.  The shortest chain per workgroup -- the form of a
 //     launch that is one round of workgroups (ZINC-128: 214 on 256 CUs).
@@ -51,26 +46,9 @@ constexpr int kThreads = 512;
 //     width 64 -- of which the pipe is busy for 29 %: in a launch of several rounds (REDDIT-like batches: 1142 workgroups;
 //     ZINC-2048: 3400) a second workgroup on the CU fills the rest.  (Half-SIZE workgroups, two per CU, were measured first:
 //     a half-size workgroup is the same chain of latencies, 15.5 k cycles against 16.1 k -- no gain.)
-template <int F, int RT, bool SEQ> struct Shape {
-    static constexpr int kRT = RT, kV = RT;
-    static constexpr int kTM = RT * 2048 / F;
-    static constexpr int kNCT = F / 16;
-    static constexpr int kKS = F / 32;
-    // bf16 elements per LDS row.  F + 8: 16 bytes of padding make the fragment reads (16 rows x 16 B per quarter wave)
-    // conflict-free.  Sequential schedule at width 64: three padded buffers of 64 rows are 2 KB beyond half a CU, so the
-    // rows are unpadded and the 16-byte chunks of a row XOR-swizzled with (row >> 1) & 7 instead (col(): rows r, r + 1 differ
-    // in bank half, the eight row pairs of a fragment read in chunk).
-    static constexpr bool kSwizzle = SEQ && F == 64;
-    static constexpr int kRowStride = kSwizzle ? F : F + 8;
-    static __device__ __forceinline__ int col(int row, int c) {
-        if constexpr (kSwizzle) return (((c >> 3) ^ ((row >> 1) & 7)) << 3) | (c & 7);
-        else return c;
-    }
-    static constexpr int kChunksPerTile = kKS * 3;    // packed weight: 1-KiB chunks per 16-column tile (k steps x planes)
-    static constexpr size_t kPlaneElems = (size_t)kTM * kRowStride;
-    static constexpr size_t kBufBytes = 3 * kPlaneElems * 2;   // three planes
-    static constexpr size_t kLdsBytes = (SEQ ? 3 : 5) * kBufBytes;   // alternating: x_up / h_b, x_b, h1_up, h1_b, h_up
-    static_assert(kTM * (F / 4) == kV * kThreads && (kTM / 16) * kNCT == 8 * kRT, "tile shape");
+//     (Swizzled rows at width 64: three padded buffers do not fit half a CU.)
+template <int F, int RT, bool SEQ> struct Shape : cwn::TileShape<F, RT, SEQ && F == 64> {
+    static constexpr size_t kLdsBytes = (SEQ ? 3 : 5) * Shape::kBufBytes;   // alternating: x_up / h_b, x_b, h1_up, h1_b, h_up
     static_assert(!SEQ || 2 * kLdsBytes <= 160 * 1024, "two workgroups per CU");
 };
 
@@ -112,9 +90,10 @@ template <int F, int RT, bool SEQ, bool NARROW>
 //  dispatcher, csrc/Makefile PRELOAD -- so the workgroup knows its dimension without a scalar load of the argument segment)
 __global__ __launch_bounds__(kThreads, SEQ ? 4 : 1) void update_mlp_kernel(int32_t n_pre, int32_t bs1_pre, int32_t bs2_pre, MlpBatch B) {
     using S = Shape<F, RT, SEQ>;
-    constexpr int TM = S::kTM, kRowStride = S::kRowStride, kChunksPerTile = S::kChunksPerTile, kKS = S::kKS;
-    constexpr int kRT = S::kRT, kV = S::kV;
-    constexpr size_t kPlaneElems = S::kPlaneElems, kBufBytes = S::kBufBytes;
+    using WT = cwn::WaveTile<S>;
+    using cwn::lds_barrier;
+    constexpr int TM = S::kTM, kRT = S::kRT, kV = S::kV;
+    constexpr size_t kBufBytes = S::kBufBytes;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     uint16_t* const bufA = reinterpret_cast<uint16_t*>(smem);                   // x_up, later h_b
     uint16_t* const bufC = reinterpret_cast<uint16_t*>(smem + kBufBytes);       // x_b
@@ -133,9 +112,10 @@ __global__ __launch_bounds__(kThreads, SEQ ? 4 : 1) void update_mlp_kernel(int32
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int ct = wave % S::kNCT, rt0 = (wave / S::kNCT) * kRT;
     const int l15 = lane & 15, kq = lane >> 4;
+    const WT W{ct, rt0, lane, l15, kq};
 
     // an input tile: TM rows x 32 float4, two per thread, row-contiguous; rows past M are clamped, not guarded
-    typedef float4 RowRegs[kV];
+    typedef typename WT::RowRegs RowRegs;
     RowRegs vU, vB;
     // (narrow input -- cwn_mlp_dim.in_width columns, the rest of the tile zero: the first weight is zero-padded to match)
     const int in_w = NARROW && D.in_width > 0 && D.in_width < F ? D.in_width : F;          // (uniform)
@@ -143,7 +123,7 @@ __global__ __launch_bounds__(kThreads, SEQ ? 4 : 1) void update_mlp_kernel(int32
 #pragma unroll
         for (int i = 0; i < kV; ++i) {
             const int idx = threadIdx.x + i * kThreads, r = idx / (F / 4), c4 = idx % (F / 4);
-            const int64_t row = row0 + r < D.M ? row0 + r : D.M - 1;
+            const int64_t row = cwn::clamped_row(row0, r, D.M);
             if (!NARROW || in_w == F) {
                 v[i] = reinterpret_cast<const float4*>(X + row * ld)[c4];
             } else {
@@ -153,111 +133,27 @@ __global__ __launch_bounds__(kThreads, SEQ ? 4 : 1) void update_mlp_kernel(int32
             }
         }
     };
-    auto stage_rows = [&](const RowRegs& v, uint16_t* buf) {   // split the tile ONCE per element into the three planes
-#pragma unroll
-        for (int i = 0; i < kV; ++i) {
-            const int idx = threadIdx.x + i * kThreads, r = idx / (F / 4), c4 = idx % (F / 4);
-            uint2 ph, pm, pl;
-            cwn::split4(v[i], ph, pm, pl);
-            uint16_t* dst = buf + (size_t)r * kRowStride + S::col(r, c4 * 4);
-            *reinterpret_cast<uint2*>(dst) = ph;
-            *reinterpret_cast<uint2*>(dst + kPlaneElems) = pm;
-            *reinterpret_cast<uint2*>(dst + 2 * kPlaneElems) = pl;
-        }
-    };
-    // workgroup barrier that orders LDS traffic only: __syncthreads() also waits for every outstanding GLOBAL
-    // load (s_waitcnt vmcnt(0)) -- here the next stage's weight, which is meant to keep streaming across the
-    // barrier (measured: 3.3 k cycles per stage spent in that wait)
-    auto lds_barrier = [&]() {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-    };
-    // the stationary operand of a stage: this wave's 16 output columns, [k step][plane]; two sets
-    typedef uint4 WeightRegs[kKS][3];
+    auto stage_rows = [&](const RowRegs& v, uint16_t* buf) { WT::stage_rows(v, buf); };
+    // two sets of weight registers: weight k is addressed by its index in D.w_packed
+    typedef typename WT::WeightRegs WeightRegs;
     WeightRegs wfA, wfB;
-    auto request_kstep = [&](WeightRegs& wf, int k, int ks) {
-        const unsigned char* wp = reinterpret_cast<const unsigned char*>(D.w_packed[k]) +
-                                  (size_t)ct * kChunksPerTile * 1024 + lane * 16;
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl) wf[ks][pl] = *reinterpret_cast<const uint4*>(wp + (ks * 3 + pl) * 1024);
-    };
-    auto request_weight = [&](WeightRegs& wf, int k) {
-#pragma unroll
-        for (int ks = 0; ks < kKS; ++ks) request_kstep(wf, k, ks);
-    };
-    typedef frag_cd AccRegs[kRT];
+    auto request_kstep = [&](WeightRegs& wf, int k, int ks) { WT::request_kstep(wf, D.w_packed[k], ks, ct, lane); };
+    auto request_weight = [&](WeightRegs& wf, int k) { W.request_weight(wf, D.w_packed[k]); };
+    typedef typename WT::AccRegs AccRegs;
     AccRegs accU, accB;                          // the two branches alternate (see the chain below)
     auto clear = [&](AccRegs& acc) {
 #pragma unroll
-        for (int rt = 0; rt < kRT; ++rt) acc[rt] = frag_cd{0.f, 0.f, 0.f, 0.f};
+        for (int rt = 0; rt < kRT; ++rt) acc[rt] = cwn::frag_cd{0.f, 0.f, 0.f, 0.f};
     };
-    // acc += buf x W^T (k steps in order, six terms each: cwn_split.h).  `next` >= 0: the k steps of weight
-    // `next` are requested into the OTHER register set one by one between this stage's MFMAs -- three 1-KiB
-    // loads a wave at a time, which the address unit takes without making the wave wait (requested twelve at
-    // once after the stage, the waves sat in the issue of their loads for 1.5 k cycles while the matrix pipe
-    // idled, and then multiplied while the address unit idled)
+    // acc += buf x W^T.  `next` >= 0: the k steps of weight `next` stream into the OTHER register set between this stage's MFMAs
     auto multiply = [&](AccRegs& acc, const uint16_t* buf, const WeightRegs& wf, WeightRegs& wnext, int next) {
-#pragma unroll
-        for (int ks = 0; ks < kKS; ++ks) {
-#pragma unroll
-            for (int rt = 0; rt < kRT; ++rt) {
-                const int row = (rt0 + rt) * 16 + l15;
-                const uint16_t* p = buf + (size_t)row * kRowStride + S::col(row, ks * 32 + kq * 8);
-                const uint4 xh = *reinterpret_cast<const uint4*>(p);
-                const uint4 xm = *reinterpret_cast<const uint4*>(p + kPlaneElems);
-                const uint4 xl = *reinterpret_cast<const uint4*>(p + 2 * kPlaneElems);
-                acc[rt] = cwn::mfma_split6(wf[ks][0], wf[ks][1], wf[ks][2], xh, xm, xl, acc[rt]);
-            }
-            if (next >= 0) request_kstep(wnext, next, ks);
-        }
+        W.multiply(acc, buf, wf, [&](int ks) { if (next >= 0) request_kstep(wnext, next, ks); });
     };
-    // the epilogue constants of a stage are requested BEFORE its MFMAs (and so before the next weight): loads
-    // return in order, a constant behind 96 KB of weight is a wait for the weight (measured: 4.4 k cycles a stage)
-    struct Consts { float4 b, sc, sh; bool affine; };
+    // epilogue of stage s (its constants requested BEFORE its MFMAs): into the planes of `buf`, or, buf == NULL, to y
+    typedef typename WT::Consts Consts;
     Consts cU, cB;
-    auto request_consts = [&](Consts& c, int s) {
-        const int n0 = ct * 16 + kq * 4;
-        c.b = make_float4(0.f, 0.f, 0.f, 0.f);
-        c.sc = make_float4(1.f, 1.f, 1.f, 1.f);
-        c.sh = c.b;
-        if (D.bias[s] != nullptr) c.b = *reinterpret_cast<const float4*>(D.bias[s] + n0);
-        c.affine = D.scale[s] != nullptr;
-        if (c.affine) {
-            c.sc = *reinterpret_cast<const float4*>(D.scale[s] + n0);
-            c.sh = *reinterpret_cast<const float4*>(D.shift[s] + n0);
-        }
-    };
-    // epilogue of stage s: + bias, folded BatchNorm, ReLU; then either into the planes of `buf` (the next
-    // stage's operand) or, for the last stage, to y.  D[i][j]: i = output column (lane >> 4) * 4 + reg,
-    // j = row (lane & 15): a lane holds 4 consecutive columns of one row.
-    auto finish = [&](const AccRegs& acc, const Consts& c, uint16_t* buf) {
-        const int n0 = ct * 16 + kq * 4;
-        const float4 b4 = c.b, sc = c.sc, sh = c.sh;
-        const bool affine = c.affine;
-#pragma unroll
-        for (int rt = 0; rt < kRT; ++rt) {
-            float y[4] = {acc[rt][0] + b4.x, acc[rt][1] + b4.y, acc[rt][2] + b4.z, acc[rt][3] + b4.w};
-            if (affine) {
-                y[0] = y[0] * sc.x + sh.x;
-                y[1] = y[1] * sc.y + sh.y;
-                y[2] = y[2] * sc.z + sh.z;
-                y[3] = y[3] * sc.w + sh.w;
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) y[q] = fmaxf(y[q], 0.0f);
-            const int r = (rt0 + rt) * 16 + l15;
-            if (buf != nullptr) {
-                uint2 ph, pm, pl;
-                cwn::split4(make_float4(y[0], y[1], y[2], y[3]), ph, pm, pl);
-                uint16_t* dst = buf + (size_t)r * kRowStride + S::col(r, n0);
-                *reinterpret_cast<uint2*>(dst) = ph;
-                *reinterpret_cast<uint2*>(dst + kPlaneElems) = pm;
-                *reinterpret_cast<uint2*>(dst + 2 * kPlaneElems) = pl;
-            } else if (row0 + r < Mv) {
-                cwn::store_result4(D.y + (row0 + r) * D.ldy + n0, y[0], y[1], y[2], y[3]);
-            }
-        }
-    };
+    auto request_consts = [&](Consts& c, int s) { W.request_consts(c, D, s); };
+    auto finish = [&](const AccRegs& acc, const Consts& c, uint16_t* buf) { W.finish(acc, c, buf, D, row0, Mv); };
 
     // ---- the chain ----------------------------------------------------------------------------------------------
     // The two branches are independent until the combine, so their stages ALTERNATE: the epilogue of a stage
@@ -346,7 +242,7 @@ __global__ __launch_bounds__(kThreads, SEQ ? 4 : 1) void update_mlp_kernel(int32
     MLP_STAMP(8);
 }
 
-inline bool al16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+using cwn::al16;
 
 }  // namespace
 
@@ -382,19 +278,11 @@ __global__ __launch_bounds__(256) void pack_mlp_weights_kernel(const float* __re
 
 template <int F, int RT, bool SEQ, bool NARROW>
 int launch_mlp(MlpBatch& B, int64_t blocks, hipStream_t stream) {
-    static std::once_flag once;
-    static hipError_t attr_err = hipSuccess;
-    std::call_once(once, [] {
-        attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&update_mlp_kernel<F, RT, SEQ, NARROW>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)Shape<F, RT, SEQ>::kLdsBytes);
-    });
-    if (attr_err != hipSuccess) return CWN_ERR_LAUNCH;
 #ifdef CWN_MLP_TIMING
     B.stamps = g_mlp_stamps;
 #endif
-    update_mlp_kernel<F, RT, SEQ, NARROW><<<dim3((unsigned)blocks), dim3(kThreads), Shape<F, RT, SEQ>::kLdsBytes, stream>>>(
-        B.n, B.blk_start[1], B.blk_start[2], B);
-    return hipGetLastError() == hipSuccess ? CWN_OK : CWN_ERR_LAUNCH;
+    return cwn::launch_tile<&update_mlp_kernel<F, RT, SEQ, NARROW>>(Shape<F, RT, SEQ>::kLdsBytes, blocks, stream, B.n, B.blk_start[1],
+                                                                    B.blk_start[2], B);
 }
 
 // which schedule: CWN_MLP_FORM = 5 (alternating, five buffers) | 3 (sequential, three buffers, two per CU) | auto (default;

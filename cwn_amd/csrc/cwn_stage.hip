@@ -19,30 +19,21 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
-#include <mutex>
-#include "../../include/cwn_hip.h"
-#include "cwn_split.h"
-#include "cwn_mem.h"
+#include "cwn_tile.h"
 #include "cwn_bn_live.h"
 
 namespace {
 
 using cwn::frag_cd;
+using cwn::lds_barrier;
 
-constexpr int kThreads = 512;
+constexpr int kThreads = cwn::kTileThreads;
 constexpr int kV = 2;                             // float4 of an input tile per thread
 constexpr int kRT = 2;                            // 16-row tiles per wave
 
-template <int F> struct Shape {
-    static constexpr int kTM = 4096 / F;
-    static constexpr int kNCT = F / 16;
-    static constexpr int kKS = F / 32;
-    static constexpr int kRowStride = F + 8;          // bf16 elements per LDS row (fragment reads conflict-free)
-    static constexpr int kChunksPerTile = kKS * 3;    // packed weight: 1-KiB chunks per 16-column tile (k steps x planes)
-    static constexpr size_t kPlaneElems = (size_t)kTM * kRowStride;
-    static constexpr size_t kBufBytes = 3 * kPlaneElems * 2;   // three planes
-    static constexpr size_t kLdsBytes = 2 * kBufBytes;         // the tile of X and of X2
-    static_assert(kTM * (F / 4) == kV * kThreads && (kTM / 16) * kNCT == 8 * kRT, "tile shape");
+// the workgroup design of csrc/cwn_tile.h (read its header first), rows padded: two buffers need no swizzle
+template <int F> struct Shape : cwn::TileShape<F, kRT, false> {
+    static constexpr size_t kLdsBytes = 2 * Shape::kBufBytes;  // the tile of X and of X2
     static_assert(kThreads % (F / 4) == 0, "a thread keeps its input columns");
 };
 
@@ -76,8 +67,9 @@ __device__ __forceinline__ float row_ror_f32(float v) {
 template <int F, bool EX, typename BatchT>
 __device__ __forceinline__ void dense_stage_body(const BatchT& B) {
     using S = Shape<F>;
-    constexpr int TM = S::kTM, kRowStride = S::kRowStride, kChunksPerTile = S::kChunksPerTile, kKS = S::kKS;
-    constexpr size_t kPlaneElems = S::kPlaneElems, kBufBytes = S::kBufBytes;
+    using WT = cwn::WaveTile<S>;
+    constexpr int TM = S::kTM;
+    constexpr size_t kBufBytes = S::kBufBytes;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     // 2 KiB next to the tiles: the affines a live BatchNorm prologue derives ([input][scale | shift][F] floats) and, behind the
     // products, the workgroup's column statistics on their way to one coalesced atomic per column ([half][sum | sq][F] doubles)
@@ -97,6 +89,7 @@ __device__ __forceinline__ void dense_stage_body(const BatchT& B) {
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int ct = wave % S::kNCT, rt0 = (wave / S::kNCT) * kRT;
     const int l15 = lane & 15, kq = lane >> 4;
+    const WT W{ct, rt0, lane, l15, kq};
     const bool two = D.X2 != nullptr;
     // (EX) the third / fourth K-block: tiles requested with the others, staged into the SAME two LDS buffers once the first
     // two products have left them
@@ -108,24 +101,10 @@ __device__ __forceinline__ void dense_stage_body(const BatchT& B) {
         four = three && E[1].X != nullptr;
     }
 
-    // workgroup barrier that orders LDS traffic only (__syncthreads() also waits for every outstanding global load: here
-    // the tiles and the weight, which keep streaming across the barrier)
-    auto lds_barrier = [&]() {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-    };
-    // an input tile: TM rows x F / 4 float4, two per thread, row-contiguous; rows past M are clamped, not guarded (their
-    // outputs are neither stored nor counted)
-    typedef float4 RowRegs[kV];
+    // an input tile: two float4 per thread; rows past M are clamped, not guarded (their outputs are neither stored nor counted)
+    typedef typename WT::RowRegs RowRegs;
     RowRegs v0, v1;
-    auto request_rows = [&](RowRegs& v, const float* X, int64_t ld) {
-#pragma unroll
-        for (int i = 0; i < kV; ++i) {
-            const int idx = threadIdx.x + i * kThreads, r = idx / (F / 4), c4 = idx % (F / 4);
-            const int64_t row = row0 + r < D.M ? row0 + r : D.M - 1;
-            v[i] = reinterpret_cast<const float4*>(X + row * ld)[c4];
-        }
-    };
+    auto request_rows = [&](RowRegs& v, const float* X, int64_t ld) { WT::request_rows(v, X, ld, row0, D); };
     // the prologue of an input: per-column affine (the producing stage's BatchNorm) and ReLU.  A thread's columns are the
     // same for every row it stages (kThreads is a multiple of F / 4): its constants are loaded once.
     struct Pro { float4 sc, sh; bool affine, relu; };
@@ -153,39 +132,18 @@ __device__ __forceinline__ void dense_stage_body(const BatchT& B) {
             float4 x = v[i];
             if (p.affine) x = make_float4(x.x * p.sc.x + p.sh.x, x.y * p.sc.y + p.sh.y, x.z * p.sc.z + p.sh.z, x.w * p.sc.w + p.sh.w);
             if (p.relu) x = make_float4(fmaxf(x.x, 0.f), fmaxf(x.y, 0.f), fmaxf(x.z, 0.f), fmaxf(x.w, 0.f));
-            uint2 ph, pm, pl;
-            cwn::split4(x, ph, pm, pl);
-            uint16_t* dst = buf + (size_t)r * kRowStride + c4 * 4;
-            *reinterpret_cast<uint2*>(dst) = ph;
-            *reinterpret_cast<uint2*>(dst + kPlaneElems) = pm;
-            *reinterpret_cast<uint2*>(dst + 2 * kPlaneElems) = pl;
+            WT::store_planes(buf, r, c4 * 4, x);
         }
     };
-    // the stationary operand: this wave's 16 output columns of one F x F block, [k step][plane]; two sets
-    typedef uint4 WeightRegs[kKS][3];
+    // two sets of weight registers, each one F x F block
+    typedef typename WT::WeightRegs WeightRegs;
     WeightRegs wfA, wfB;
-    auto request_kstep = [&](WeightRegs& wf, const void* packed, int ks) {
-        const unsigned char* wp = reinterpret_cast<const unsigned char*>(packed) + (size_t)ct * kChunksPerTile * 1024 + lane * 16;
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl) wf[ks][pl] = *reinterpret_cast<const uint4*>(wp + (ks * 3 + pl) * 1024);
-    };
-    typedef frag_cd AccRegs[kRT];
-    AccRegs acc;
-    // acc += buf x W^T (k steps in order, six terms each: cwn_split.h).  `next` != NULL: the k steps of that block are
-    // requested into the OTHER register set one by one between this block's MFMAs.
+    auto request_kstep = [&](WeightRegs& wf, const void* packed, int ks) { WT::request_kstep(wf, packed, ks, ct, lane); };
+    typename WT::AccRegs acc;
+    // acc += buf x W^T.  `next` != NULL: the k steps of that block stream into the OTHER register set between this block's MFMAs
     auto multiply = [&](const uint16_t* buf, const WeightRegs& wf, WeightRegs& wnext, const void* next) {
-#pragma unroll
-        for (int ks = 0; ks < kKS; ++ks) {
-#pragma unroll
-            for (int rt = 0; rt < kRT; ++rt) {
-                const uint16_t* p = buf + (size_t)((rt0 + rt) * 16 + l15) * kRowStride + ks * 32 + kq * 8;
-                const uint4 xh = *reinterpret_cast<const uint4*>(p);
-                const uint4 xm = *reinterpret_cast<const uint4*>(p + kPlaneElems);
-                const uint4 xl = *reinterpret_cast<const uint4*>(p + 2 * kPlaneElems);
-                acc[rt] = cwn::mfma_split6(wf[ks][0], wf[ks][1], wf[ks][2], xh, xm, xl, acc[rt]);
-            }
-            if (next != nullptr) request_kstep(wnext, next, ks);
-        }
+        const bool more = next != nullptr;         // (tested once, here: inside the callable the assembly changes)
+        W.multiply(acc, buf, wf, [&](int ks) { if (more) request_kstep(wnext, next, ks); });
     };
 
     // requests: rows and the constants behind them first, then the weight (loads return in order: a constant behind 96 KB of
@@ -244,8 +202,7 @@ __device__ __forceinline__ void dense_stage_body(const BatchT& B) {
     const int n0 = ct * 16 + kq * 4;                 // D[i][j]: i = output column (lane >> 4) * 4 + reg, j = row (lane & 15)
     float4 b4 = make_float4(0.f, 0.f, 0.f, 0.f);
     if (D.bias != nullptr) b4 = *reinterpret_cast<const float4*>(D.bias + n0);
-#pragma unroll
-    for (int ks = 0; ks < kKS; ++ks) request_kstep(wfA, D.w_packed, ks);
+    W.request_weight(wfA, D.w_packed);
     stage_rows(v0, p0, buf0);
     if (two) stage_rows(v1, p1, buf1);
     lds_barrier();
@@ -351,8 +308,8 @@ struct StageBwdBatch {
 template <int F>
 __global__ __launch_bounds__(kThreads, 4) void dense_stage_bwd_kernel(StageBwdBatch B) {
     using S = Shape<F>;
-    constexpr int TM = S::kTM, kRowStride = S::kRowStride, kChunksPerTile = S::kChunksPerTile, kKS = S::kKS;
-    constexpr size_t kPlaneElems = S::kPlaneElems;
+    using WT = cwn::WaveTile<S>;
+    constexpr int TM = S::kTM;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     // 1 KiB next to the tile: the slot sums s1 | s2 a live consumer takes in its prologue, and the workgroup's column sums of
     // a live producer on their way to one coalesced atomic per column ([half][s1 | s2][F])
@@ -369,48 +326,20 @@ __global__ __launch_bounds__(kThreads, 4) void dense_stage_bwd_kernel(StageBwdBa
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int ct = wave % S::kNCT, rt0 = (wave / S::kNCT) * kRT;
     const int l15 = lane & 15, kq = lane >> 4;
+    const WT W{ct, rt0, lane, l15, kq};
     const bool two = D.wt2_packed != nullptr;
 
-    typedef float4 RowRegs[kV];
+    typedef typename WT::RowRegs RowRegs;
     RowRegs vy, vz;
-    auto request_rows = [&](RowRegs& v, const float* X, int64_t ld) {
-#pragma unroll
-        for (int i = 0; i < kV; ++i) {
-            const int idx = threadIdx.x + i * kThreads, r = idx / (F / 4), c4 = idx % (F / 4);
-            const int64_t row = row0 + r < D.M ? row0 + r : D.M - 1;
-            v[i] = reinterpret_cast<const float4*>(X + row * ld)[c4];
-        }
-    };
-    auto lds_barrier = [&]() {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-    };
+    auto request_rows = [&](RowRegs& v, const float* X, int64_t ld) { WT::request_rows(v, X, ld, row0, D); };
     // ONE set of weight registers; the second block of a two-output stage is requested when the first product is done (its
     // latency is covered by the CU's other workgroup).  Two sets, two accumulator sets and the fragments of both row tiles
     // were 164 registers -- one workgroup per CU where two overlap each other's loads -- and bounded to 128 the compiler
     // put 56 of them in scratch; requesting the second block k step by k step into the registers the first had just
     // finished with was allocated as a second set all the same (44 in scratch).
-    typedef uint4 WeightRegs[kKS][3];
-    WeightRegs wf;
-    auto request_kstep = [&](const void* packed, int ks) {
-        const unsigned char* wp = reinterpret_cast<const unsigned char*>(packed) + (size_t)ct * kChunksPerTile * 1024 + lane * 16;
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl) wf[ks][pl] = *reinterpret_cast<const uint4*>(wp + (ks * 3 + pl) * 1024);
-    };
-    typedef frag_cd AccRegs[kRT];
-    auto multiply = [&](AccRegs& acc) {
-#pragma unroll
-        for (int ks = 0; ks < kKS; ++ks) {
-#pragma unroll
-            for (int rt = 0; rt < kRT; ++rt) {
-                const uint16_t* p = buf0 + (size_t)((rt0 + rt) * 16 + l15) * kRowStride + ks * 32 + kq * 8;
-                const uint4 xh = *reinterpret_cast<const uint4*>(p);
-                const uint4 xm = *reinterpret_cast<const uint4*>(p + kPlaneElems);
-                const uint4 xl = *reinterpret_cast<const uint4*>(p + 2 * kPlaneElems);
-                acc[rt] = cwn::mfma_split6(wf[ks][0], wf[ks][1], wf[ks][2], xh, xm, xl, acc[rt]);
-            }
-        }
-    };
+    typename WT::WeightRegs wf;
+    typedef typename WT::AccRegs AccRegs;
+    auto multiply = [&](AccRegs& acc) { W.multiply(acc, buf0, wf, [](int) {}); };
 
     // requests: (a live consumer: the slot sums of its s1 | s2, thread t < 2 F one column, AHEAD of the tiles,) the two tiles,
     // the constants of this thread's four columns (the same in every row it stages), the weight
@@ -468,8 +397,7 @@ __global__ __launch_bounds__(kThreads, 4) void dense_stage_bwd_kernel(StageBwdBa
     // (a tile past the batch's own rows leaves here -- behind the hand-over of the sums above, which the FIRST workgroup of a
     // descriptor does whatever the batch holds)
     if (row0 >= Mv) return;
-#pragma unroll
-    for (int ks = 0; ks < kKS; ++ks) request_kstep(D.wt_packed, ks);
+    W.request_weight(wf, D.wt_packed);
     const bool relu = D.relu != 0;
 #pragma unroll
     for (int i = 0; i < kV; ++i) {
@@ -483,12 +411,7 @@ __global__ __launch_bounds__(kThreads, 4) void dense_stage_bwd_kernel(StageBwdBa
         const float4 d = make_float4(one(dy.x, z.x, sc.x, sh.x, mu.x, c0.x, c1.x), one(dy.y, z.y, sc.y, sh.y, mu.y, c0.y, c1.y),
                                      one(dy.z, z.z, sc.z, sh.z, mu.z, c0.z, c1.z), one(dy.w, z.w, sc.w, sh.w, mu.w, c0.w, c1.w));
         if (D.dz != nullptr && row0 + r < Mv) cwn::store_result4(D.dz + (row0 + r) * D.lddz + c4 * 4, d.x, d.y, d.z, d.w);
-        uint2 ph, pm, pl;
-        cwn::split4(d, ph, pm, pl);
-        uint16_t* dst = buf0 + (size_t)r * kRowStride + c4 * 4;
-        *reinterpret_cast<uint2*>(dst) = ph;
-        *reinterpret_cast<uint2*>(dst + kPlaneElems) = pm;
-        *reinterpret_cast<uint2*>(dst + 2 * kPlaneElems) = pl;
+        WT::store_planes(buf0, r, c4 * 4, d);
     }
     lds_barrier();
     const int n0 = ct * 16 + kq * 4;                 // D[i][j]: i = output column (lane >> 4) * 4 + reg, j = row (lane & 15)
@@ -565,8 +488,7 @@ __global__ __launch_bounds__(kThreads, 4) void dense_stage_bwd_kernel(StageBwdBa
     multiply(acc);
     if (two) {
         __builtin_amdgcn_sched_barrier(0);               // (the requests below not hoisted into the product above)
-#pragma unroll
-        for (int ks = 0; ks < kKS; ++ks) request_kstep(D.wt2_packed, ks);
+        W.request_weight(wf, D.wt2_packed);
     }
     store(D.dx, D.lddx, D.out_bn, live_in);
     if (two) {
@@ -578,32 +500,16 @@ __global__ __launch_bounds__(kThreads, 4) void dense_stage_bwd_kernel(StageBwdBa
     }
 }
 
-inline bool al16(const void* p) { return p == nullptr || ((uintptr_t)p & 15u) == 0; }
+using cwn::al16;
 
 template <int F>
 int launch_stage(const StageBatch& B, int64_t blocks, hipStream_t stream) {
-    static std::once_flag once;
-    static hipError_t attr_err = hipSuccess;
-    std::call_once(once, [] {
-        attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_stage_kernel<F>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)Shape<F>::kLdsBytes);
-    });
-    if (attr_err != hipSuccess) return CWN_ERR_LAUNCH;
-    dense_stage_kernel<F><<<dim3((unsigned)blocks), dim3(kThreads), Shape<F>::kLdsBytes, stream>>>(B);
-    return hipGetLastError() == hipSuccess ? CWN_OK : CWN_ERR_LAUNCH;
+    return cwn::launch_tile<&dense_stage_kernel<F>>(Shape<F>::kLdsBytes, blocks, stream, B);
 }
 
 template <int F>
 int launch_stage_ex(const StageBatchEx& B, int64_t blocks, hipStream_t stream) {
-    static std::once_flag once;
-    static hipError_t attr_err = hipSuccess;
-    std::call_once(once, [] {
-        attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_stage_ex_kernel<F>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)Shape<F>::kLdsBytes);
-    });
-    if (attr_err != hipSuccess) return CWN_ERR_LAUNCH;
-    dense_stage_ex_kernel<F><<<dim3((unsigned)blocks), dim3(kThreads), Shape<F>::kLdsBytes, stream>>>(B);
-    return hipGetLastError() == hipSuccess ? CWN_OK : CWN_ERR_LAUNCH;
+    return cwn::launch_tile<&dense_stage_ex_kernel<F>>(Shape<F>::kLdsBytes, blocks, stream, B);
 }
 
 template <int F>
