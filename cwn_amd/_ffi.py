@@ -24,6 +24,7 @@ EXPORTS = ('cwn_abi_version', 'cwn_error_string', 'cwn_target_arch', 'cwn_csr_wo
            'cwn_bn_finalize_f32', 'cwn_step_begin', 'cwn_axpy_eps_f32', 'cwn_dropout_f32', 'cwn_embed_front_bwd_f32', 'cwn_norm_act_f32', 'cwn_norm_bwd_reduce_f32', 'cwn_norm_bwd_apply_f32', 'cwn_norm_bwd_f32',
            'cwn_layernorm_act_f32', 'cwn_layernorm_bwd_workspace_bytes', 'cwn_layernorm_bwd_f32',
            'cwn_oriented_layer_f32', 'cwn_oriented_dz_f32',
+           'cwn_target_head_f32', 'cwn_target_head_bwd_f32', 'cwn_target_head_bwd_workspace_bytes',
            'cwn_gemm_tn_f32', 'cwn_gemm_tn_workspace_bytes', 'cwn_adam_f32', 'cwn_adam_dev_f32', 'cwn_loss_f32', 'cwn_loss_cols_f32', 'cwn_embedding_fwd_f32', 'cwn_embedding_bwd_f32', 'cwn_embed_front_f32', 'cwn_head_f32', 'cwn_head_bwd_f32', 'cwn_head_pool_floats', 'cwn_lift_create', 'cwn_lift_size', 'cwn_lift_copy', 'cwn_lift_destroy',
            'cwn_lift_many', 'cwn_lift_many_count', 'cwn_lift_many_lengths', 'cwn_lift_many_copy', 'cwn_lift_many_destroy',
            # the evaluation pass (csrc/cwn_metrics.hip)
@@ -287,6 +288,7 @@ class LnDesc(C.Structure):
 
 ACT_ID, ACT_RELU, ACT_ELU, ACT_TANH, ACT_SIGMOID = range(5)      # = CWN_ACT_*
 ORIENTED_MAX_WIDTH = 128       # widest x / out row of cwn_oriented_layer_f32
+TARGET_HEAD_MAX_H, TARGET_HEAD_MAX_K = 512, 64     # = CWN_TARGET_HEAD_MAX_H / _K: widest row / most classes of cwn_target_head_f32
 
 
 def oriented_tm(w: int) -> int:
@@ -463,6 +465,15 @@ def lib():
     L.cwn_adam_f32.restype = C.c_int
     L.cwn_adam_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float,
                                C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cwn_target_head_f32.restype = C.c_int
+    L.cwn_target_head_f32.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cwn_target_head_bwd_f32.restype = C.c_int
+    L.cwn_target_head_bwd_f32.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                          C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t,
+                                          C.c_void_p, C.c_void_p]
+    L.cwn_target_head_bwd_workspace_bytes.restype = C.c_size_t
+    L.cwn_target_head_bwd_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32]
     L.cwn_adam_dev_f32.restype = C.c_int
     L.cwn_adam_dev_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p]
@@ -725,9 +736,46 @@ def oriented_dz(dout: torch.Tensor, out: torch.Tensor, act: int) -> torch.Tensor
     return dz
 
 
+def target_head_served(H: int, K: int) -> bool:
+    """The widths and class counts cwn_target_head_f32 / _bwd_f32 take."""
+    return H % 4 == 0 and 4 <= H <= TARGET_HEAD_MAX_H and 1 <= K <= TARGET_HEAD_MAX_K
+
+
+def target_head(x: torch.Tensor, target_rows: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor],
+                err: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[c] = weight . x[target_rows[c]] + bias in one launch; rows of out past a `dynamic_rows` count of the complexes stay
+    unwritten."""
+    Cn, (K, H) = target_rows.numel(), weight.shape
+    out = torch.empty(Cn, K, dtype=torch.float32, device=x.device)
+    check(lib().cwn_target_head_f32(x.data_ptr(), x.size(0), x.stride(0), target_rows.data_ptr(), Cn, weight.data_ptr(), ptr(bias),
+                                    out.data_ptr(), K, H, K, ptr(err), dyn(Cn), stream_ptr(x.device)), 'cwn_target_head_f32')
+    return out
+
+
+def target_head_bwd(g: torch.Tensor, x: torch.Tensor, target_rows: torch.Tensor, weight: torch.Tensor, need_dx: bool,
+                    need_dw: bool, need_db: bool):
+    """(dx [N, H] every row written, dW, db) of target_head in one launch (two beyond 64 complexes); None for what is not needed."""
+    Cn, (K, H), N = target_rows.numel(), weight.shape, x.size(0)
+    dev = x.device
+    dx = torch.empty(N, H, dtype=torch.float32, device=dev) if need_dx else None
+    dW = torch.empty(K, H, dtype=torch.float32, device=dev) if need_dw or need_db else None
+    db = torch.empty(K, dtype=torch.float32, device=dev) if need_db else None
+    # (beyond 64 complexes: the groups' partial sums, added in group order by a second launch; a torch buffer the stream's
+    #  ordering keeps alive until both have run)
+    nbytes = int(lib().cwn_target_head_bwd_workspace_bytes(Cn, H, K)) if dW is not None else 0
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    check(lib().cwn_target_head_bwd_f32(g.data_ptr(), g.stride(0), x.data_ptr(), N, x.stride(0), target_rows.data_ptr(), Cn,
+                                        weight.data_ptr(), ptr(dx), H, ptr(dW), ptr(db), H, K, ptr(ws), nbytes, dyn(Cn),
+                                        stream_ptr(dev)), 'cwn_target_head_bwd_f32')
+    return dx, (dW if need_dw else None), db
+
+
 # False: the row bands of a weight gradient are added with fp32 atomics (fastest: 1.48 ms ZINC training
 # step).  True: per-band partial tiles + a second launch that sums them in band order -- bit-reproducible
 # weight gradients for 0.14 ms more per step (17 extra launches).
+# (That figure is from the form whose band height followed the launch's cost rule.  The bands are now 128 rows whatever M is --
+# what makes a static batch's step bit-identical to the collated batch's -- and the cost of that form has NOT been measured again;
+# a reduction over very many rows, REDDIT-like, gets more bands than before.)
 DETERMINISTIC_TN = os.environ.get('CWN_DETERMINISTIC_TN', '0') == '1'
 
 

@@ -34,7 +34,12 @@ class Cochain(object):
     """Vector-valued signal on the k-cells of a complex (data/complex.py:36-92).
 
     x [num_cells, F]; upper_index / lower_index [2, E] (int64); shared_coboundaries /
-    shared_boundaries [E]; boundary_index [2, B] with row 0 = boundary cell (dim k-1), row 1 = cell."""
+    shared_boundaries [E]; boundary_index [2, B] with row 0 = boundary cell (dim k-1), row 1 = cell.
+    `mask` (bool [num_cells], passed as a keyword like any extra attribute of the reference's cochains): the marked cells
+    of a node-level target -- data/datasets/ringtransfer.py:69-72 marks the one vertex RingSparseCIN reads."""
+
+    mask = None        # bool [num_cells], or None
+    target = None      # batches only: the ONE marked row of every complex (int32 [num_complexes]), or None
 
     def __init__(self, dim: int, x: Tensor = None, upper_index: Tensor = None,
                  lower_index: Tensor = None, shared_boundaries: Tensor = None,
@@ -95,7 +100,7 @@ class Cochain(object):
     def keys(self):
         return [k for k in ('x', 'upper_index', 'lower_index', 'shared_boundaries',
                             'shared_coboundaries', 'boundary_index', 'upper_orient', 'lower_orient',
-                            'y', 'batch', 'ptr') if getattr(self, k, None) is not None]
+                            'y', 'batch', 'ptr', 'mask', 'target') if getattr(self, k, None) is not None]
 
     def __getitem__(self, key):
         return getattr(self, key, None)
@@ -208,6 +213,23 @@ def _cat_with_offsets(items: List[Tensor], offsets: List, two_rows: bool) -> Ten
     return (flat + off.to(flat.device)).contiguous()
 
 
+def _target_rows(masks: List[Tensor], offsets: List[int]) -> Optional[Tensor]:
+    """The global row of the one marked cell of every cochain (int32, on the masks' device), or None when some cochain does
+    not mark exactly one cell.  Masks that already live on a device cost ONE copy to the host for the whole list (a
+    synchronisation: batch on the host and move the batch, as the loaders do, or pack the dataset)."""
+    sizes = [int(m.numel()) for m in masks]
+    flat = torch.cat([m.reshape(-1) for m in masks]).cpu()
+    hits = torch.nonzero(flat).reshape(-1)
+    if hits.numel() != len(masks):
+        return None
+    first = torch.tensor(_offsets(sizes), dtype=torch.long)
+    owner = torch.bucketize(hits, first, right=True) - 1            # the cochain every mark lies in
+    if not torch.equal(owner, torch.arange(len(masks))):
+        return None
+    rows = hits - first + torch.tensor(list(offsets), dtype=torch.long)
+    return rows.to(torch.int32).to(masks[0].device)
+
+
 class CochainBatch(Cochain):
     """A batch of cochains stored as one big cochain over disconnected cells
     (data/complex.py:296-458).  `batch[i]` is the position (in the list) of the complex cell i
@@ -276,6 +298,12 @@ class CochainBatch(Cochain):
                 out._x = val
             else:
                 setattr(out, key, val)
+        # the extra key of the ring experiment (data/complex.py batches any extra key by concatenation): `mask`, and -- here,
+        # once per batch, where the masks are still what the caller built -- the marked row of every complex as a number
+        masks = [c.mask for c in data_list]
+        if all(m is not None for m in masks) and data_list:
+            out.mask = torch.cat([m.reshape(-1) for m in masks], dim=0).contiguous()
+            out.target = _target_rows(masks, off_here)
         have = [(i, n) for i, n in enumerate(n_here) if n is not None]
         if have:
             ids = torch.tensor([i for i, _ in have], dtype=torch.long)
@@ -526,6 +554,16 @@ class ComplexBatch(Complex):
         super().__init__(*cochains, y=y)
         self.num_complexes = num_complexes
         self.dimension = dimension
+
+    def target_rows(self, dim: int = 0) -> Optional[Tensor]:
+        """The row of the ONE marked cell (`mask`) of every complex among the batched cells of dimension `dim`: int32
+        [num_complexes], ascending, on the device the batch is on -- what ops.target_head reads instead of `x[mask]` (a
+        nonzero: a host synchronisation).  Computed where the batch is built (from_complex_list over the complexes' masks;
+        PackedComplexes.collate and the slots of a StaticBatch get it from the collate launch) and moved with the batch.
+        None when the cochain carries no mask, or some complex does not mark exactly one cell: a model then takes `x[mask]`
+        literally (eager only)."""
+        c = self.cochains.get(dim)
+        return None if c is None else getattr(c, 'target', None)
 
     @classmethod
     def from_complex_list(cls, data_list: List[Complex], follow_batch=(), max_dim: int = 2):

@@ -163,7 +163,9 @@ __device__ __forceinline__ void tile_store(float* lds, const f32x4 (&v)[kU], con
 // (a static batch: D.M is the CAPACITY of the buffers) the batch's own rows would all fall into the first bands -- the others
 // idle, the launch as long as a full-capacity one (REDDIT-32, capacity 1.46 x the batch: 87 against 67 us, round 6).  The same
 // number of bands over the rows that exist instead: shorter bands, every workgroup busy; never longer than the host's (the
-// workspace of the deterministic form is laid out by band NUMBER).
+// workspace of the deterministic form is laid out by band NUMBER).  Not in the deterministic form itself (the callers pass
+// dynamic = false there): its bands are kBandRows rows whatever the capacity, so that a row's band -- and with it every bit of
+// the sum -- is the same for a static batch and for the same complexes collated to their own size.
 __device__ __forceinline__ int64_t dev_band_rows(int64_t host_rows, int bands, bool dynamic, int64_t M, int chunk) {
     if (!dynamic || bands < 1) return host_rows;
     const int64_t per = (M + bands - 1) / bands;
@@ -191,7 +193,7 @@ __global__ __launch_bounds__(kThreads, 4) void gemm_tn_kernel(TnBatch B) {
     // grid and bounds the addresses of the loads, which do not wait for this one
     const int64_t Mcap = D.M;
     const int64_t M = D.m_dev != nullptr ? (*D.m_dev < Mcap ? *D.m_dev : Mcap) : Mcap;
-    const int64_t band_rows = dev_band_rows(B.band_rows_of[di], B.bands[di], D.m_dev != nullptr, M, kChunk);
+    const int64_t band_rows = dev_band_rows(B.band_rows_of[di], B.bands[di], D.m_dev != nullptr && B.ws[di] == nullptr, M, kChunk);
     const int64_t row_lo = (int64_t)band * band_rows;
     const int64_t cap_hi = row_lo + band_rows < Mcap ? row_lo + band_rows : Mcap;
     const int64_t row_hi = row_lo + band_rows < M ? row_lo + band_rows : M;
@@ -398,7 +400,7 @@ __global__ __launch_bounds__(kThreads2, CWN_TN_WGS) void gemm_tn_split_kernel(Tn
     // (a static batch: the bands are cut from the batch's OWN rows -- dev_band_rows -- so this launch's first loads wait for the
     //  row count; a prepared batch: the host's cut, the count not waited for)
     const int64_t M = D.m_dev != nullptr ? (*D.m_dev < Mcap ? *D.m_dev : Mcap) : Mcap;
-    const int64_t band_rows = dev_band_rows(B.band_rows_of[di], B.bands[di], D.m_dev != nullptr, M, kChunk2);
+    const int64_t band_rows = dev_band_rows(B.band_rows_of[di], B.bands[di], D.m_dev != nullptr && B.ws[di] == nullptr, M, kChunk2);
     const int64_t row_lo = (int64_t)band * band_rows;
     const int64_t cap_hi = row_lo + band_rows < Mcap ? row_lo + band_rows : Mcap;
     const int n0 = tile_n * kTile2, k0 = tile_k * kTile2;
@@ -613,15 +615,20 @@ extern "C" int cwn_gemm_tn_f32(const cwn_gemm_tn_desc* descs, int n, void* works
     // a target of `cand` rows per workgroup; descriptor i is cut into ceil(M_i / cand) bands of EQUAL length (rounded up to the
     // chunk): the workgroups of a launch end together instead of a short last band per descriptor idling its CU
     auto bands_of = [&](int i, int cand) { return (descs[i].M + cand - 1) / cand; };
+    // The deterministic form (a workspace: per-band partial tiles, added in band order) takes bands of kBandRows rows always:
+    // rows r .. r + kBandRows - 1 are one partial sum whatever M is, and the bands past the rows that exist add zeros.  A
+    // captured step over capacity-sized buffers (m_dev) then gives the bits of the eager step on the batch's own rows.
+    const bool ordered = workspace != nullptr;
     auto rows_of = [&](int i, int cand) {
         const int64_t nb = bands_of(i, cand);
-        if (!split || nb == 0) return (int64_t)cand;
+        if (!split || nb == 0 || ordered) return (int64_t)cand;
         return ((descs[i].M + nb - 1) / nb + chunk - 1) / chunk * chunk;
     };
     int band_rows = kBandRows;
     {
         double best = 0.0;
         for (int cand = kBandRows; cand <= kMaxBandRows; cand += kChunk) {
+            if (ordered && cand != kBandRows) continue;
             if (band_env >= kBandRows && band_env % kChunk == 0 && cand != band_env) continue;
             int64_t nb = 0, longest = 0;
             for (int i = 0; i < n; ++i) {

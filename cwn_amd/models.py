@@ -144,6 +144,34 @@ class BondEncoder(torch.nn.Module):
         return sum(self.bond_embedding_list[i](edge_attr[:, i]) for i in range(edge_attr.shape[1]))
 
 
+def _pack_training_weights(convs) -> None:
+    """Before a training forward over SparseCINConv / CINppConv layers: the packed forms of their weights that the blocked layer
+    kernel and the dense-stage kernels stream, every layer's in one launch each (and what lets the stage kernels take the
+    launches of a static batch, which carry a device-side row count)."""
+    if torch.is_grad_enabled() and layers.BLOCKED_TRAIN_FORWARD and layers.BLOCKED_LAYER:
+        # training forward through the blocked layer kernel: the message weights of all layers packed in one launch
+        ws = [lvl.msg_up_nn[1].weight for conv in convs          # (CIN++ layers too: round 6)
+              for lvl in getattr(conv, 'mp_levels', [])
+              if getattr(lvl, '_up_kind', lambda: None)() == 'cat_linear_relu' and lvl.msg_up_nn[1].weight.is_cuda]
+        if ws:
+            ops.pack_layer_weights_many(ws, transposed=bool(ops.BLOCKED_BACKWARD))
+    if torch.is_grad_enabled() and ops.STAGE_KERNEL and layers.FUSED_DENSE_TRAINING:
+        # ... and the blocks of the update / combine Linear layers (cwn_dense_stage_f32 streams them pre-split)
+        sw = []
+        for conv in convs:
+            if isinstance(conv, layers.CINppConv):
+                continue                  # (packs its own blocks per forward, layers.CINppConv._dense_train)
+            for lvl in getattr(conv, 'mp_levels', []):
+                for net in (getattr(lvl, 'update_up_nn', None), getattr(lvl, 'update_boundaries_nn', None),
+                            getattr(lvl, 'combine_nn', None)):
+                    st = layers._mlp_stages(net) if net is not None else None
+                    for lin, _ in (st or []):
+                        if lin.weight.is_cuda and lin.weight.requires_grad:
+                            sw.append(lin.weight)
+        if sw:
+            ops.pack_stage_weights_many(sw)
+
+
 class _SparseCINStack(torch.nn.Module):
     """What SparseCIN (mp/models.py:112-260), EmbedSparseCIN (mp/molec_models.py:12-163) and
     OGBEmbedSparseCIN (mp/molec_models.py:201-352) share: L x SparseCINConv, optional JK-cat,
@@ -195,28 +223,7 @@ class _SparseCINStack(torch.nn.Module):
     def _convs_and_head(self, data: ComplexBatch, include_partial: bool, res: dict):
         act = get_nonlinearity(self.nonlinearity, return_module=False)
         jump_xs, xs = None, None
-        if torch.is_grad_enabled() and layers.BLOCKED_TRAIN_FORWARD and layers.BLOCKED_LAYER:
-            # training forward through the blocked layer kernel: the message weights of all layers packed in one launch
-            ws = [lvl.msg_up_nn[1].weight for conv in self.convs          # (CIN++ layers too: round 6)
-                  for lvl in getattr(conv, 'mp_levels', [])
-                  if getattr(lvl, '_up_kind', lambda: None)() == 'cat_linear_relu' and lvl.msg_up_nn[1].weight.is_cuda]
-            if ws:
-                ops.pack_layer_weights_many(ws, transposed=bool(ops.BLOCKED_BACKWARD))
-        if torch.is_grad_enabled() and ops.STAGE_KERNEL and layers.FUSED_DENSE_TRAINING:
-            # ... and the blocks of the update / combine Linear layers (cwn_dense_stage_f32 streams them pre-split)
-            sw = []
-            for conv in self.convs:
-                if isinstance(conv, layers.CINppConv):
-                    continue                  # (packs its own blocks per forward, layers.CINppConv._dense_train)
-                for lvl in getattr(conv, 'mp_levels', []):
-                    for net in (getattr(lvl, 'update_up_nn', None), getattr(lvl, 'update_boundaries_nn', None),
-                                getattr(lvl, 'combine_nn', None)):
-                        st = layers._mlp_stages(net) if net is not None else None
-                        for lin, _ in (st or []):
-                            if lin.weight.is_cuda and lin.weight.requires_grad:
-                                sw.append(lin.weight)
-            if sw:
-                ops.pack_stage_weights_many(sw)
+        _pack_training_weights(self.convs)
         for c, conv in enumerate(self.convs):
             params = self._edit_params(data.get_all_cochain_params(max_dim=self.max_dim, include_down_features=False))
             if self.conv_dropout and self.training and self.dropout_rate > 0 and isinstance(conv, SparseCINConv):
@@ -743,6 +750,73 @@ class EdgeMPNN(torch.nn.Module):
         x = ops.dropout(x, self.dropout_rate, self.training)
         x = self.lin2(x)
         return (x, cell_pred) if include_partial else x
+
+    def __repr__(self):
+        return self.__class__.__name__
+
+
+class RingSparseCIN(torch.nn.Module):
+    """mp/ring_exp_models.py:10-73, the model of the ring-transfer experiment (exp/run_ring_exp.py): same constructor
+    arguments, parameter names and forward(data, include_partial), so the reference's state_dict loads.  The only model of
+    the reference whose prediction is not a pooled readout: `lin1(x[data.nodes.mask])`, the features of the ONE marked vertex
+    of every complex -- here ops.target_head on `data.target_rows(0)` (one launch each way, capturable: StaticForward /
+    StaticTrainStep serve the model like the others; the output is [complexes, classes]).  A batch that does not carry one
+    marked vertex per complex takes the reference's `x[mask]` literally (a nonzero: eager only)."""
+
+    def __init__(self, num_input_features, num_classes, num_layers, hidden, max_dim: int = 2, nonlinearity='relu',
+                 train_eps=False, use_coboundaries=False, graph_norm='id'):
+        super().__init__()
+        self.max_dim = max_dim
+        self.convs = torch.nn.ModuleList()
+        self.nonlinearity = nonlinearity
+        self.init_layer = Linear(num_input_features, num_input_features)
+        act_module = get_nonlinearity(nonlinearity, return_module=True)
+        self.graph_norm = get_graph_norm(graph_norm)
+        for i in range(num_layers):
+            layer_dim = num_input_features if i == 0 else hidden
+            self.convs.append(SparseCINConv(
+                up_msg_size=layer_dim, down_msg_size=layer_dim, boundary_msg_size=layer_dim, passed_msg_boundaries_nn=None,
+                passed_msg_up_nn=None, passed_update_up_nn=None, passed_update_boundaries_nn=None, train_eps=train_eps,
+                max_dim=self.max_dim, hidden=hidden, act_module=act_module, layer_dim=layer_dim, graph_norm=self.graph_norm,
+                use_coboundaries=use_coboundaries))
+        self.lin1 = Linear(hidden, num_classes)
+
+    def reset_parameters(self):
+        self.init_layer.reset_parameters()
+        for conv in self.convs:                  # (:43-44 calls conv.reset_parameters(), which SparseCINConv does not define there
+            for m in conv.modules():             #  either: every submodule that can is reset)
+                if m is not conv and hasattr(m, 'reset_parameters'):
+                    m.reset_parameters()
+        self.lin1.reset_parameters()
+
+    def _init(self, x: torch.Tensor) -> torch.Tensor:
+        lin = self.init_layer
+        if x.is_cuda and x.dtype == torch.float32 and lin.weight.dtype == torch.float32 and lin.in_features <= ops.GEMM_MAX_K:
+            return ops.gemm_many([ops.Gemm(X=x, W=lin.weight, bias=lin.bias)])[0]
+        return lin(x)
+
+    @_one_check
+    def forward(self, data: ComplexBatch, include_partial=False):
+        xs, res = None, {}
+        _pack_training_weights(self.convs)
+        data.nodes.x = self._init(data.nodes.x)             # (written back to the batch, as :51 does)
+        for c, conv in enumerate(self.convs):
+            params = data.get_all_cochain_params(max_dim=self.max_dim, include_down_features=False)
+            xs = conv(*params, start_to_process=0)
+            data.set_xs(xs)
+            if include_partial:
+                for k in range(len(xs)):
+                    res[f'layer{c}_{k}'] = xs[k]
+        x = xs[0]
+        rows = data.target_rows(0) if hasattr(data, 'target_rows') else None
+        if rows is not None:
+            x = ops.target_head(x, rows, self.lin1.weight, self.lin1.bias)
+        else:                                               # :61-64 literally
+            x = self.lin1(x[data.nodes.mask])
+        if include_partial:
+            res['out'] = x
+            return x, res
+        return x
 
     def __repr__(self):
         return self.__class__.__name__

@@ -581,7 +581,8 @@ DETERMINISTIC = False
 def deterministic(on: bool = True) -> None:
     """Bit-reproducible TRAINING arithmetic (DDP debugging: two runs, graph vs eager, rank vs rank give torch.equal gradients):
     every sum whose order the fast path leaves to the arrival order of atomics takes its ordered form --
-      weight gradients: per-band partial tiles + a reduce in band order (cwn_gemm_tn_f32 with a workspace: _ffi.DETERMINISTIC_TN);
+      weight gradients: per-band partial tiles + a reduce in band order (cwn_gemm_tn_f32 with a workspace: _ffi.DETERMINISTIC_TN;
+        bands of 128 rows whatever the capacity: a static batch's step has the bits of the step on the collated batch);
       BatchNorm(train) statistics: per-band partials summed in band order by cwn_bn_finalize_f32 (dense_train.LIVE_BN = False);
       BatchNorm backward sums: the one-launch column-owning form cwn_norm_bwd_f32 (dense_train.FUSED_NORM_BACKWARD; matrices
         of at most 4096 rows -- larger ones keep the atomic reduce) and no slot sums (LIVE_BN_BWD = False);
@@ -1985,6 +1986,80 @@ def oriented_layer(x: Tensor, up_adj: Optional[Adjacency], up_orient: Optional[T
     if not grad:
         return _oriented_launch(x, up, dn, w_self, w_up if up is not None else None, w_dn if dn is not None else None, act, H)
     return _OrientedLayer.apply(x, w_self, w_up, w_dn, up, dn, act, H)
+
+
+# ------------------------------------------------------------------------------------------------
+# The target-cell head (csrc/cwn_target_head.hip): lin1(x[mask]) of RingSparseCIN, one launch each way
+# ------------------------------------------------------------------------------------------------
+FUSED_TARGET_HEAD = os.environ.get('CWN_FUSED_TARGET_HEAD') != '0'     # A/B: '0' keeps gather_rows + linear
+
+
+class _TargetHead(torch.autograd.Function):
+    """out[c] = W x[rows[c]] + b: cwn_target_head_f32 forward, cwn_target_head_bwd_f32 backward (dx with every row written,
+    dW and db summed in complex order: the same bits on every run, with or without `deterministic()`)."""
+
+    @staticmethod
+    def forward(ctx, x, rows, weight, bias, err):
+        ctx.save_for_backward(x, rows, weight)
+        ctx.has_bias = bias is not None
+        return _ffi.target_head(x, rows, weight, bias, err)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, rows, weight = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        g = _f32c(g, 'grad')
+        dx, dW, db = _ffi.target_head_bwd(g, x, rows, weight, need[0], need[2], ctx.has_bias and need[3])
+        return dx, None, dW, db, None
+
+
+def target_head_applies(x: Tensor, target_rows: Tensor, weight: Tensor, bias: Optional[Tensor]) -> bool:
+    """Do cwn_target_head_f32 / _bwd_f32 take these operands?  float32 on the GPU, x [N, H] with 16-byte rows, weight
+    [K, H], H % 4 == 0, H <= 512, K <= 64, int32 rows."""
+    ts = (x, weight) + ((bias,) if bias is not None else ())
+    if not all(isinstance(t, Tensor) and t.is_cuda and t.dtype == torch.float32 for t in ts):
+        return False
+    if not (isinstance(target_rows, Tensor) and target_rows.is_cuda and target_rows.dtype == torch.int32 and target_rows.dim() == 1):
+        return False
+    if x.dim() != 2 or weight.dim() != 2 or x.size(1) != weight.size(1) or (bias is not None and tuple(bias.shape) != (weight.size(0),)):
+        return False
+    return (_ffi.target_head_served(int(weight.size(1)), int(weight.size(0))) and x.stride(1) == 1 and x.stride(0) % 4 == 0
+            and x.data_ptr() % 16 == 0)
+
+
+def target_head(x: Tensor, target_rows: Tensor, weight: Tensor, bias: Optional[Tensor] = None) -> Tensor:
+    """A prediction read off one marked cell per complex -- `lin1(x[mask])` of mp/ring_exp_models.py:61-64 with the marked
+    rows given as numbers (ComplexBatch.target_rows: int32, one per complex, ascending), so that nothing synchronises:
+
+        out[c, :] = weight . x[target_rows[c], :] + bias            [len(target_rows), K]
+
+    One launch forward, one backward (csrc/cwn_target_head.hip), differentiable w.r.t. x, weight and bias; under
+    `_ffi.dynamic_rows` (a static batch) the rows past the live number of complexes are left unwritten.  The launch takes
+    float32 operands with H % 4 == 0, H <= 512, K <= 64 (`target_head_applies`); float64, other widths or class counts and
+    CWN_FUSED_TARGET_HEAD=0 (`ops.FUSED_TARGET_HEAD = False`) take the former form -- gather_rows on the same rows, then
+    linear -- which is capturable too.  A row outside x raises IndexError (at the model's one check, or at the next
+    csr.check_errors under capture)."""
+    _ffi.require_gpu(x, 'x')
+    _ffi.require_gpu(target_rows, 'target_rows')
+    if target_rows.dtype not in (torch.int32, torch.long) or target_rows.dim() != 1:
+        raise TypeError('target_rows: a vector of int32 (or int64) row numbers')
+    if FUSED_TARGET_HEAD and target_rows.dtype == torch.int32:
+        xc = x if x.dim() != 2 or x.stride(1) == 1 else x.contiguous()
+        wc = weight.contiguous()
+        if target_head_applies(xc, target_rows, wc, bias):
+            from .csr import _err_flag, VALIDATE_INDICES, check_errors
+            rows = target_rows.contiguous()
+            bc = None if bias is None else bias.contiguous()
+            err = _err_flag(x.device)
+            if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (xc, wc, bc)):
+                out = _TargetHead.apply(xc, rows, wc, bc, err)
+            else:
+                out = _ffi.target_head(xc, rows, wc, bc, err)
+            if VALIDATE_INDICES and not torch.cuda.is_current_stream_capturing():
+                check_errors(x.device)
+            return out
+    idx = target_rows.to(torch.long)           # (a launch of its own, inside a capture too: a static slot's rows change under it)
+    return torch.nn.functional.linear(gather_rows(x, idx), weight, bias)
 
 
 # ------------------------------------------------------------------------------------------------

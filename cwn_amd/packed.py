@@ -28,6 +28,11 @@ _ALL_KEYS = ('x', 'y') + _INDEX_KEYS
 # running entry count.  What cwn_csr_build does per batch (two launches per step for the front's plans and their transposes)
 # is then part of the one collate launch.
 _CSR_KEYS = ('b_rowptr', 'b_col', 'bt_rowptr', 'bt_col')
+# The node-level target of the ring experiment (data/datasets/ringtransfer.py:69-72: `mask`, one marked vertex per complex):
+# kept as the LOCAL number of the marked cell, one int32 per complex.  It collates like a CSR column -- + the complex's
+# first row of that dimension, the existing add-an-offset op -- into the global row numbers ops.target_head reads
+# (ComplexBatch.target_rows): no host work per batch, and a slot of a StaticBatch holds them like any other key.
+_TARGET_KEY = 'target'
 
 
 class _Packed:
@@ -77,6 +82,20 @@ class PackedComplexes:
                     continue
                 per_key[key] = self._pack(items, key)
             self.keys.append(per_key)
+        for d in range(D):
+            masks = [getattr(cx.cochains[d], 'mask', None) if (d in cx.cochains and d <= cx.dimension) else None for cx in complexes]
+            if all(m is None for m in masks):
+                continue
+            local = np.zeros(C, dtype=np.int64)
+            for ci, m in enumerate(masks):
+                hit = None if m is None else torch.nonzero(m.reshape(-1)).reshape(-1)
+                if hit is None or hit.numel() != 1:
+                    raise ValueError(f'complex {ci}: the mask of dimension {d} must mark exactly one cell (it marks '
+                                     f'{0 if hit is None else hit.numel()}): a packed dataset carries ONE target row per complex')
+                if int(m.numel()) != int(self.n_cells[d, ci]):
+                    raise IndexError(f'complex {ci}: a mask of {int(m.numel())} entries over {int(self.n_cells[d, ci])} cells of dimension {d}')
+                local[ci] = int(hit[0])
+            self._add_target(d, local)
         ys = [cx.y for cx in complexes]
         self.y = self._pack(ys, 'y') if all(t is not None for t in ys) else None
         self._finalise()
@@ -107,9 +126,25 @@ class PackedComplexes:
                 if key in keys[d] and np.asarray(keys[d][key][2], dtype=bool).any():
                     per_key[key] = self._packed(*keys[d][key], key)
             self.keys.append(per_key)
+        for d in range(D):
+            if _TARGET_KEY in keys[d]:     # the marked cell of every complex, LOCAL numbers: an array of one integer per complex
+                self._add_target(d, np.asarray(torch.as_tensor(keys[d][_TARGET_KEY]).cpu().numpy(), dtype=np.int64).reshape(-1))
         self.y = self._packed(*y, 'y') if y is not None else None
         self._finalise()
         return self
+
+    def _add_target(self, d: int, local: np.ndarray) -> None:
+        """The packed key (d, 'target'): `local[c]` = the marked cell of complex c among its cells of dimension d."""
+        n = np.asarray(self.n_cells[d], dtype=np.int64)
+        if local.shape != (self.num,):
+            raise ValueError(f'one target per complex ({self.num}), got {local.shape}')
+        if self.num and (local.min() < 0 or (local >= n).any()):
+            bad = int(np.nonzero((local < 0) | (local >= n))[0][0])
+            raise IndexError(f'target of dimension {d}: complex {bad} marks cell {int(local[bad])} of its {int(n[bad])}: a local '
+                             'index outside its complex')
+        ones = np.ones(self.num, dtype=np.int64)
+        self.keys[d][_TARGET_KEY] = _Packed(torch.from_numpy(local.astype(np.int32)).to(self.device), np.arange(self.num, dtype=np.int64),
+                                            ones, ones > 0, 1, 1, _ffi.COLLATE_ADD32)
 
     def _packed(self, data: torch.Tensor, lengths, has, key) -> _Packed:
         lengths = np.asarray(lengths, dtype=np.int64)
@@ -211,7 +246,8 @@ class PackedComplexes:
         return -1
 
     # add-table of a key inside a dimension's block of five offset rows (here, here, down, here, up), in rows
-    _ADD_ROW = {'upper_index': 0, 'lower_index': 0, 'shared_boundaries': 2, 'shared_coboundaries': 4, 'boundary_index': 2}
+    _ADD_ROW = {'upper_index': 0, 'lower_index': 0, 'shared_boundaries': 2, 'shared_coboundaries': 4, 'boundary_index': 2,
+                _TARGET_KEY: 0}
 
     def _prepare(self, idx):
         """Host half of collate: output tensors (uninitialised), ONE int64 array holding every segment table, and
@@ -267,6 +303,8 @@ class PackedComplexes:
             cb = cochains[d]
             if key == 'x':
                 cb._x = out
+            elif key == _TARGET_KEY:
+                cb.target = out
             else:
                 cb.__slices__[key] = dst[k].tolist()
                 setattr(cb, key, out)
@@ -318,6 +356,11 @@ class PackedComplexes:
             arr = (_ffi.CollateDesc * len(chunk))(*chunk)
             _ffi.check(L.cwn_collate(arr, len(chunk), B, s), 'cwn_collate')
         tab.record_stream(torch.cuda.current_stream(dev))
+        for cb in cochains:
+            # the reference's key, for code that takes `x[mask]` literally (RingSparseCIN reads `target`): three small launches
+            # per batch (zeros, the int64 rows, index_fill_), no host work
+            if cb.target is not None:
+                cb.mask = torch.zeros(cb.__num_cells__, dtype=torch.bool, device=dev).index_fill_(0, cb.target.to(torch.long), True)
         batch = ComplexBatch(*cochains, y=y, num_complexes=B, dimension=len(cochains) - 1)
         batch._collate_tables = tab     # keep the tables alive until the launch has consumed them
         return batch

@@ -209,16 +209,21 @@ class StaticBatch:
     `fits(batches)` tells the caller which batches the buffers hold."""
 
     def __init__(self, packed: PackedComplexes, batch_size: int, caps: Optional[dict] = None, variant: Optional[int] = None,
-                 group: Optional[int] = None, indices: Optional[Sequence[int]] = None, slots: int = 1, mode: str = 'blocked'):
+                 group: Optional[int] = None, indices: Optional[Sequence[int]] = None, slots: int = 1, mode: str = 'blocked',
+                 items: bool = False):
         """mode 'blocked' (default): the complex-blocked launches of SparseCINConv are the only path -- item tables cut on the
         device, no CSR of the upper adjacencies; a complex beyond one workgroup does not fit.  mode 'csr' (round 5): every
         adjacency of a slot gets a REAL destination-sorted CSR plan, rebuilt by the fill from the slot's int64 entries with
         the entry count read from the tables (cwn_csr_desc.e_dev) -- the streaming path (grouped GEMM + cwn_aggregate_f32)
         then runs inside the captured graph: hub complexes (REDDIT-like clique lifts), CINppConv / OrientedConv layers,
-        molecules beyond a workgroup.  No item tables in this mode (the layers take their CSR path)."""
+        molecules beyond a workgroup.  No item tables in this mode (the layers take their CSR path) -- unless `items=True`:
+        then a slot carries both, and every layer takes the launch it takes on a collated batch (a model whose layers differ:
+        RingSparseCIN's 5-wide first layer streams, its 64-wide layers run complex-blocked; as in mode 'blocked', a complex
+        beyond a workgroup does not fit)."""
         if mode not in ('blocked', 'csr'):
             raise ValueError("mode 'blocked' or 'csr'")
         self.mode = mode
+        self.items = bool(items) and mode == 'csr'
         self.build_backward = False          # (StaticTrainStep: the fill also builds the transposed plans)
         self._slot_long: Dict = {}           # slot -> the collated plans whose long-row lists the fill writes (mode 'csr')
         self._cap_cols = None                # (_check_capacity: the distinct size columns a batch can exceed)
@@ -508,7 +513,7 @@ class StaticBatch:
             self.variant = 1
 
     def _make_family(self, kind: str, F: int, has_up, has_b):
-        if self.mode == 'csr':
+        if self.mode == 'csr' and not self.items:
             return None                        # (no item tables: the layers take their CSR path)
         if kind == 'fwd':
             self._pick_variant(F, has_up, has_b)

@@ -553,3 +553,43 @@ def edge_flows(n_complexes: int, side: int, seed: int, holes: bool = True, flip=
                            upper_orient=torch.from_numpy(mesh['upper_orient'] * t[up[0]] * t[up[1]]),
                            y=torch.tensor([cls])))
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# ring transfer (data/datasets/ring_utils.py:61-103, data/datasets/ringtransfer.py:60-76)
+# ------------------------------------------------------------------------------------------------
+def ring_transfer(nodes: int, samples: int, classes: int = 5) -> List[Complex]:
+    """The RING-TRANSFER dataset restated: `samples` rings of `nodes` vertices, lifted with max_k = nodes (one two-cell with
+    all `nodes` edges on its boundary).  Vertex features are constant one, zero at vertex 0 (the target) and the one-hot
+    label at vertex nodes // 2 (the source, on the other side of the ring); complex i carries label i // (samples //
+    classes); edge and two-cell features are zeroed; `nodes.mask` marks vertex 0.  Three cellular layers carry the label
+    across for every ring size (the two-cell touches every edge), a GIN needs nodes / 2.  The complexes of one call share
+    their index tensors (they all are the same ring)."""
+    if nodes < 3 or classes < 1 or samples < classes or samples % classes != 0:
+        raise ValueError('a ring has at least 3 vertices, and `samples` is a positive multiple of `classes`')
+    per_class = samples // classes
+    bonds = [(i, i + 1) for i in range(nodes - 1)] + [(0, nodes - 1)]
+    zeros = torch.zeros(nodes, classes)
+    shape = ring_lift(nodes, bonds, zeros, zeros.clone(), max_k=nodes, rx=torch.zeros(1, classes))
+    assert shape.dimension == 2 and shape.two_cells.num_cells == 1
+    v, e, r = shape.nodes, shape.edges, shape.two_cells
+    mask = torch.zeros(nodes, dtype=torch.bool)
+    mask[0] = True
+    xs = []
+    for label in range(classes):
+        x = torch.ones(nodes, classes)
+        x[0, :] = 0.0
+        x[nodes // 2, :] = 0.0
+        x[nodes // 2, label] = 1.0
+        xs.append(x)
+    out = []
+    for i in range(samples):
+        label = i // per_class
+        out.append(Complex(
+            Cochain(dim=0, x=xs[label], upper_index=v.upper_index, shared_coboundaries=v.shared_coboundaries,
+                    num_cells_up=nodes, num_cells=nodes, mask=mask),
+            Cochain(dim=1, x=e.x, upper_index=e.upper_index, shared_coboundaries=e.shared_coboundaries,
+                    boundary_index=e.boundary_index, num_cells=nodes, num_cells_down=nodes, num_cells_up=1),
+            Cochain(dim=2, x=r.x, boundary_index=r.boundary_index, num_cells=1, num_cells_down=nodes, num_cells_up=0),
+            y=torch.tensor([label], dtype=torch.long), dimension=2))
+    return out

@@ -28,7 +28,7 @@
  *     cwn_layer_bwd_items_build_dev produce the per-batch tables on the device.
  *     Who checks "*m_dev <= capacity": cwn_gemm_f32 (both kernels), cwn_gemm_tn_f32, cwn_layernorm_*, cwn_dropout_f32,
  *     cwn_loss_f32 / cwn_loss_cols_f32, cwn_csr_long_rows, cwn_embedding_bwd_f32, cwn_embed_front_f32,
- *     cwn_embed_front_bwd_f32 and cwn_oriented_layer_f32 / cwn_oriented_dz_f32 CLAMP the count to the capacity (a larger count behaves as the capacity); cwn_dense_stage_f32 /
+ *     cwn_embed_front_bwd_f32, cwn_oriented_layer_f32 / cwn_oriented_dz_f32 and cwn_target_head_f32 / _bwd_f32 CLAMP the count to the capacity (a larger count behaves as the capacity); cwn_dense_stage_f32 /
  *     _ex / _bwd, cwn_bn_finalize_f32, cwn_norm_*, cwn_update_mlp_f32 / cwn_update_mlp3_f32 and cwn_aggregate_f32 / _f64 take
  *     the count AS IT IS -- there the caller's vouching is what keeps the stores inside the buffers (the collate guard,
  *     cwn_collate_guard, zeroes the counts of a batch beyond its capacities before any of them is read).
@@ -1060,7 +1060,9 @@ typedef struct cwn_gemm_tn_desc {
 } cwn_gemm_tn_desc;
 
 /* With a workspace of cwn_gemm_tn_workspace_bytes() the row bands are combined in a fixed order by
- * a second small launch (deterministic); with workspace == NULL they are added with fp32 atomics. */
+ * a second small launch (deterministic); with workspace == NULL they are added with fp32 atomics.
+ * The deterministic form's bands are 128 rows whatever M is: with m_dev, the result has the bits of the
+ * same call with M = *m_dev on the live rows alone (the bands past them add zeros). */
 size_t cwn_gemm_tn_workspace_bytes(const cwn_gemm_tn_desc* descs_host, int n);
 int cwn_gemm_tn_f32(const cwn_gemm_tn_desc* descs_host, int n, void* workspace, size_t workspace_bytes,
                     cwn_stream_t stream);
@@ -1129,6 +1131,54 @@ int cwn_oriented_layer_f32(const cwn_oriented_desc* desc_host, cwn_stream_t stre
  * step of the layer's backward; dz may alias dout.  Same error codes. */
 int cwn_oriented_dz_f32(const float* dout, const float* out, float* dz, int64_t n, int32_t H, int64_t lddout, int64_t ldout,
                         int64_t lddz, int32_t act, const int64_t* m_dev, cwn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The target-cell head (csrc/cwn_target_head.hip): a prediction read off ONE marked cell per complex.
+ *
+ * Replaces `x = self.lin1(x[mask])`, mp/ring_exp_models.py:61-64 (RingSparseCIN: `mask = data.nodes.mask`) -- the only
+ * head of the reference that is not a pooled readout.  torch's `x[mask]` is a nonzero plus an index (a host
+ * synchronisation); here the marked rows arrive as numbers:
+ *
+ *     out[c, :] = W . x[target_row[c], :] + bias            c < C
+ *
+ *   - x [N, H] row stride ldx (16-byte aligned, ldx % 4 == 0); W [K, H] contiguous (16-byte aligned), bias [K] or NULL;
+ *     target_row int32 [C]: global row numbers, ASCENDING (one target per complex, complexes contiguous in a batch);
+ *     out [C, K] row stride ldout.  H % 4 == 0, 4 <= H <= 512, 1 <= K <= 64: CWN_ERR_BAD_ARG otherwise.
+ *   - a wave64 per complex, 16-byte loads of the one row, W read through L2 (below 16 KiB -- 5 x 64, the ring experiment's --
+ *     and above 64 KiB) or staged in LDS once per workgroup (16 .. 64 KiB), a wave reduction per class; nothing
+ *     of x is read but the target rows; no atomics on data.
+ *   - a row outside [0, N) reads as a zero row and ORs the value 2 into *err_flag (when given: the word's "index
+ *     outside its table" value, as cwn_embedding_fwd_f32), as does a row below its
+ *     predecessor's.
+ *   - m_dev: see "Conventions" (C is the capacity); the count is CLAMPED to C.  Rows of out in [*m_dev, C) are never
+ *     written, their target_row entries never read.
+ * CWN_ERR_ALIGN: x / W off 16 bytes, ldx % 4 != 0, another pointer off 4 bytes (m_dev: 8).  C == 0: nothing is launched.
+ * ------------------------------------------------------------------------------------------ */
+#define CWN_TARGET_HEAD_MAX_H 512
+#define CWN_TARGET_HEAD_MAX_K 64
+int cwn_target_head_f32(const float* x, int64_t N, int64_t ldx, const int32_t* target_row, int64_t C, const float* W,
+                        const float* bias, float* out, int64_t ldout, int32_t H, int32_t K, int32_t* err_flag,
+                        const int64_t* m_dev, cwn_stream_t stream);
+
+/* Its backward (the autograd of mp/ring_exp_models.py:64), one launch (two beyond 64 complexes):
+ *     dx[r, :] = sum over the complexes c with target_row[c] == r, in complex order, of dlogits[c, :] . W     EVERY r < N
+ *     dW       = sum_c dlogits[c, :]^T x[target_row[c], :]          db = sum_c dlogits[c, :]
+ *   - every row of dx is written by exactly one workgroup (zeros off the target rows: no separate fill); a chunk of 64
+ *     rows finds its targets in the ascending target_row (binary search; up to 4096 complexes one pass over all of it).
+ *   - dW / db: the complexes of a group of 64 are added one after the other in complex order by one thread per element;
+ *     C <= 64 is one group, written straight to dW / db; beyond, every group writes its slice of `workspace`
+ *     (cwn_target_head_bwd_workspace_bytes(C, H, K); 16-byte aligned; 0 bytes for C <= 64) and a second launch adds the
+ *     live groups' slices in group order.  No atomics: the same bits on every run (there is no second, ordered form).
+ *     They are WRITTEN, not accumulated.
+ *   - dx NULL: the data gradient is skipped; dW NULL: the weight gradients are (db needs dW).  dx [N, H] row stride lddx
+ *     (16-byte aligned, lddx % 4 == 0), dW [K, H] contiguous (16-byte aligned), dlogits [C, K] row stride lddl.
+ *   - m_dev as above: complexes in [*m_dev, C) enter nothing.  All N rows of dx are written whatever the count.
+ * Same shapes and error codes (CWN_ERR_WORKSPACE: a workspace smaller than asked for); dx must not alias x or dlogits. */
+size_t cwn_target_head_bwd_workspace_bytes(int64_t C, int32_t H, int32_t K);
+int cwn_target_head_bwd_f32(const float* dlogits, int64_t lddl, const float* x, int64_t N, int64_t ldx,
+                            const int32_t* target_row, int64_t C, const float* W, float* dx, int64_t lddx, float* dW, float* db,
+                            int32_t H, int32_t K, void* workspace, size_t workspace_bytes, const int64_t* m_dev,
+                            cwn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Device-side batching (collate): build the arrays of a ComplexBatch from a dataset that is
