@@ -25,6 +25,7 @@ EXPORTS = ('cwn_abi_version', 'cwn_error_string', 'cwn_target_arch', 'cwn_csr_wo
            'cwn_layernorm_act_f32', 'cwn_layernorm_bwd_workspace_bytes', 'cwn_layernorm_bwd_f32',
            'cwn_oriented_layer_f32', 'cwn_oriented_dz_f32',
            'cwn_target_head_f32', 'cwn_target_head_bwd_f32', 'cwn_target_head_bwd_workspace_bytes',
+           'cwn_linear_many_f64', 'cwn_update_chain_f64',
            'cwn_gemm_tn_f32', 'cwn_gemm_tn_workspace_bytes', 'cwn_adam_f32', 'cwn_adam_dev_f32', 'cwn_loss_f32', 'cwn_loss_cols_f32', 'cwn_embedding_fwd_f32', 'cwn_embedding_bwd_f32', 'cwn_embed_front_f32', 'cwn_head_f32', 'cwn_head_bwd_f32', 'cwn_head_pool_floats', 'cwn_lift_create', 'cwn_lift_size', 'cwn_lift_copy', 'cwn_lift_destroy',
            'cwn_lift_many', 'cwn_lift_many_count', 'cwn_lift_many_lengths', 'cwn_lift_many_copy', 'cwn_lift_many_destroy',
            # the evaluation pass (csrc/cwn_metrics.hip)
@@ -305,6 +306,25 @@ class OrientedDesc(C.Structure):
                 ('w', C.c_int32), ('H', C.c_int32), ('act', C.c_int32), ('w_trans', C.c_int32), ('m_dev', C.c_void_p)]
 
 
+# the float64 dense path (csrc/cwn_dense_f64.hip) = CWN_LINEAR_F64_* / CWN_CHAIN_F64_* / CWN_DENSE_F64_TILE_ROWS
+LINEAR_F64_MAX_DESCS, LINEAR_F64_MAX_WIDTH, CHAIN_F64_MAX_DIMS, CHAIN_F64_MAX_WIDTH, DENSE_F64_TILE_ROWS = 16, 128, 4, 64, 16
+
+
+class LinearDescF64(C.Structure):
+    """cwn_linear_desc_f64: one Y = act(X W^T + bias) of a cwn_linear_many_f64 launch."""
+    _fields_ = [('X', C.c_void_p), ('W', C.c_void_p), ('bias', C.c_void_p), ('Y', C.c_void_p), ('M', C.c_int64),
+                ('ldx', C.c_int64), ('ldw', C.c_int64), ('ldy', C.c_int64), ('K', C.c_int32), ('N', C.c_int32),
+                ('act', C.c_int32), ('reserved', C.c_int32)]
+
+
+class ChainDescF64(C.Structure):
+    """cwn_chain_desc_f64: the update / combine networks of one dimension of a cwn_update_chain_f64 launch."""
+    _fields_ = [('in_up', C.c_void_p), ('in_b', C.c_void_p), ('out', C.c_void_p), ('W', C.c_void_p * 5),
+                ('bias', C.c_void_p * 5), ('scale', C.c_void_p * 5), ('shift', C.c_void_p * 5), ('n', C.c_int64),
+                ('ld_up', C.c_int64), ('ld_b', C.c_int64), ('ld_out', C.c_int64), ('F', C.c_int32), ('H', C.c_int32),
+                ('act', C.c_int32), ('reserved', C.c_int32)]
+
+
 class GemmTnDesc(C.Structure):
     _fields_ = [('dZ', C.c_void_p), ('X', C.c_void_p), ('X2', C.c_void_p), ('in_scale', C.c_void_p),
                 ('in_shift', C.c_void_p), ('in_scale2', C.c_void_p), ('in_shift2', C.c_void_p),
@@ -472,6 +492,10 @@ def lib():
     L.cwn_target_head_bwd_f32.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                           C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t,
                                           C.c_void_p, C.c_void_p]
+    L.cwn_linear_many_f64.restype = C.c_int
+    L.cwn_linear_many_f64.argtypes = [C.POINTER(LinearDescF64), C.c_int, C.c_void_p]
+    L.cwn_update_chain_f64.restype = C.c_int
+    L.cwn_update_chain_f64.argtypes = [C.POINTER(ChainDescF64), C.c_int, C.c_void_p]
     L.cwn_target_head_bwd_workspace_bytes.restype = C.c_size_t
     L.cwn_target_head_bwd_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32]
     L.cwn_adam_dev_f32.restype = C.c_int

@@ -86,6 +86,10 @@ FUSED_CIN_TRAINING = os.environ.get('CWN_FUSED_CIN_TRAINING') != '0'      # Fals
 FUSED_UPDATE_MLP = os.environ.get('CWN_FUSED_UPDATE_MLP') != '0'   # False: the update / combine networks as three grouped GEMM launches
 BLOCKED_TRAIN_FORWARD = os.environ.get('CWN_BLOCKED_TRAIN_FORWARD') != '0'    # the training forward through the blocked kernel too
 BLOCKED_LAYER = os.environ.get('CWN_BLOCKED_LAYER') != '0'   # False: propagate scope as grouped GEMM + CSR aggregation
+# False: the dense parts of a float64 model (SparseCINConv's update / combine networks, the message products, the head's
+# lin1s / lin2) as torch modules -- a rocBLAS dgemm, a bias add and an activation launch per Linear -- instead of the
+# csrc/cwn_dense_f64.hip launches
+FUSED_F64_DENSE = os.environ.get('CWN_FUSED_F64_DENSE') != '0'
 CSR_REUSE = True              # blocked layer kernel: sort a batch's adjacencies once, later layers load the result
 # One workgroup per item and one item per CU at a time: the blocked kernel wins while the items fit the chip
 # a few times over (measured on ZINC-like batches, tools/range_of_use.sh, M cells/s blocked vs CSR path: 256
@@ -238,6 +242,25 @@ def _fold_norm(norm, width: int):
         fold = (scale.contiguous(), shift.contiguous())
     norm._cwn_fold = (key, fold)
     return fold
+
+
+_F64_ACTS = {torch.nn.Identity: 'id', ReLU: 'relu', torch.nn.ELU: 'elu', torch.nn.Tanh: 'tanh', torch.nn.Sigmoid: 'sigmoid'}
+
+
+def _f64_stages(nn, groups: int):
+    """([(Linear, norm), ...], activation name) of a stock Sequential of `groups` (Linear, norm, act) groups whose
+    activation modules are all the same one of the five of models.get_nonlinearity, or None."""
+    if not isinstance(nn, Sequential) or len(nn) != 3 * groups:
+        return None
+    stages, acts = [], set()
+    for i in range(0, len(nn), 3):
+        lin, norm, act = nn[i], nn[i + 1], nn[i + 2]
+        name = _F64_ACTS.get(type(act))
+        if type(lin) is not Linear or name is None or (name == 'elu' and act.alpha != 1.0):
+            return None
+        stages.append((lin, norm))
+        acts.add(name)
+    return (stages, acts.pop()) if len(acts) == 1 else None
 
 
 def _mlp_stages(nn):
@@ -742,15 +765,19 @@ class SparseCINCochainConv(CochainMessagePassing):
         out_boundaries = self.update_boundaries_nn(out_boundaries)
         return self.combine_nn(torch.cat([out_up, out_boundaries], dim=-1))
 
-    def forward_unfused(self, cochain: CochainMessagePassingParams) -> Tensor:
-        """The reference's own sequence (mp/layers.py:184-199) through propagate()."""
+    def aggregate_unfused(self, cochain: CochainMessagePassingParams):
+        """The two aggregated inputs of the update networks, self terms added, through propagate() (mp/layers.py:184-192)."""
         out_up, _, out_boundaries = self.propagate(cochain.up_index, cochain.down_index,
                                                    cochain.boundary_index, x=cochain.x,
                                                    up_attr=cochain.kwargs['up_attr'],
                                                    boundary_attr=cochain.kwargs['boundary_attr'])
         out_up = out_up + (1 + self.eps1) * cochain.x
         out_boundaries = out_boundaries + (1 + self.eps2) * cochain.x
-        return self.finish(out_up, out_boundaries)
+        return out_up, out_boundaries
+
+    def forward_unfused(self, cochain: CochainMessagePassingParams) -> Tensor:
+        """The reference's own sequence (mp/layers.py:184-199) through propagate()."""
+        return self.finish(*self.aggregate_unfused(cochain))
 
     def forward(self, cochain: CochainMessagePassingParams):
         sts = self.streams(cochain)
@@ -770,6 +797,10 @@ def _torch_products(lin, x: Tensor, attr) -> Optional[List[Tensor]]:
     if x.dtype != torch.float64 or lin.in_features != F + src.size(1):
         return None
     W = lin.weight
+    if (FUSED_F64_DENSE and not torch.is_grad_enabled() and x.is_cuda and src.dtype == torch.float64 and W.dtype == torch.float64
+            and max(F, int(src.size(1)), lin.out_features) <= ops._ffi.LINEAR_F64_MAX_WIDTH and x.dim() == src.dim() == 2):
+        # inference: both products in one launch (csrc/cwn_dense_f64.hip), the weight read as its two column slices
+        return ops.linear_many_f64([(x.contiguous(), W[:, :F], lin.bias, None), (src.contiguous(), W[:, F:], None, None)])
     return [torch.nn.functional.linear(x, W[:, :F], lin.bias), torch.nn.functional.linear(src, W[:, F:])]
 
 
@@ -1179,6 +1210,59 @@ class SparseCINConv(torch.nn.Module):
                                   out_scale=folds[2][0][0], out_shift=folds[2][0][1]))
         return ops.run_gemm(gemms, dev)
 
+    def _f64_chain(self, lvl):
+        """(weights, biases, folds, activation) of one dimension's three networks in the order of ops.ChainDim, or None when
+        they are not the stock Linear-norm-act structure with one of the five activations and Identity / eval-mode
+        BatchNorm norms, or are wider than the launch takes."""
+        if type(lvl) is not SparseCINCochainConv:
+            return None
+        got = [_f64_stages(lvl.update_up_nn, 2), _f64_stages(lvl.update_boundaries_nn, 2), _f64_stages(lvl.combine_nn, 1)]
+        if any(g is None for g in got) or len({g[1] for g in got}) != 1:
+            return None
+        stages = got[0][0] + got[1][0] + got[2][0]
+        wmax = ops._ffi.CHAIN_F64_MAX_WIDTH
+        if any(lin.weight.dtype != torch.float64 or lin.out_features > wmax for lin, _ in stages) or stages[0][0].in_features > wmax:
+            return None                  # (hidden 256 of cwn-sr-base.sh: dgemm is the right tool)
+        folds = [_fold_norm(norm, lin.out_features) for lin, norm in stages]
+        if any(f is None for f in folds):
+            return None                  # LayerNorm, a training-mode BatchNorm
+        return [lin.weight for lin, _ in stages], [lin.bias for lin, _ in stages], folds, got[0][1]
+
+    def _dense_f64(self, plans, outs, start: int = 0, cochain_params=None) -> Optional[List[Tensor]]:
+        """The update / combine networks of ALL dimensions of a float64 layer in ONE launch (ops.update_chain_f64,
+        csrc/cwn_dense_f64.hip): five Linear layers per dimension, eval-mode BatchNorm folded, any of the five
+        activations, widths up to 64.  A dimension whose message network has no fused stream (plans[d] is None: the
+        act(Linear(cat)) message of an ELU model) runs its generic propagate first and joins the same launch.
+        Inference only (the condition of `_dense_eval`).  None when it does not apply -- training or a recording
+        autograd, LayerNorm, a passed-in network, widths above 64 (there dgemm is the right tool), CIN++, float32 or CPU
+        features, FUSED_F64_DENSE off -- and the caller runs the torch modules."""
+        if not FUSED_F64_DENSE or torch.is_grad_enabled() or type(self) is not SparseCINConv:
+            return None
+        active = list(range(start, len(plans)))
+        unfused = [d for d in active if plans[d] is None]
+        if not active or len(outs) != 2 * (len(active) - len(unfused)) or len(active) > ops._ffi.CHAIN_F64_MAX_DIMS:
+            return None
+        if unfused and cochain_params is None:
+            return None
+        feats = list(outs) + [cochain_params[d].x for d in unfused]
+        if any(not isinstance(t, Tensor) or t.dtype != torch.float64 or not t.is_cuda for t in feats):
+            return None
+        nets = [self._f64_chain(self.mp_levels[d]) for d in active]
+        if any(net is None for net in nets):
+            return None
+        ins, k = [], 0
+        for d in active:
+            if plans[d] is None:
+                ins.append(self.mp_levels[d].aggregate_unfused(cochain_params[d]))
+            else:
+                ins.append((outs[k], outs[k + 1]))
+                k += 2
+        dims = [ops.ChainDim(in_up=u.contiguous(), in_b=b.contiguous(), weights=net[0], biases=net[1], folds=net[2], act=net[3])
+                for (u, b), net in zip(ins, nets)]
+        if not ops.update_chain_f64_applies(dims):       # (an input of another width than its network: let torch say so)
+            return [self.mp_levels[d].finish(u, b) for d, (u, b) in zip(active, ins)]
+        return ops.update_chain_f64(dims)
+
     def _dense_train(self, plans, outs, start: int = 0) -> Optional[List[Tensor]]:
         """The same networks with autograd and training-mode BatchNorm (batch statistics, running
         statistics updated) as grouped launches forward and backward: cwn_amd/dense_train.py.
@@ -1253,6 +1337,8 @@ class SparseCINConv(torch.nn.Module):
         self.__dict__['_out_drop'], self.__dict__['_out_dropped'] = (float(out_dropout) if self.training else 0.0), False
         plans, outs = self.propagate_all(*cochain_params, start_to_process=start_to_process)
         dense = self._dense_eval(plans, outs, start_to_process)
+        if dense is None:
+            dense = self._dense_f64(plans, outs, start_to_process, cochain_params)
         if dense is None:
             dense = self._dense_train(plans, outs, start_to_process)
         if dense is None:

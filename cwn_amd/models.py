@@ -266,11 +266,18 @@ class _SparseCINStack(torch.nn.Module):
         lins = [self.lin1s[d] for d in self.readout_dims]
         dense_head = (self.nonlinearity == 'relu' and xs[0].is_cuda and xs[0].dtype == torch.float32     # (fp32 MFMA GEMMs)
                       and max(l.in_features for l in lins + [self.lin2]) <= ops.GEMM_MAX_K)
+        # a float64 model in inference: the lin1s with their activation in ONE launch, lin2 in one more (csrc/cwn_dense_f64.hip)
+        f64_head = (layers.FUSED_F64_DENSE and not torch.is_grad_enabled() and self.nonlinearity in ops.ACT_CODES
+                    and all(x.is_cuda and x.dtype == torch.float64 and x.dim() == 2 for x in xs)
+                    and all(l.weight.dtype == torch.float64 and max(l.in_features, l.out_features) <= _ffi.LINEAR_F64_MAX_WIDTH
+                            for l in lins + [self.lin2]))
         if self.apply_dropout_before == 'lin1':
             xs = [ops.dropout(x, self.dropout_rate, self.training) for x in xs]
         if dense_head:     # lin1s of all dimensions (+ReLU) in ONE grouped MFMA launch
             new_xs = ops.gemm_many([ops.Gemm(X=x, W=l.weight, bias=l.bias, relu=True)
                                     for x, l in zip(xs, lins)])
+        elif f64_head:
+            new_xs = ops.linear_many_f64([(x.contiguous(), l.weight, l.bias, self.nonlinearity) for x, l in zip(xs, lins)])
         else:
             new_xs = [act(l(x)) for x, l in zip(xs, lins)]
         if self.apply_dropout_before == 'final_readout':
@@ -284,6 +291,8 @@ class _SparseCINStack(torch.nn.Module):
             x = ops.dropout(x, self.dropout_rate, self.training)
         if dense_head:
             x, = ops.gemm_many([ops.Gemm(X=x, W=self.lin2.weight, bias=self.lin2.bias)])
+        elif f64_head:
+            x, = ops.linear_many_f64([(x.contiguous(), self.lin2.weight, self.lin2.bias, None)])
         else:
             x = self.lin2(x)
         if include_partial:

@@ -2063,6 +2063,155 @@ def target_head(x: Tensor, target_rows: Tensor, weight: Tensor, bias: Optional[T
 
 
 # ------------------------------------------------------------------------------------------------
+# The float64 dense path (csrc/cwn_dense_f64.hip): the Linear layers of a double model, inference only
+# ------------------------------------------------------------------------------------------------
+ACT_CODES = {'id': _ffi.ACT_ID, 'relu': _ffi.ACT_RELU, 'elu': _ffi.ACT_ELU, 'tanh': _ffi.ACT_TANH, 'sigmoid': _ffi.ACT_SIGMOID}
+
+
+def _act_code(act) -> int:
+    if act is None:
+        return _ffi.ACT_ID
+    code = ACT_CODES.get(act, act) if isinstance(act, str) else act
+    if not isinstance(code, int) or not _ffi.ACT_ID <= code <= _ffi.ACT_SIGMOID:
+        raise ValueError(f'unknown activation {act!r}: one of {sorted(ACT_CODES)} or a CWN_ACT_* code')
+    return code
+
+
+def _f64rows(t: Optional[Tensor], name: str, dim: int = 2) -> Optional[Tensor]:
+    """An operand of the float64 dense kernels: float64, on the GPU, rows contiguous (a row stride is allowed)."""
+    if t is None:
+        return None
+    if not isinstance(t, Tensor) or t.dtype != torch.float64:
+        raise TypeError(f'{name} must be float64 (got {getattr(t, "dtype", type(t).__name__)}): this kernel computes in fp64 only '
+                        '(float32 runs through the MFMA launches: gemm_many, update_mlp)')
+    if not t.is_cuda:
+        raise TypeError(f'{name} must be a float64 tensor on the GPU (got {t.dtype} on {t.device})')
+    if t.dim() != dim or (t.numel() and t.stride(-1) != 1) or (dim == 2 and t.size(0) > 1 and t.stride(0) < t.size(1)):
+        raise TypeError(f'{name} must be a {dim}-D float64 tensor with contiguous rows (got {t.dtype}, shape {tuple(t.shape)}, '
+                        f'strides {tuple(t.stride())})')
+    return t
+
+
+def _ld(t: Tensor) -> int:
+    return int(t.stride(0)) if t.size(0) > 1 else int(t.size(1))
+
+
+def linear_many_f64(items) -> List[Tensor]:
+    """[act(x @ weight.T + bias) for (x, weight, bias, act) in items] in float64 from ONE launch (16 products at most per
+    launch; a longer list takes more).  x [M, K] and weight [N, K] may be row-strided views -- the two column slices
+    W[:, :F], W[:, F:] of a message weight are -- with 1 <= K, N <= 128 and any M >= 0; bias [N] or None; act one of
+    'id', 'relu', 'elu', 'tanh', 'sigmoid' (or its CWN_ACT_* code, None = 'id').  Inference only: nothing is recorded
+    for autograd.  Each output element is one fma chain over k in ascending order, so a row's result depends on that
+    row and the weights alone (include/cwn_hip.h).  Anything but float64 GPU tensors is a TypeError."""
+    descs, outs, dev = [], [], None
+    for i, (x, w, b, act) in enumerate(items):
+        x, w, b = _f64rows(x, f'x[{i}]'), _f64rows(w, f'weight[{i}]'), _f64rows(b, f'bias[{i}]', 1)
+        M, K = int(x.size(0)), int(x.size(1))
+        N = int(w.size(0))
+        if int(w.size(1)) != K or (b is not None and b.numel() != N):
+            raise ValueError(f'product {i}: x {tuple(x.shape)}, weight {tuple(w.shape)}, bias {None if b is None else tuple(b.shape)}')
+        if not (1 <= K <= _ffi.LINEAR_F64_MAX_WIDTH and 1 <= N <= _ffi.LINEAR_F64_MAX_WIDTH):
+            raise ValueError(f'product {i}: widths K = {K}, N = {N} outside [1, {_ffi.LINEAR_F64_MAX_WIDTH}]')
+        dev = x.device
+        y = torch.empty(M, N, dtype=torch.float64, device=dev)
+        outs.append(y)
+        descs.append(_ffi.LinearDescF64(X=x.data_ptr(), W=w.data_ptr(), bias=_ffi.ptr(b), Y=y.data_ptr(), M=M, ldx=_ld(x),
+                                        ldw=_ld(w), ldy=N, K=K, N=N, act=_act_code(act)))
+    for lo in range(0, len(descs), _ffi.LINEAR_F64_MAX_DESCS):
+        part = descs[lo:lo + _ffi.LINEAR_F64_MAX_DESCS]
+        _ffi.check(_ffi.lib().cwn_linear_many_f64((_ffi.LinearDescF64 * len(part))(*part), len(part), _ffi.stream_ptr(dev)),
+                   'cwn_linear_many_f64')
+    return outs
+
+
+@dataclass
+class ChainDim:
+    """One dimension of `update_chain_f64`: the two aggregated inputs [n, F] (self terms added), the weights and biases of
+    update_up_nn[0], update_up_nn[3], update_boundaries_nn[0], update_boundaries_nn[3], combine_nn[0] in that order, per
+    stage a (scale, shift) pair of [H] tensors or (None, None) (layers._fold_norm), and the activation of all five stages.
+    `out`: an output buffer [>= n, H] of the caller's (only its first n rows are written), or None."""
+    in_up: Tensor
+    in_b: Tensor
+    weights: Sequence[Tensor]
+    biases: Sequence[Optional[Tensor]]
+    folds: Sequence[Tuple[Optional[Tensor], Optional[Tensor]]]
+    act: object = 'relu'
+    out: Optional[Tensor] = None
+
+
+def _chain_shapes(d: ChainDim) -> Optional[Tuple[int, int, int]]:
+    """(n, F, H) when the shapes of `d` are those of a SparseCINConv dimension, else None."""
+    ts = [d.in_up, d.in_b] + list(d.weights)
+    if len(d.weights) != 5 or len(d.biases) != 5 or len(d.folds) != 5 or not all(isinstance(t, Tensor) and t.dim() == 2 for t in ts):
+        return None
+    n, F = int(d.in_up.size(0)), int(d.in_up.size(1))
+    H = int(d.weights[0].size(0))
+    want = [(H, F), (H, H), (H, F), (H, H), (H, 2 * H)]
+    if tuple(d.in_b.shape) != (n, F) or [tuple(w.shape) for w in d.weights] != want:
+        return None
+    vecs = list(d.biases) + [t for f in d.folds for t in f]
+    if any(t is not None and tuple(t.shape) != (H,) for t in vecs) or any((s is None) != (t is None) for s, t in d.folds):
+        return None
+    if d.out is not None and (d.out.dim() != 2 or d.out.size(0) < n or d.out.size(1) != H):
+        return None
+    return n, F, H
+
+
+def update_chain_f64_applies(dims: Sequence[ChainDim]) -> bool:
+    """Does cwn_update_chain_f64 take these dimensions?  1 to 4 of them, every tensor float64 on the GPU with contiguous
+    rows (the weights contiguous), 1 <= F, H <= 64, the five-stage shapes of a SparseCINConv dimension, a known activation."""
+    if not 1 <= len(dims) <= _ffi.CHAIN_F64_MAX_DIMS:
+        return False
+    for d in dims:
+        shp = _chain_shapes(d)
+        if shp is None or not (1 <= shp[1] <= _ffi.CHAIN_F64_MAX_WIDTH and 1 <= shp[2] <= _ffi.CHAIN_F64_MAX_WIDTH):
+            return False
+        ts = [d.in_up, d.in_b, d.out] + list(d.weights) + list(d.biases) + [t for f in d.folds for t in f]
+        if not all(t is None or (t.dtype == torch.float64 and t.is_cuda and (t.numel() == 0 or t.stride(-1) == 1)) for t in ts):
+            return False
+        if not all(w.is_contiguous() for w in d.weights):
+            return False
+        if isinstance(d.act, str) and d.act not in ACT_CODES:
+            return False
+    return True
+
+
+def update_chain_f64(dims: Sequence[ChainDim]) -> List[Tensor]:
+    """act(aff(combine_nn[0](cat(update_up_nn(in_up), update_boundaries_nn(in_b))))) of every dimension of a SparseCINConv
+    layer (mp/layers.py:193-199) in ONE float64 launch -- five Linear layers per dimension with everything between the
+    two inputs and the output in LDS and registers (csrc/cwn_dense_f64.hip).  Returns the outputs [n, H] per dimension.
+    Inference only; the arithmetic is row-independent (see `linear_many_f64`).  Anything but float64 GPU tensors is a
+    TypeError, shapes the launch does not take (`update_chain_f64_applies`) a ValueError."""
+    descs, outs, dev = [], [], None
+    for i, d in enumerate(dims):
+        named = [('in_up', d.in_up), ('in_b', d.in_b)] + [(f'weights[{s}]', w) for s, w in enumerate(d.weights)]
+        for name, t in named:
+            _f64rows(t, f'dims[{i}].{name}')
+        for name, t in [(f'biases[{s}]', b) for s, b in enumerate(d.biases)] + \
+                       [(f'folds[{s}]', t) for s, f in enumerate(d.folds) for t in f]:
+            _f64rows(t, f'dims[{i}].{name}', 1)
+        _f64rows(d.out, f'dims[{i}].out')
+    if not update_chain_f64_applies(dims):
+        raise ValueError('update_chain_f64: 1 to 4 dimensions of the five-stage shapes [H, F], [H, H], [H, F], [H, H], [H, 2H] '
+                         f'with 1 <= F, H <= {_ffi.CHAIN_F64_MAX_WIDTH}, contiguous weights, a known activation')
+    for d in dims:
+        n, F, H = _chain_shapes(d)
+        dev = d.in_up.device
+        out = torch.empty(n, H, dtype=torch.float64, device=dev) if d.out is None else d.out[:n]
+        outs.append(out)
+        D = _ffi.ChainDescF64(in_up=d.in_up.data_ptr(), in_b=d.in_b.data_ptr(), out=out.data_ptr(), n=n, ld_up=_ld(d.in_up),
+                              ld_b=_ld(d.in_b), ld_out=int(d.out.stride(0)) if d.out is not None and d.out.size(0) > 1 else H,
+                              F=F, H=H, act=_act_code(d.act))
+        for s in range(5):
+            D.W[s], D.bias[s] = d.weights[s].data_ptr(), _ffi.ptr(d.biases[s])
+            D.scale[s], D.shift[s] = _ffi.ptr(d.folds[s][0]), _ffi.ptr(d.folds[s][1])
+        descs.append(D)
+    _ffi.check(_ffi.lib().cwn_update_chain_f64((_ffi.ChainDescF64 * len(descs))(*descs), len(descs), _ffi.stream_ptr(dev)),
+               'cwn_update_chain_f64')
+    return outs
+
+
+# ------------------------------------------------------------------------------------------------
 # gemm_many + aggregate_many of one propagate step as ONE autograd node
 # ------------------------------------------------------------------------------------------------
 FUSED_PROPAGATE_NODE = os.environ.get('CWN_FUSED_PROPAGATE_NODE') != '0'     # A/B: '0' keeps the two nodes

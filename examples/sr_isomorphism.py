@@ -5,8 +5,11 @@ the ring lift (rings up to 6) of each graph and of a vertex-relabelled copy, in 
 torch.set_default_dtype(torch.float64) because sum aggregation reaches 1e8 without a norm layer, and two isomorphic complexes
 must land within 0.01 of each other (torch.pdist) while non-isomorphic ones are told apart.
 
-Every gather and segmented reduce of the float64 model is a launch of csrc/cwn_aggregate_f64.hip; the dense parts are
-torch.nn.Linear (rocBLAS dgemm).
+Every gather and segmented reduce of the float64 model is a launch of csrc/cwn_aggregate_f64.hip.  The dense parts are
+launches of csrc/cwn_dense_f64.hip: per layer ONE launch for the update and combine networks of all three dimensions, and
+two for the head (the lin1s with their activation, lin2); its arithmetic is row-independent, so a complex gets the same
+bits whatever else shares its batch.  The ELU(Linear(cat)) message itself still runs as torch modules through the generic
+propagate.  CWN_FUSED_F64_DENSE=0 puts every Linear back on torch.nn.Linear (rocBLAS dgemm).
 
     python examples/sr_isomorphism.py [seed]        (needs an MI355X)
 """

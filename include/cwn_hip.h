@@ -1181,6 +1181,77 @@ int cwn_target_head_bwd_f32(const float* dlogits, int64_t lddl, const float* x, 
                             cwn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The float64 dense path (csrc/cwn_dense_f64.hip): the Linear layers of a double model, inference only.
+ *
+ * The strongly-regular-graph experiments (exp/test_sr.py: SparseCIN in double, hidden 16, batches of 8 graphs) put
+ * matrices of a few hundred rows by 16 columns through five Linear layers per dimension and layer: as torch modules
+ * that is a dgemm, a bias add and an activation launch each, every one far below a launch's own cost in useful work.
+ *
+ * Arithmetic of both entry points: an output element is ONE chain of fma() over k in ascending order starting at 0,
+ * then + bias, then * scale + shift (one fma, when given), then the activation -- plain vector FP64, no matrix cores,
+ * no split of K.  The value of a row depends on that row of the input and on the weights alone: not on its place in
+ * its tile, on the tile's place in the grid, on the number of rows, or on the other products / dimensions of the
+ * launch ("the same complex in any batch gives the same bits", which a dgemm picked by row count does not promise).
+ *
+ * Both launchers validate every descriptor before the first HIP call, never allocate and never synchronise; the row
+ * counts are host counts (the float64 path has no static batches: no m_dev).  Pointers must be 8-byte aligned
+ * (CWN_ERR_ALIGN); more than INT32_MAX tiles: CWN_ERR_TOO_LARGE.
+ * ------------------------------------------------------------------------------------------ */
+#define CWN_LINEAR_F64_MAX_DESCS 16     /* products of one cwn_linear_many_f64 launch */
+#define CWN_LINEAR_F64_MAX_WIDTH 128    /* K and N of a product */
+#define CWN_CHAIN_F64_MAX_DIMS 4        /* dimensions of one cwn_update_chain_f64 launch */
+#define CWN_CHAIN_F64_MAX_WIDTH 64      /* F and H of a dimension */
+#define CWN_DENSE_F64_TILE_ROWS 16      /* rows a workgroup owns, in both kernels */
+
+/* Y = act(X W^T + bias): X [M, K] row stride ldx, W [N, K] row stride ldw (a column slice W[:, a:b] of a wider
+ * weight is ldw > K), bias [N] or NULL, Y [M, N] row stride ldy.  M >= 0 (0: the product writes nothing and its
+ * pointers are not looked at), 1 <= K, N <= 128, strides at least the row's width, act a CWN_ACT_* code. */
+typedef struct cwn_linear_desc_f64 {
+    const double* X;
+    const double* W;
+    const double* bias;
+    double* Y;
+    int64_t M, ldx, ldw, ldy;
+    int32_t K, N;
+    int32_t act;               /* CWN_ACT_* */
+    int32_t reserved;
+} cwn_linear_desc_f64;
+
+/* n products (1 <= n <= CWN_LINEAR_F64_MAX_DESCS) in ONE launch: a workgroup owns 16 rows of one product, the tiles
+ * of all products form one grid.  CWN_ERR_BAD_ARG: descs NULL, n outside the range, M < 0, a width outside [1, 128],
+ * a stride below its width, an unknown act, a NULL X / W / Y with M > 0. */
+int cwn_linear_many_f64(const cwn_linear_desc_f64* descs_host, int n, cwn_stream_t stream);
+
+/* The update and combine networks of ONE dimension of a SparseCINConv layer (mp/layers.py:193-199):
+ *     up  = act(aff1(L1(act(aff0(L0(in_up))))))        L0 = update_up_nn[0]          [H, F], L1 = update_up_nn[3] [H, H]
+ *     bd  = act(aff3(L3(act(aff2(L2(in_b))))))         L2 = update_boundaries_nn[0], L3 = update_boundaries_nn[3]
+ *     out = act(aff4(L4(cat(up, bd))))                 L4 = combine_nn[0]            [H, 2H]
+ * in_up / in_b [n, F] are the two aggregated inputs with their self terms already added; W[i] are contiguous
+ * row-major weights, bias[i] [H] or NULL; scale[i] / shift[i] [H] a per-column affine (an eval-mode BatchNorm folded),
+ * both NULL for Identity; out [n, H].  1 <= F, H <= 64, any integer. */
+typedef struct cwn_chain_desc_f64 {
+    const double* in_up;
+    const double* in_b;
+    double* out;
+    const double* W[5];
+    const double* bias[5];
+    const double* scale[5];
+    const double* shift[5];
+    int64_t n, ld_up, ld_b, ld_out;
+    int32_t F, H;
+    int32_t act;               /* CWN_ACT_*, the one activation of all five stages */
+    int32_t reserved;
+} cwn_chain_desc_f64;
+
+/* All dimensions of a layer (1 <= n_dims <= 4) in ONE launch.  A workgroup owns 16 rows of one dimension: it loads
+ * them of both inputs into LDS, stages one weight at a time (transposed) in LDS, and runs the five stages with the
+ * combine stage reading the two branch results as the two halves of K -- no concatenation, nothing but `out` written.
+ * CWN_ERR_BAD_ARG: descs NULL, n_dims outside the range, n < 0, F or H outside [1, 64], a stride below its width, an
+ * unknown act, scale without shift (or the reverse), a NULL in_up / in_b / out / W[i] with n > 0.  n == 0: the
+ * dimension writes nothing. */
+int cwn_update_chain_f64(const cwn_chain_desc_f64* descs_host, int n_dims, cwn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Device-side batching (collate): build the arrays of a ComplexBatch from a dataset that is
  * resident in HBM in packed form, with ONE launch.
  *
