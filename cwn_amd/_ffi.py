@@ -26,6 +26,7 @@ EXPORTS = ('cwn_abi_version', 'cwn_error_string', 'cwn_target_arch', 'cwn_csr_wo
            'cwn_oriented_layer_f32', 'cwn_oriented_dz_f32',
            'cwn_target_head_f32', 'cwn_target_head_bwd_f32', 'cwn_target_head_bwd_workspace_bytes',
            'cwn_linear_many_f64', 'cwn_update_chain_f64',
+           'cwn_aggregate_act_f32', 'cwn_aggregate_act_f64',
            'cwn_gemm_tn_f32', 'cwn_gemm_tn_workspace_bytes', 'cwn_adam_f32', 'cwn_adam_dev_f32', 'cwn_loss_f32', 'cwn_loss_cols_f32', 'cwn_embedding_fwd_f32', 'cwn_embedding_bwd_f32', 'cwn_embed_front_f32', 'cwn_head_f32', 'cwn_head_bwd_f32', 'cwn_head_pool_floats', 'cwn_lift_create', 'cwn_lift_size', 'cwn_lift_copy', 'cwn_lift_destroy',
            'cwn_lift_many', 'cwn_lift_many_count', 'cwn_lift_many_lengths', 'cwn_lift_many_copy', 'cwn_lift_many_destroy',
            # the evaluation pass (csrc/cwn_metrics.hip)
@@ -52,6 +53,19 @@ class AggDesc(C.Structure):
                 ('msg_op', C.c_int32), ('reduce', C.c_int32),
                 ('long_cap', C.c_int32), ('flags', C.c_int32),
                 ('self_x2', C.c_void_p), ('eps2', C.c_void_p), ('m_dev', C.c_void_p)]
+
+
+class AggActDesc(C.Structure):
+    """cwn_agg_act_desc and cwn_agg_act_desc_f64 (include/cwn_hip.h): one layout, every data pointer is a void*."""
+    _fields_ = [('rowptr', C.c_void_p), ('ia', C.c_void_p), ('ib', C.c_void_p),
+                ('A', C.c_void_p), ('B', C.c_void_p), ('self_x', C.c_void_p),
+                ('eps', C.c_void_p), ('out', C.c_void_p),
+                ('long_rows', C.c_void_p), ('n_long', C.c_void_p),
+                ('n_dst', C.c_int64), ('F', C.c_int32), ('act', C.c_int32),
+                ('long_cap', C.c_int32), ('flags', C.c_int32)]
+
+
+AggActDescF64 = AggActDesc
 
 
 class LongRowsDesc(C.Structure):
@@ -496,6 +510,10 @@ def lib():
     L.cwn_linear_many_f64.argtypes = [C.POINTER(LinearDescF64), C.c_int, C.c_void_p]
     L.cwn_update_chain_f64.restype = C.c_int
     L.cwn_update_chain_f64.argtypes = [C.POINTER(ChainDescF64), C.c_int, C.c_void_p]
+    L.cwn_aggregate_act_f32.restype = C.c_int
+    L.cwn_aggregate_act_f32.argtypes = [C.POINTER(AggActDesc), C.c_int, C.c_void_p]
+    L.cwn_aggregate_act_f64.restype = C.c_int
+    L.cwn_aggregate_act_f64.argtypes = [C.POINTER(AggActDescF64), C.c_int, C.c_void_p]
     L.cwn_target_head_bwd_workspace_bytes.restype = C.c_size_t
     L.cwn_target_head_bwd_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32]
     L.cwn_adam_dev_f32.restype = C.c_int
@@ -651,6 +669,22 @@ def aggregate(descs: Sequence[AggDesc], device, dtype: torch.dtype = torch.float
     for i in range(0, len(descs), MAX_DESCS):
         chunk = descs[i:i + MAX_DESCS]
         arr = (AggDesc * len(chunk))(*chunk)
+        check(fn(arr, len(chunk), s), name)
+
+
+def aggregate_act(descs: Sequence[AggActDesc], device, dtype: torch.dtype = torch.float32) -> None:
+    """The activated two-operand message (csrc/cwn_aggregate_act.hip): one kernel launch for up to MAX_DESCS descriptors,
+    more are split into several calls.  Every operand of every descriptor has the one `dtype`.  Row counts are host
+    counts: the descriptor has no m_dev, so nothing is looked up in DYN_ROWS."""
+    L = lib()
+    s = stream_ptr(device)
+    if dtype not in FLOAT_DTYPES:
+        raise TypeError(f'aggregate_act computes in float32 or float64, not {dtype}')
+    name = 'cwn_aggregate_act_f32' if dtype == torch.float32 else 'cwn_aggregate_act_f64'
+    fn = getattr(L, name)
+    for i in range(0, len(descs), MAX_DESCS):
+        chunk = descs[i:i + MAX_DESCS]
+        arr = (AggActDesc * len(chunk))(*chunk)
         check(fn(arr, len(chunk), s), name)
 
 

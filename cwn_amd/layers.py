@@ -80,6 +80,32 @@ def _is_cat_linear_relu(nn) -> bool:
             and isinstance(nn[1], Linear) and isinstance(nn[2], ReLU))
 
 
+# the activation modules other than ReLU that models.get_nonlinearity hands out, by their ops.ACT_CODES name
+_MESSAGE_ACTS = {torch.nn.ELU: 'elu', torch.nn.Tanh: 'tanh', torch.nn.Sigmoid: 'sigmoid', torch.nn.Identity: 'id'}
+
+
+def _cat_linear_act(nn) -> Optional[str]:
+    """The activation's name when `nn` is Sequential(Catter, Linear, ELU | Tanh | Sigmoid | Identity), else None."""
+    if not (isinstance(nn, Sequential) and len(nn) == 3 and isinstance(nn[0], Catter) and isinstance(nn[1], Linear)):
+        return None
+    name = _MESSAGE_ACTS.get(type(nn[2]))
+    return None if name == 'elu' and nn[2].alpha != 1.0 else name
+
+
+# A coboundary message act(Linear(cat(x_j, up_attr))) with an activation other than ReLU as two per-cell products and one
+# cwn_aggregate_act_f32 / _f64 launch (csrc/cwn_aggregate_act.hip; inference only) instead of the generic propagate (two row
+# gathers, cat, a per-entry product, the activation, the segmented reduce).  True / False: for every dtype / for none
+# (CWN_FUSED_ACT_MESSAGE=1 / =0); a set of dtypes: for those -- the default, FUSED_ACT_MESSAGE_DEFAULT, holds the dtypes at
+# which the route has measured faster than the generic propagate by more than the run-to-run spread of both forms
+# (tools/bench_act_message.py, profiles/act_message.md: float64 1.32 against 1.92 ms for the SR forward; the float32 forward
+# has no figure yet, so float32 stays off unless asked for).
+FUSED_ACT_MESSAGE_DEFAULT = frozenset({torch.float64})
+FUSED_ACT_MESSAGE = {'0': False, '1': True}.get(os.environ.get('CWN_FUSED_ACT_MESSAGE'), FUSED_ACT_MESSAGE_DEFAULT)
+
+
+def _act_message_on(dtype) -> bool:
+    on = FUSED_ACT_MESSAGE
+    return dtype in on if isinstance(on, (set, frozenset)) else bool(on)
 FUSED_DENSE_TRAINING = True   # set False to run the update / combine networks as torch modules
 FUSED_CINPP_COMBINE = os.environ.get('CWN_FUSED_CINPP_COMBINE') != '0'    # False: CINppConv's combine network as torch modules behind the fused branches
 FUSED_CIN_TRAINING = os.environ.get('CWN_FUSED_CIN_TRAINING') != '0'      # False: CINCochainConv's training forward on the generic path
@@ -668,6 +694,11 @@ class SparseCINCochainConv(CochainMessagePassing):
             return 'first'
         if _is_cat_linear_relu(self.msg_up_nn):
             return 'cat_linear_relu'
+        # the same split behind another activation: a launch without a backward and without a device-side row count, so
+        # a recording autograd and a static batch see the 'custom' network they saw before
+        if (FUSED_ACT_MESSAGE and not torch.is_grad_enabled() and not _ffi_dyn()
+                and _cat_linear_act(self.msg_up_nn) is not None and _act_message_on(self.msg_up_nn[1].weight.dtype)):
+            return 'cat_linear_act'
         return 'custom'
 
     def gemm_specs(self, cochain: CochainMessagePassingParams) -> List[ops.Gemm]:
@@ -675,7 +706,7 @@ class SparseCINCochainConv(CochainMessagePassing):
         Y2 = X_{d+1} W[:, F:]^T ([] when the message network is another form or there is no upper
         adjacency).  SparseCINConv groups the specs of all dimensions into one MFMA launch."""
         x, up_attr = cochain.x, cochain.kwargs.get('up_attr')
-        if (cochain.up_index is None or up_attr is None or self._up_kind() != 'cat_linear_relu'
+        if (cochain.up_index is None or up_attr is None or self._up_kind() not in ('cat_linear_relu', 'cat_linear_act')
                 or (self.aggr_up or 'add') != 'add' or x.dtype != torch.float32):
             return []                    # (float64: _torch_products, behind the same fused stream)
         lin = self.msg_up_nn[1]
@@ -695,15 +726,20 @@ class SparseCINCochainConv(CochainMessagePassing):
         if kind == 'first':
             return ops.Stream(adj=adj, n_dst=adj.n_dst, width=int(x.size(1)), A=x, self_x=self_x,
                               eps=eps, reduce=self.aggr_up or 'add')
-        if kind == 'cat_linear_relu' and up_attr is not None and (self.aggr_up or 'add') == 'add':
+        if kind in ('cat_linear_relu', 'cat_linear_act') and up_attr is not None and (self.aggr_up or 'add') == 'add':
+            relu = kind == 'cat_linear_relu'
             if ys is None:
                 specs = SparseCINCochainConv.gemm_specs(self, CochainMessagePassingParams(x, adj, up_attr=up_attr))
-                ys = ops.gemm_many(specs) if specs else _torch_products(self.msg_up_nn[1], x, up_attr)
+                ys = ops.gemm_many(specs) if specs else _torch_products(self.msg_up_nn[1], x, up_attr, part_of_message=not relu)
                 if ys is None:
                     return None
             _, mode = _attr_operand(up_attr)
-            return ops.Stream(adj=adj, n_dst=adj.n_dst, width=int(ys[0].size(1)), A=ys[0], B=ys[1],
-                              msg_op=ops.MSG_RELU_A_PLUS_B, ib_mode=mode, self_x=self_x, eps=eps)
+            if relu:
+                return ops.Stream(adj=adj, n_dst=adj.n_dst, width=int(ys[0].size(1)), A=ys[0], B=ys[1],
+                                  msg_op=ops.MSG_RELU_A_PLUS_B, ib_mode=mode, self_x=self_x, eps=eps)
+            # act(Y1[src] + Y2[shared]) summed: the stream of cwn_aggregate_act_f32 / _f64
+            return ops.Stream(adj=adj, n_dst=adj.n_dst, width=int(ys[0].size(1)), A=ys[0], B=ys[1], msg_op=ops.MSG_A_PLUS_B,
+                              act=_cat_linear_act(self.msg_up_nn), ib_mode=mode, self_x=self_x, eps=eps)
         return None
 
     def _boundary_fusable(self) -> bool:
@@ -787,11 +823,12 @@ class SparseCINCochainConv(CochainMessagePassing):
         return self.finish(out_up, out_boundaries)
 
 
-def _torch_products(lin, x: Tensor, attr) -> Optional[List[Tensor]]:
-    """Y1 = X W[:, :F]^T + b and Y2 = X_attr W[:, F:]^T of a ReLU(Linear(cat(x_j, attr))) message for features the fp32 MFMA
+def _torch_products(lin, x: Tensor, attr, part_of_message: bool = False) -> Optional[List[Tensor]]:
+    """Y1 = X W[:, :F]^T + b and Y2 = X_attr W[:, F:]^T of an act(Linear(cat(x_j, attr))) message for features the fp32 MFMA
     GEMMs do not take (float64): the same split on torch.nn.functional.linear (rocBLAS), so that the message still runs as
-    the fused CWN_MSG_RELU_A_PLUS_B stream -- in float64 -- and no per-entry matrix is materialised.  None when the split
-    does not apply (float32 features reach here only after gemm_specs has refused their shape)."""
+    a fused stream -- in float64 -- and no per-entry matrix is materialised.  None when the split does not apply (float32
+    features reach here only after gemm_specs has refused their shape).  `part_of_message`: the products of the activated
+    message ('cat_linear_act') go to the launcher behind ops.linear_many_f64, not through the public function."""
     F = int(x.size(1))
     src, _ = _attr_operand(attr)
     if x.dtype != torch.float64 or lin.in_features != F + src.size(1):
@@ -800,7 +837,8 @@ def _torch_products(lin, x: Tensor, attr) -> Optional[List[Tensor]]:
     if (FUSED_F64_DENSE and not torch.is_grad_enabled() and x.is_cuda and src.dtype == torch.float64 and W.dtype == torch.float64
             and max(F, int(src.size(1)), lin.out_features) <= ops._ffi.LINEAR_F64_MAX_WIDTH and x.dim() == src.dim() == 2):
         # inference: both products in one launch (csrc/cwn_dense_f64.hip), the weight read as its two column slices
-        return ops.linear_many_f64([(x.contiguous(), W[:, :F], lin.bias, None), (src.contiguous(), W[:, F:], None, None)])
+        launch = ops._linear_many_f64 if part_of_message else ops.linear_many_f64
+        return launch([(x.contiguous(), W[:, :F], lin.bias, None), (src.contiguous(), W[:, F:], None, None)])
     return [torch.nn.functional.linear(x, W[:, :F], lin.bias), torch.nn.functional.linear(src, W[:, F:])]
 
 

@@ -143,6 +143,69 @@ def run_aggregate(specs: Sequence[AggSpec], device) -> List[Tensor]:
 
 
 @dataclass
+class AggActSpec:
+    """One descriptor of cwn_aggregate_act_f32 / cwn_aggregate_act_f64: out = sum_p act(A[ia[p]] + B[ib[p]]) + (1 + eps)
+    self_x.  `ia` / `ib` are int32 tensors in CSR order, B has the width of A, `act` is a CWN_ACT_* code."""
+    adj: Optional[Adjacency]
+    n_dst: int
+    F: int
+    act: int
+    A: Optional[Tensor] = None
+    ia: Optional[Tensor] = None
+    B: Optional[Tensor] = None
+    ib: Optional[Tensor] = None
+    self_x: Optional[Tensor] = None
+    eps: Optional[Tensor] = None
+    out: Optional[Tensor] = None
+    dtype: Optional[torch.dtype] = None
+
+    def resolve_dtype(self) -> torch.dtype:
+        if self.dtype is None:
+            self.dtype = _common_dtype([('A', self.A), ('B', self.B), ('self_x', self.self_x), ('out', self.out)])
+        return self.dtype
+
+    def desc(self) -> _ffi.AggActDesc:
+        absent = self.adj is None or self.adj.n_entries == 0
+        esize = 8 if self.resolve_dtype() == torch.float64 else 4
+        small = ALLOW_SMALL_OPERANDS and all(t is None or t.numel() * esize < (1 << 32) for t in (self.A, self.B))
+        return _ffi.AggActDesc(
+            flags=AGG_SMALL_OPERANDS if small else 0,
+            rowptr=None if absent else self.adj.rowptr.data_ptr(),
+            ia=_ffi.ptr(self.ia), ib=_ffi.ptr(self.ib), A=_ffi.ptr(self.A), B=_ffi.ptr(self.B),
+            self_x=_ffi.ptr(self.self_x), eps=_ffi.ptr(self.eps), out=self.out.data_ptr(),
+            long_rows=None if absent else _ffi.ptr(self.adj.long_rows),
+            n_long=None if absent else _ffi.ptr(self.adj.n_long),
+            long_cap=0 if absent else self.adj.long_cap,
+            n_dst=self.n_dst, F=self.F, act=self.act)
+
+
+def run_aggregate_act(specs: Sequence[AggActSpec], device) -> List[Tensor]:
+    """Raw launch of the activated message (no autograd): allocates missing outputs, ONE kernel per <= 8 descriptors of one
+    dtype.  Row counts are host counts: the launch has no device-side row count, so it refuses to run under
+    `_ffi.dynamic_rows` (no static batch reaches it)."""
+    if _ffi.DYN_ROWS:
+        raise _ffi.CwnError('cwn_aggregate_act_* has no device-side row count: it does not serve static batches')
+    for s in specs:
+        if s.dtype is not None and s.dtype not in _ffi.FLOAT_DTYPES:
+            raise TypeError(f'aggregate_act computes in float32 or float64, not {s.dtype}')
+        if s.out is None:
+            s.out = torch.empty(s.n_dst, s.F, dtype=s.resolve_dtype(), device=device)
+    live = [s for s in specs if s.n_dst > 0]
+    if live:
+        late = [s.adj for s in live if s.adj is not None and not s.adj.built]
+        if late:
+            from .csr import build_many
+            build_many(late)
+        wait_ready([s.adj for s in live])
+        by_dtype = {}
+        for s in live:
+            by_dtype.setdefault(s.resolve_dtype(), []).append(s.desc())
+        for dt, descs in by_dtype.items():
+            _ffi.aggregate_act(descs, device, dt)
+    return [s.out for s in specs]
+
+
+@dataclass
 class Stream:
     """One aggregation stream:  out = reduce_p msg(A[ia[p]], B[ib[p]])  (+ (1 + eps) * self_x).
 
@@ -153,6 +216,10 @@ class Stream:
     ib_mode  'aux'  B is a cell-feature matrix gathered through the adjacency's shared-cell index
              'perm' B holds one row per entry (e.g. `up_attr` as data/complex.py:579-580
                     materialises it)
+    act      None, or an activation ('id' | 'relu' | 'elu' | 'tanh' | 'sigmoid', or its CWN_ACT_* code: ACT_CODES) applied
+             to the message A + B: out = sum_p act(A[ia[p]] + B[ib[p]]) (+ self term).  Only with msg_op == MSG_A_PLUS_B,
+             reduce == 'add' and a B as wide as A; the stream then runs on cwn_aggregate_act_f32 / _f64
+             (run_aggregate_act), inference only.
     """
     adj: Optional[Adjacency]
     n_dst: int
@@ -166,8 +233,18 @@ class Stream:
     self_x: Optional[Tensor] = None
     eps: Optional[Tensor] = None
     dtype: Optional[torch.dtype] = None      # set by validate(): the one dtype of A, B and self_x
+    act: Optional[object] = None
 
     def validate(self):
+        if self.act is not None:
+            _act_code(self.act)
+            if self.msg_op != MSG_A_PLUS_B or self.reduce not in ('add', 'sum'):
+                raise ValueError("a stream with an activation is act(A + B) summed: msg_op must be MSG_A_PLUS_B and reduce 'add' "
+                                 f'(got msg_op {self.msg_op}, reduce {self.reduce!r})')
+            if self.adj is not None and (self.A is None or self.B is None or self.A.dim() != 2 or self.B.dim() != 2
+                                         or self.B.size(1) != self.A.size(1)):
+                raise ValueError('a stream with an activation takes a B as wide as A (no scalar attribute): '
+                                 f'A {None if self.A is None else tuple(self.A.shape)}, B {None if self.B is None else tuple(self.B.shape)}')
         self.A, self.B = _fc(self.A, 'A'), _fc(self.B, 'B')
         self.self_x, self.eps = _fc(self.self_x, 'self_x'), _fc(self.eps, 'eps')
         # one dtype per stream; eps, a device scalar (usually a parameter), follows it
@@ -336,6 +413,15 @@ class _AggregateMany(torch.autograd.Function):
         specs = []
         for k, st in enumerate(streams):
             A, B, self_x, eps = tensors[4 * k: 4 * k + 4]
+            if getattr(st, 'act', None) is not None:
+                s = AggActSpec(adj=st.adj, n_dst=st.n_dst, F=st.width, act=_act_code(st.act), self_x=self_x, eps=eps,
+                               dtype=getattr(st, 'dtype', None))
+                if st.adj is not None:
+                    s.A, s.B = A, B
+                    s.ia = st.adj.col if st.ia_mode == 'col' else st.adj.perm
+                    s.ib = st.adj.aux if st.ib_mode == 'aux' else st.adj.perm
+                specs.append(s)
+                continue
             s = AggSpec(adj=st.adj, n_dst=st.n_dst, F=st.width, msg_op=st.msg_op,
                         reduce=_ffi.REDUCE[st.reduce], self_x=self_x, eps=eps, dtype=getattr(st, 'dtype', None))
             if st.adj is not None:
@@ -391,8 +477,27 @@ class _AggregateMany(torch.autograd.Function):
         return (None, None) + tuple(grads)
 
 
+_ACT_NO_GRAD = ('a stream with an activation (Stream.act) runs on cwn_aggregate_act_f32 / _f64, which has no backward: '
+                'inference only')
+
+
+def _run_streams(specs: Sequence, device) -> List[Tensor]:
+    """The specs of `_AggregateMany.specs_of` launched, outputs in spec order: those of streams with an activation through
+    `run_aggregate_act`, the rest through `run_aggregate` (one call each, and only when it has something to run)."""
+    acts = [s for s in specs if isinstance(s, AggActSpec)]
+    if not acts:
+        return run_aggregate(specs, device)
+    plain = [s for s in specs if not isinstance(s, AggActSpec)]
+    run_aggregate_act(acts, device)
+    if plain:
+        run_aggregate(plain, device)
+    return [s.out for s in specs]
+
+
 def aggregate_many(streams: Sequence[Stream]) -> List[Tensor]:
-    """All streams in ONE kernel launch (per <= 8), differentiable w.r.t. A, B, self_x and eps."""
+    """All streams in ONE kernel launch (per <= 8), differentiable w.r.t. A, B, self_x and eps.  Streams with an
+    activation (Stream.act) take a launch of their own (run_aggregate_act) and are inference only; the outputs come back
+    in stream order either way."""
     device = None
     flat: List[Optional[Tensor]] = []
     for st in streams:
@@ -417,7 +522,9 @@ def aggregate_many(streams: Sequence[Stream]) -> List[Tensor]:
         build_many(todo)
     if not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in flat)):
         # inference: no autograd node to build (Function.apply alone is ~15 us of host time)
-        return run_aggregate(_AggregateMany.specs_of(streams, flat), device)
+        return _run_streams(_AggregateMany.specs_of(streams, flat), device)
+    if any(st.act is not None for st in streams):
+        raise NotImplementedError(_ACT_NO_GRAD)
     return list(_AggregateMany.apply(tuple(streams), device, *flat))
 
 
@@ -2103,6 +2210,13 @@ def linear_many_f64(items) -> List[Tensor]:
     'id', 'relu', 'elu', 'tanh', 'sigmoid' (or its CWN_ACT_* code, None = 'id').  Inference only: nothing is recorded
     for autograd.  Each output element is one fma chain over k in ascending order, so a row's result depends on that
     row and the weights alone (include/cwn_hip.h).  Anything but float64 GPU tensors is a TypeError."""
+    return _linear_many_f64(items)
+
+
+def _linear_many_f64(items) -> List[Tensor]:
+    """The launcher behind `linear_many_f64`, which callers inside the package use for products that are part of another
+    op -- the Y1 / Y2 of an activated coboundary message (layers._torch_products) -- so that the public function's calls
+    stay the ones a model's Linear layers make."""
     descs, outs, dev = [], [], None
     for i, (x, w, b, act) in enumerate(items):
         x, w, b = _f64rows(x, f'x[{i}]'), _f64rows(w, f'weight[{i}]'), _f64rows(b, f'bias[{i}]', 1)
@@ -2399,7 +2513,9 @@ def gemm_aggregate(gemms: Sequence[Gemm], make_streams, precomputed=None) -> Tup
             return streams, list(precomputed[1])
         for (k, slot), gi in links.items():
             flat_s[4 * k + slot] = ys[gi]
-        return streams, run_aggregate(_AggregateMany.specs_of(streams, flat_s), device)
+        return streams, _run_streams(_AggregateMany.specs_of(streams, flat_s), device)
+    if any(st.act is not None for st in streams):
+        raise NotImplementedError(_ACT_NO_GRAD)
     # the adjacency plans and their transposes in one batched build -- unless neither pass will read them: the forward is
     # precomputed (the blocked launch) and the backward is the owner-form launch over its own item table (a backward that
     # falls back to the streaming path after all builds them when it asks for them: csr.Adjacency.t_src / t_aux)

@@ -8,8 +8,9 @@ must land within 0.01 of each other (torch.pdist) while non-isomorphic ones are 
 Every gather and segmented reduce of the float64 model is a launch of csrc/cwn_aggregate_f64.hip.  The dense parts are
 launches of csrc/cwn_dense_f64.hip: per layer ONE launch for the update and combine networks of all three dimensions, and
 two for the head (the lin1s with their activation, lin2); its arithmetic is row-independent, so a complex gets the same
-bits whatever else shares its batch.  The ELU(Linear(cat)) message itself still runs as torch modules through the generic
-propagate.  CWN_FUSED_F64_DENSE=0 puts every Linear back on torch.nn.Linear (rocBLAS dgemm).
+bits whatever else shares its batch.  The ELU(Linear(cat)) message is two per-cell products and one launch of
+csrc/cwn_aggregate_act.hip per layer (sum of ELU(Y1[src] + Y2[shared]) in CSR order); CWN_FUSED_ACT_MESSAGE=0 puts it back on
+the generic propagate.  CWN_FUSED_F64_DENSE=0 puts every Linear back on torch.nn.Linear (rocBLAS dgemm).
 
     python examples/sr_isomorphism.py [seed]        (needs an MI355X)
 """

@@ -1252,6 +1252,76 @@ typedef struct cwn_chain_desc_f64 {
 int cwn_update_chain_f64(const cwn_chain_desc_f64* descs_host, int n_dims, cwn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The activated two-operand message (csrc/cwn_aggregate_act.hip), float32 and float64, inference:
+ *
+ *     out[i, :] = sum_{p in row i, in CSR order} act(A[ia[p], :] + B[ib[p], :])  +  (1 + eps) * self_x[i, :]
+ *
+ * -- the coboundary message act(Linear(cat(x_j, up_attr))) of a model built with a nonlinearity other than ReLU
+ * (exp/scripts/cwn-sr.sh: elu), split as the ReLU stream splits it: A = X W[:, :F]^T + b per source cell,
+ * B = X_attr W[:, F:]^T per shared cell (or per entry), gathered and added per entry, THEN activated.
+ * cwn_aggregate_f32 / _f64 apply no activation but ReLU, and their descriptor and device code are fixed; these entry
+ * points have their own descriptor, cwn_agg_act_desc / cwn_agg_act_desc_f64: one layout with float / double pointers.
+ * It carries the fields of cwn_agg_desc that apply, with their meaning there, plus `act`, any of the five CWN_ACT_*
+ * codes (CWN_ACT_RELU and CWN_ACT_ID included: those two can be compared with CWN_MSG_RELU_A_PLUS_B / CWN_MSG_A_PLUS_B).
+ * What it leaves out: B always has width F (no scalar B); the reduction is add; one self term, no self_pre; and there
+ * is NO m_dev -- n_dst is a host count and every row below it exists: no static batch reaches this launch.
+ * rowptr == NULL (absent adjacency): out = (1 + eps) * self_x, zeros without self_x.  n_dst == 0 and n == 0 are legal.
+ * Any F >= 1 (rows wider than one pass of a lane group are chunked).  One launch covers all n <= CWN_MAX_DESCS
+ * descriptors; the launcher validates every descriptor on the host before it launches, neither allocates nor
+ * synchronises.  CWN_ERR_BAD_ARG: n < 0 or n > CWN_MAX_DESCS, descs NULL with n > 0, act outside CWN_ACT_ID ..
+ * CWN_ACT_SIGMOID, F <= 0, n_dst < 0, out NULL with n_dst > 0, a non-NULL rowptr with a NULL ia / ib / A / B.
+ * CWN_ERR_TOO_LARGE: n_dst or the grid beyond int32.  CWN_ERR_ALIGN: a data pointer (eps included) that misses the
+ * alignment of its element type.
+ * Arithmetic: one add in the element type for the pre-activation; expm1f / tanhf / expf in float32 and expm1 / tanh /
+ * exp in float64 (ELU with alpha = 1); the accumulator starts at 0 and takes the messages in CSR order; then
+ * acc + (1 + eps) * self, un-fused.  No atomics.  A row's bits depend on its entries, F and its own descriptor's
+ * operands (their alignment decides the vector width) alone -- not on the row's place in the grid, on n_dst or on the
+ * other descriptors of the launch: the vector width and the lanes per row are chosen per descriptor.  Rows of at most
+ * CWN_LONG_ROW entries are folded sequentially by one lane group (with fewer than 8 feature lanes -- F <= 16 in
+ * float32, F <= 14 in float64 -- rows above 16 entries by the group's entry slots and a fixed tree, as in
+ * cwn_aggregate_*); longer rows listed in long_rows / n_long by a whole workgroup, contiguous chunks combined in chunk
+ * order.  CWN_AGG_SMALL_OPERANDS means what it means in cwn_agg_desc.flags.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct cwn_agg_act_desc {
+    const int32_t* rowptr;    /* [n_dst+1] or NULL (absent adjacency) */
+    const int32_t* ia;        /* [E] row of A per CSR position */
+    const int32_t* ib;        /* [E] row of B per CSR position */
+    const float* A;           /* [rows_a, F] */
+    const float* B;           /* [rows_b, F] */
+    const float* self_x;      /* [n_dst, F] or NULL */
+    const float* eps;         /* device scalar or NULL (= 0) */
+    float* out;               /* [n_dst, F] */
+    const int32_t* long_rows; /* from cwn_csr_build, or NULL (every row is reduced by one lane group) */
+    const int32_t* n_long;    /* [CWN_LONG_PARTS] from cwn_csr_build, or NULL */
+    int64_t n_dst;            /* host count: there is no m_dev */
+    int32_t F;
+    int32_t act;              /* CWN_ACT_* */
+    int32_t long_cap;         /* capacity of one long-row sub-list (E / CWN_LONG_ROW + 1) */
+    int32_t flags;            /* CWN_AGG_* bits (0: none) */
+} cwn_agg_act_desc;
+
+typedef struct cwn_agg_act_desc_f64 {
+    const int32_t* rowptr;
+    const int32_t* ia;
+    const int32_t* ib;
+    const double* A;
+    const double* B;
+    const double* self_x;
+    const double* eps;
+    double* out;
+    const int32_t* long_rows;
+    const int32_t* n_long;
+    int64_t n_dst;
+    int32_t F;
+    int32_t act;
+    int32_t long_cap;
+    int32_t flags;
+} cwn_agg_act_desc_f64;
+
+int cwn_aggregate_act_f32(const cwn_agg_act_desc* descs_host, int n, cwn_stream_t stream);
+int cwn_aggregate_act_f64(const cwn_agg_act_desc_f64* descs_host, int n, cwn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Device-side batching (collate): build the arrays of a ComplexBatch from a dataset that is
  * resident in HBM in packed form, with ONE launch.
  *
