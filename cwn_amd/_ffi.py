@@ -27,6 +27,7 @@ EXPORTS = ('cwn_abi_version', 'cwn_error_string', 'cwn_target_arch', 'cwn_csr_wo
            'cwn_target_head_f32', 'cwn_target_head_bwd_f32', 'cwn_target_head_bwd_workspace_bytes',
            'cwn_linear_many_f64', 'cwn_update_chain_f64',
            'cwn_aggregate_act_f32', 'cwn_aggregate_act_f64',
+           'cwn_embed_pool_f32', 'cwn_embed_pool_f64', 'cwn_agnostic_head_f32', 'cwn_agnostic_head_f64',
            'cwn_gemm_tn_f32', 'cwn_gemm_tn_workspace_bytes', 'cwn_adam_f32', 'cwn_adam_dev_f32', 'cwn_loss_f32', 'cwn_loss_cols_f32', 'cwn_embedding_fwd_f32', 'cwn_embedding_bwd_f32', 'cwn_embed_front_f32', 'cwn_head_f32', 'cwn_head_bwd_f32', 'cwn_head_pool_floats', 'cwn_lift_create', 'cwn_lift_size', 'cwn_lift_copy', 'cwn_lift_destroy',
            'cwn_lift_many', 'cwn_lift_many_count', 'cwn_lift_many_lengths', 'cwn_lift_many_copy', 'cwn_lift_many_destroy',
            # the evaluation pass (csrc/cwn_metrics.hip)
@@ -66,6 +67,26 @@ class AggActDesc(C.Structure):
 
 
 AggActDescF64 = AggActDesc
+
+# = CWN_EMBED_POOL_MAX_K, CWN_AGNOSTIC_MAX_WIDTH, CWN_EMBED_POOL_CHUNK (csrc/cwn_agnostic.hip)
+EMBED_POOL_MAX_K, AGNOSTIC_MAX_WIDTH, EMBED_POOL_CHUNK = 128, 1024, 16
+
+
+class EmbedPoolDesc(C.Structure):
+    """cwn_embed_pool_desc and cwn_embed_pool_desc_f64 (include/cwn_hip.h): one layout, every data pointer is a void*."""
+    _fields_ = [('x', C.c_void_p), ('cell_ptr', C.c_void_p), ('W', C.c_void_p), ('bias', C.c_void_p), ('out', C.c_void_p),
+                ('N', C.c_int64), ('C', C.c_int64), ('ldx', C.c_int64), ('ldw', C.c_int64), ('ldo', C.c_int64),
+                ('K', C.c_int32), ('H', C.c_int32), ('act', C.c_int32), ('mean', C.c_int32)]
+
+
+class AgnosticHeadDesc(C.Structure):
+    """cwn_agnostic_head_desc and cwn_agnostic_head_desc_f64: one layout (MAX_DESCS pooled matrices at most)."""
+    _fields_ = [('P', C.c_void_p * MAX_DESCS), ('ldp', C.c_int64 * MAX_DESCS), ('W1', C.c_void_p), ('b1', C.c_void_p), ('W2', C.c_void_p),
+                ('b2', C.c_void_p), ('out', C.c_void_p), ('C', C.c_int64), ('ldw1', C.c_int64), ('ldw2', C.c_int64),
+                ('ldo', C.c_int64), ('D', C.c_int32), ('H', C.c_int32), ('O', C.c_int32), ('act', C.c_int32)]
+
+
+EmbedPoolDescF64, AgnosticHeadDescF64 = EmbedPoolDesc, AgnosticHeadDesc
 
 
 class LongRowsDesc(C.Structure):
@@ -514,6 +535,12 @@ def lib():
     L.cwn_aggregate_act_f32.argtypes = [C.POINTER(AggActDesc), C.c_int, C.c_void_p]
     L.cwn_aggregate_act_f64.restype = C.c_int
     L.cwn_aggregate_act_f64.argtypes = [C.POINTER(AggActDescF64), C.c_int, C.c_void_p]
+    for fn in (L.cwn_embed_pool_f32, L.cwn_embed_pool_f64):
+        fn.restype = C.c_int
+        fn.argtypes = [C.POINTER(EmbedPoolDesc), C.c_int, C.c_void_p]
+    for fn in (L.cwn_agnostic_head_f32, L.cwn_agnostic_head_f64):
+        fn.restype = C.c_int
+        fn.argtypes = [C.POINTER(AgnosticHeadDesc), C.c_void_p]
     L.cwn_target_head_bwd_workspace_bytes.restype = C.c_size_t
     L.cwn_target_head_bwd_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32]
     L.cwn_adam_dev_f32.restype = C.c_int

@@ -9,6 +9,7 @@ mp/models.py:120-260 for non-embedded inputs (REDDIT-like config).  The readout
 """
 from typing import List
 
+import os
 import weakref
 
 import torch
@@ -651,6 +652,113 @@ class Dummy(torch.nn.Module):
         for t in pooled[1:]:
             x = x + t
         return self.lin(x)
+
+    def __repr__(self):
+        return self.__class__.__name__
+
+
+# MessagePassingAgnostic in inference as two launches of csrc/cwn_agnostic.hip (ops.embed_pool, ops.agnostic_head).
+# True / False: for every dtype / for none (CWN_FUSED_AGNOSTIC=1 / =0); a set of dtypes: for those -- the default,
+# FUSED_AGNOSTIC_DEFAULT, holds the dtypes at which the two launches have measured faster than the torch modules by more
+# than the run-to-run spread of both forms (tools/bench_agnostic.py, profiles/sr_baseline.md: on the SR batch at hidden 256
+# float64 96.2 against 170.0 us per forward, spread 9.4 us; float32 88.3 against 203.5 us, spread 26.7 us).
+FUSED_AGNOSTIC_DEFAULT = frozenset({torch.float32, torch.float64})
+FUSED_AGNOSTIC = {'0': False, '1': True}.get(os.environ.get('CWN_FUSED_AGNOSTIC'), FUSED_AGNOSTIC_DEFAULT)
+
+
+def _agnostic_on(dtype) -> bool:
+    on = FUSED_AGNOSTIC
+    return dtype in on if isinstance(on, (set, frozenset)) else bool(on)
+
+
+class MessagePassingAgnostic(torch.nn.Module):
+    """mp/models.py:618-661: no message passing -- a Linear and the nonlinearity per dimension, the readout per complex,
+    lin1 and the nonlinearity on every dimension's readout (an absent dimension enters as zeros), their sum, dropout, lin2.
+    The control of the strongly-regular-graph experiment (exp/scripts/cwn-sr-base.sh).  Same constructor, attributes and
+    state_dict keys as the reference.
+
+    In inference on the GPU the forward is two launches (`FUSED_AGNOSTIC`): ops.embed_pool, then ops.agnostic_head.
+    `last_route` says which way the last forward went: 'fused' or 'torch'."""
+
+    def __init__(self, num_input_features, num_classes, hidden, dropout_rate: float = 0.5,
+                 max_dim: int = 2, nonlinearity='relu', readout='sum'):
+        super().__init__()
+        self.max_dim = max_dim
+        self.dropout_rate = dropout_rate
+        self.readout_type = readout
+        self.nonlinearity = nonlinearity
+        self.act = get_nonlinearity(nonlinearity, return_module=False)
+        self.lin0s = torch.nn.ModuleList(Linear(num_input_features, hidden) for _ in range(max_dim + 1))
+        self.lin1 = Linear(hidden, hidden)
+        self.lin2 = Linear(hidden, num_classes)
+        self.last_route = None
+
+    def reset_parameters(self):
+        for lin0 in self.lin0s:
+            lin0.reset_parameters()
+        self.lin1.reset_parameters()
+        self.lin2.reset_parameters()
+
+    def _fused(self, data: ComplexBatch):
+        """The two launches, or None where they do not apply (the conditions are README's "MessagePassingAgnostic")."""
+        if torch.is_grad_enabled() or (self.training and self.dropout_rate > 0) or _ffi.DYN_ROWS:
+            return None
+        if self.nonlinearity not in ops.ACT_CODES or self.readout_type not in ('sum', 'mean'):
+            return None
+        n_dims = min(self.max_dim, data.dimension) + 1
+        xs = [data.cochains[d].x for d in range(n_dims)]
+        dtype = self.lin1.weight.dtype
+        if any(x is None or not x.is_cuda or x.dim() != 2 or x.dtype != dtype for x in xs) or not _agnostic_on(dtype):
+            return None
+        if dtype not in _ffi.FLOAT_DTYPES or any(p.dtype != dtype or not p.is_cuda for p in self.parameters()):
+            return None
+        K, H, O = self.lin0s[0].in_features, self.lin1.in_features, self.lin2.out_features
+        if not (1 <= K <= _ffi.EMBED_POOL_MAX_K and 1 <= H <= _ffi.AGNOSTIC_MAX_WIDTH and 1 <= O <= _ffi.AGNOSTIC_MAX_WIDTH) \
+                or self.max_dim + 1 > _ffi.MAX_DESCS or any(x.size(1) != K for x in xs):
+            return None
+        plan = data.block_plan()
+        if plan is None or data.num_complexes is None or plan.C != data.num_complexes or plan.n_dims < n_dims \
+                or any(int(plan.cell_ptr[d][-1]) != x.size(0) for d, x in enumerate(xs)):
+            return None                    # a batch assembled by hand, or features that are not the batch's own rows
+        dev = xs[0].device
+        xs = [x if x.stride(-1) == 1 or not x.numel() else x.contiguous() for x in xs]
+        pooled = ops.embed_pool(xs, [plan.cell_ptr_device(d, dev) for d in range(n_dims)], plan.C,
+                                [self.lin0s[d].weight for d in range(n_dims)], [self.lin0s[d].bias for d in range(n_dims)],
+                                self.nonlinearity, mean=self.readout_type == 'mean')
+        pooled += [None] * (self.max_dim + 1 - n_dims)          # absent dimensions: zero rows (mp/nn.py:55-56)
+        return ops.agnostic_head(pooled, self.lin1.weight, self.lin1.bias, self.lin2.weight, self.lin2.bias,
+                                 self.nonlinearity, n_complexes=plan.C)
+
+    @staticmethod
+    def _pool_on_host(xs, data: ComplexBatch, max_dim: int, readout_type: str):
+        """pool_complex (mp/nn.py:50-60) for features on the CPU, where the segmented-reduce kernel does not run: index_add_
+        over the batch vector, differentiable.  -> [max_dim + 1, num_complexes, H]; rows of absent dimensions stay zero."""
+        if readout_type not in ('sum', 'mean'):
+            raise NotImplementedError(f'Readout {readout_type} is not currently supported.')
+        size = data.num_complexes if data.num_complexes is not None else int(data.cochains[0].batch.max()) + 1
+        pooled = []
+        for i, x in enumerate(xs):
+            batch = data.cochains[i].batch
+            p = torch.zeros(size, x.size(-1), dtype=x.dtype).index_add_(0, batch, x)
+            if readout_type == 'mean':
+                p = p / torch.bincount(batch, minlength=size).clamp(min=1).to(x.dtype).unsqueeze(1)
+            pooled.append(p)
+        pooled += [torch.zeros_like(pooled[0]) for _ in range(len(xs), max_dim + 1)]
+        return torch.stack(pooled, dim=0)
+
+    @_one_check
+    def forward(self, data: ComplexBatch):
+        out = self._fused(data)
+        self.last_route = 'torch' if out is None else 'fused'
+        if out is not None:
+            return out
+        params = data.get_all_cochain_params(max_dim=self.max_dim, include_down_features=False)
+        xs = [self.act(self.lin0s[dim](params[dim].x)) for dim in range(len(params))]
+        pool = pool_complex if xs[0].is_cuda else self._pool_on_host
+        pooled_xs = self.act(self.lin1(pool(xs, data, self.max_dim, self.readout_type)))
+        x = pooled_xs.sum(dim=0)
+        x = F.dropout(x, p=self.dropout_rate, training=self.training)
+        return self.lin2(x)
 
     def __repr__(self):
         return self.__class__.__name__

@@ -2326,6 +2326,112 @@ def update_chain_f64(dims: Sequence[ChainDim]) -> List[Tensor]:
 
 
 # ------------------------------------------------------------------------------------------------
+# The message-passing-agnostic baseline (csrc/cwn_agnostic.hip): embed + activate + pool, and the head, inference only
+# ------------------------------------------------------------------------------------------------
+def _agnostic_dtype(named, what: str) -> torch.dtype:
+    """The one dtype of the operands of an `embed_pool` / `agnostic_head` call: float32 or float64, on the GPU, rows
+    contiguous (a row stride is allowed).  Anything else is a TypeError that names the dtype."""
+    dtype = None
+    for name, t, dim in named:
+        if t is None:
+            continue
+        if not isinstance(t, Tensor) or t.dtype not in _ffi.FLOAT_DTYPES:
+            raise TypeError(f'{what}: {name} must be float32 or float64 (got {getattr(t, "dtype", type(t).__name__)}): '
+                            'the kernels of csrc/cwn_agnostic.hip compute in fp32 or fp64 only')
+        if dtype is None:
+            dtype = t.dtype
+        if t.dtype != dtype:
+            raise TypeError(f'{what}: {name} is {t.dtype}, the operands before it {dtype}: all operands of a call share one dtype')
+    for name, t, dim in named:
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise TypeError(f'{what}: {name} must be a {t.dtype} tensor on the GPU (it is on {t.device})')
+        if t.dim() != dim or (t.numel() and t.stride(-1) != 1) or (dim == 2 and t.size(0) > 1 and t.stride(0) < t.size(1)):
+            raise TypeError(f'{what}: {name} must be a {dim}-D {t.dtype} tensor with contiguous rows (shape {tuple(t.shape)}, '
+                            f'strides {tuple(t.stride())})')
+    if dtype is None:
+        raise ValueError(f'{what}: no operand')
+    return dtype
+
+
+def embed_pool(xs, cell_ptrs, n_complexes: int, weights, biases, act, mean: bool = False) -> List[Tensor]:
+    """[pool_c(act(x @ weight.T + bias)) for x, weight, bias in zip(xs, weights, biases)] -> a list of [n_complexes, H]:
+    the per-complex sum (mean: the mean, an empty complex gives zeros) of the activated embedding of every dimension from
+    ONE launch (8 dimensions at most per launch; a longer list takes more) that writes nothing but the results.
+    x [N, K] and weight [H, K] may be row-strided views, 1 <= K <= 128, 1 <= H <= 1024, bias [H] or None; cell_ptrs[i]:
+    the collate's `ptr` of that dimension as a device int64 [n_complexes + 1] (`BlockPlan.cell_ptr_device`); act one of
+    'id', 'relu', 'elu', 'tanh', 'sigmoid' (or its CWN_ACT_* code, None = 'id').  Inference only: nothing is recorded for
+    autograd.  The bits of a complex's row depend on its own rows in order and the weights alone (include/cwn_hip.h).
+    All operands are float32 or all float64, on the GPU: anything else is a TypeError that names the dtype."""
+    if not (len(xs) == len(cell_ptrs) == len(weights) == len(biases)) or not xs:
+        raise ValueError(f'embed_pool: {len(xs)} inputs, {len(cell_ptrs)} cell_ptrs, {len(weights)} weights, {len(biases)} biases')
+    named = [(f'{n}[{i}]', t, dim) for i in range(len(xs))
+             for n, t, dim in (('xs', xs[i], 2), ('weights', weights[i], 2), ('biases', biases[i], 1))]
+    dtype = _agnostic_dtype(named, 'embed_pool')
+    C_, code = int(n_complexes), _act_code(act)
+    descs, outs, dev = [], [], xs[0].device
+    for i, (x, ptr, w, b) in enumerate(zip(xs, cell_ptrs, weights, biases)):
+        N, K, H = int(x.size(0)), int(x.size(1)), int(w.size(0))
+        if int(w.size(1)) != K or (b is not None and b.numel() != H):
+            raise ValueError(f'embed_pool {i}: x {tuple(x.shape)}, weight {tuple(w.shape)}, bias {None if b is None else tuple(b.shape)}')
+        if not (1 <= K <= _ffi.EMBED_POOL_MAX_K and 1 <= H <= _ffi.AGNOSTIC_MAX_WIDTH):
+            raise ValueError(f'embed_pool {i}: K = {K} outside [1, {_ffi.EMBED_POOL_MAX_K}] or H = {H} outside [1, {_ffi.AGNOSTIC_MAX_WIDTH}]')
+        if not isinstance(ptr, Tensor) or ptr.dtype != torch.int64 or ptr.device != dev or ptr.numel() != C_ + 1 \
+                or not ptr.is_contiguous():
+            raise ValueError(f'embed_pool {i}: cell_ptr must be a contiguous int64 [{C_ + 1}] on {dev}')
+        out = torch.empty(C_, H, dtype=dtype, device=dev)
+        outs.append(out)
+        descs.append(_ffi.EmbedPoolDesc(x=x.data_ptr() if N else None, cell_ptr=ptr.data_ptr(), W=w.data_ptr(), bias=_ffi.ptr(b),
+                                        out=out.data_ptr(), N=N, C=C_, ldx=_ld(x), ldw=_ld(w), ldo=H, K=K, H=H, act=code,
+                                        mean=int(bool(mean))))
+    name = 'cwn_embed_pool_f32' if dtype == torch.float32 else 'cwn_embed_pool_f64'
+    fn = getattr(_ffi.lib(), name)
+    for lo in range(0, len(descs), _ffi.MAX_DESCS):
+        part = descs[lo:lo + _ffi.MAX_DESCS]
+        _ffi.check(fn((_ffi.EmbedPoolDesc * len(part))(*part), len(part), _ffi.stream_ptr(dev)), name)
+    return outs
+
+
+def agnostic_head(pooled, lin1_w: Tensor, lin1_b: Optional[Tensor], lin2_w: Tensor, lin2_b: Optional[Tensor], act,
+                  n_complexes: Optional[int] = None) -> Tensor:
+    """sum_d act(pooled[d] @ lin1_w.T + lin1_b) @ lin2_w.T + lin2_b -> [C, O] from ONE launch: the part of
+    MessagePassingAgnostic behind the readout.  pooled: 1 to 8 matrices [C, H]; None stands for a matrix of zeros (an
+    absent dimension, which still contributes act(lin1_b)) -- with nothing but None, `n_complexes` says C.  lin1_w [H, H],
+    lin2_w [O, H], 1 <= H, O <= 1024, the biases or None.  Inference only; a row depends on that complex's rows alone.
+    All operands are float32 or all float64, on the GPU: anything else is a TypeError that names the dtype."""
+    pooled = list(pooled)
+    if not 1 <= len(pooled) <= _ffi.MAX_DESCS:
+        raise ValueError(f'agnostic_head: {len(pooled)} pooled matrices (1 to {_ffi.MAX_DESCS})')
+    named = [(f'pooled[{d}]', p, 2) for d, p in enumerate(pooled)] + [('lin1_w', lin1_w, 2), ('lin1_b', lin1_b, 1),
+                                                                        ('lin2_w', lin2_w, 2), ('lin2_b', lin2_b, 1)]
+    if lin1_w is None or lin2_w is None:
+        raise ValueError('agnostic_head: lin1_w and lin2_w are required')
+    dtype = _agnostic_dtype(named, 'agnostic_head')
+    have = [p for p in pooled if p is not None]
+    C_ = int(have[0].size(0)) if have else n_complexes
+    if C_ is None:
+        raise ValueError('agnostic_head: every pooled matrix is None and n_complexes is not given')
+    H, O = int(lin1_w.size(0)), int(lin2_w.size(0))
+    if tuple(lin1_w.shape) != (H, H) or int(lin2_w.size(1)) != H or any(tuple(p.shape) != (C_, H) for p in have) \
+            or (lin1_b is not None and lin1_b.numel() != H) or (lin2_b is not None and lin2_b.numel() != O):
+        raise ValueError(f'agnostic_head: pooled {[None if p is None else tuple(p.shape) for p in pooled]}, lin1_w '
+                         f'{tuple(lin1_w.shape)}, lin2_w {tuple(lin2_w.shape)}')
+    if not (1 <= H <= _ffi.AGNOSTIC_MAX_WIDTH and 1 <= O <= _ffi.AGNOSTIC_MAX_WIDTH):
+        raise ValueError(f'agnostic_head: widths H = {H}, O = {O} outside [1, {_ffi.AGNOSTIC_MAX_WIDTH}]')
+    dev = lin1_w.device
+    out = torch.empty(C_, O, dtype=dtype, device=dev)
+    D = _ffi.AgnosticHeadDesc(W1=lin1_w.data_ptr(), b1=_ffi.ptr(lin1_b), W2=lin2_w.data_ptr(), b2=_ffi.ptr(lin2_b),
+                              out=out.data_ptr(), C=C_, ldw1=_ld(lin1_w), ldw2=_ld(lin2_w), ldo=O, D=len(pooled), H=H, O=O,
+                              act=_act_code(act))
+    for d, p in enumerate(pooled):
+        D.P[d], D.ldp[d] = (p.data_ptr() if p is not None and C_ else None), (_ld(p) if p is not None else H)
+    name = 'cwn_agnostic_head_f32' if dtype == torch.float32 else 'cwn_agnostic_head_f64'
+    _ffi.check(getattr(_ffi.lib(), name)(C.byref(D), _ffi.stream_ptr(dev)), name)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # gemm_many + aggregate_many of one propagate step as ONE autograd node
 # ------------------------------------------------------------------------------------------------
 FUSED_PROPAGATE_NODE = os.environ.get('CWN_FUSED_PROPAGATE_NODE') != '0'     # A/B: '0' keeps the two nodes

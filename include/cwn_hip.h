@@ -1322,6 +1322,125 @@ int cwn_aggregate_act_f32(const cwn_agg_act_desc* descs_host, int n, cwn_stream_
 int cwn_aggregate_act_f64(const cwn_agg_act_desc_f64* descs_host, int n, cwn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The message-passing-agnostic baseline (csrc/cwn_agnostic.hip), float32 and float64, inference:
+ * MessagePassingAgnostic (mp/models.py:618-661), the control of the strongly-regular-graph experiment
+ * (exp/scripts/cwn-sr-base.sh: hidden 256, ELU, float64), as two launches.
+ *
+ * cwn_embed_pool_f32 / _f64 -- embed, activate and pool every dimension in one launch, n <= CWN_MAX_DESCS descriptors
+ * (cwn_embed_pool_desc / cwn_embed_pool_desc_f64: one layout with float / double pointers), one per dimension:
+ *
+ *     out[c, h] = sum_{r = cell_ptr[c] .. cell_ptr[c+1]-1} act((sum_k x[r, k] * W[h, k]) + bias[h])
+ *                                                              [ / max(cell_ptr[c+1] - cell_ptr[c], 1) when mean ]
+ *
+ * x [N, K] (row stride ldx), W [H, K] (row stride ldw: a column slice is allowed), bias [H] or NULL, out [C, H] (row stride
+ * ldo); cell_ptr: DEVICE int64 [C+1], the collate's `ptr` (the rows of complex c; values outside [0, N] are clamped).
+ * 1 <= K <= CWN_EMBED_POOL_MAX_K, 1 <= H <= CWN_AGNOSTIC_MAX_WIDTH.  A complex without a row in that dimension -- N == 0
+ * included, x may then be NULL -- gets a zero row; C == 0 and n == 0 are legal.  Every row of out is written.
+ * N and C are HOST counts: there is NO m_dev and no static batch reaches this launch.
+ * Arithmetic: the pre-activation is one fma chain over k ascending from 0, then the bias add (no add without a bias); then
+ * the activation -- expm1f / tanhf / expf in float32, expm1 / tanh / exp in float64, ELU with alpha = 1.  The rows of a
+ * complex are cut into chunks of CWN_EMBED_POOL_CHUNK rows, chunk j is folded by wave j % 4 of the workgroup, a wave adds
+ * the rows of its chunks in ascending order onto one accumulator that starts at 0, and the four partials are combined
+ * as ((p0 + p1) + p2) + p3.  No atomics.  The bits of out[c, :] are therefore a function of the complex's own rows in
+ * order, W, bias, K, H, act and mean -- not of C, of the complex's place in the batch, of the other complexes or of the
+ * other descriptors of the launch.
+ *
+ * cwn_agnostic_head_f32 / _f64 -- the rest of the model, ONE descriptor, one workgroup per complex:
+ *
+ *     s[c, j]   = sum_{d = 0 .. D-1, ascending} act((sum_k P_d[c, k] * W1[j, k]) + b1[j])
+ *     out[c, o] = (sum_k s[c, k] * W2[o, k]) + b2[o]
+ *
+ * P[d] [C, H] (row stride ldp[d]) for d < D <= CWN_MAX_DESCS; a NULL P[d] is a matrix of zeros -- the reference's absent
+ * dimension, which still contributes act(b1) (mp/nn.py:55-56).  W1 [H, H], W2 [O, H], b1 / b2 or NULL, out [C, O];
+ * 1 <= H, O <= CWN_AGNOSTIC_MAX_WIDTH.  Both fma chains ascend in k from 0, the sum over d starts at 0 and ascends; a
+ * row of out depends on that complex's rows of P alone.  C is a host count; C == 0 is legal.
+ *
+ * Both launchers validate everything on the host before the first HIP call, neither allocates nor synchronises.
+ * CWN_ERR_BAD_ARG: n < 0 or n > CWN_MAX_DESCS (D < 1 or D > CWN_MAX_DESCS), a NULL descriptor, K / H / O outside their
+ * ranges, act outside CWN_ACT_ID .. CWN_ACT_SIGMOID, mean other than 0 / 1, N < 0, C < 0, a row stride below its width,
+ * x or W NULL with N > 0, cell_ptr or out NULL with C > 0, W1 / W2 / out NULL with C > 0.  CWN_ERR_TOO_LARGE: N, C or
+ * the grid beyond int32.  CWN_ERR_ALIGN: a data pointer that misses the alignment of its element type (cell_ptr: 8).
+ * ------------------------------------------------------------------------------------------ */
+#define CWN_EMBED_POOL_MAX_K 128    /* widest input row of cwn_embed_pool_* */
+#define CWN_AGNOSTIC_MAX_WIDTH 1024 /* widest H (both launches) and O */
+#define CWN_EMBED_POOL_CHUNK 16     /* rows per chunk of a complex: the unit the four waves of a workgroup share out */
+
+typedef struct cwn_embed_pool_desc {
+    const float* x;          /* [N, K] or NULL (N == 0) */
+    const int64_t* cell_ptr; /* device int64 [C+1] */
+    const float* W;          /* [H, K] */
+    const float* bias;       /* [H] or NULL */
+    float* out;              /* [C, H] */
+    int64_t N;               /* host count: there is no m_dev */
+    int64_t C;               /* host count */
+    int64_t ldx;
+    int64_t ldw;
+    int64_t ldo;
+    int32_t K;
+    int32_t H;
+    int32_t act;             /* CWN_ACT_* */
+    int32_t mean;            /* 0: sum, 1: mean */
+} cwn_embed_pool_desc;
+
+typedef struct cwn_embed_pool_desc_f64 {
+    const double* x;
+    const int64_t* cell_ptr;
+    const double* W;
+    const double* bias;
+    double* out;
+    int64_t N;
+    int64_t C;
+    int64_t ldx;
+    int64_t ldw;
+    int64_t ldo;
+    int32_t K;
+    int32_t H;
+    int32_t act;
+    int32_t mean;
+} cwn_embed_pool_desc_f64;
+
+typedef struct cwn_agnostic_head_desc {
+    const float* P[CWN_MAX_DESCS]; /* [C, H] each, or NULL (zeros) */
+    int64_t ldp[CWN_MAX_DESCS];
+    const float* W1;               /* [H, H] */
+    const float* b1;               /* [H] or NULL */
+    const float* W2;               /* [O, H] */
+    const float* b2;               /* [O] or NULL */
+    float* out;                    /* [C, O] */
+    int64_t C;                     /* host count */
+    int64_t ldw1;
+    int64_t ldw2;
+    int64_t ldo;
+    int32_t D;
+    int32_t H;
+    int32_t O;
+    int32_t act;                   /* CWN_ACT_* */
+} cwn_agnostic_head_desc;
+
+typedef struct cwn_agnostic_head_desc_f64 {
+    const double* P[CWN_MAX_DESCS];
+    int64_t ldp[CWN_MAX_DESCS];
+    const double* W1;
+    const double* b1;
+    const double* W2;
+    const double* b2;
+    double* out;
+    int64_t C;
+    int64_t ldw1;
+    int64_t ldw2;
+    int64_t ldo;
+    int32_t D;
+    int32_t H;
+    int32_t O;
+    int32_t act;
+} cwn_agnostic_head_desc_f64;
+
+int cwn_embed_pool_f32(const cwn_embed_pool_desc* descs_host, int n, cwn_stream_t stream);
+int cwn_embed_pool_f64(const cwn_embed_pool_desc_f64* descs_host, int n, cwn_stream_t stream);
+int cwn_agnostic_head_f32(const cwn_agnostic_head_desc* desc_host, cwn_stream_t stream);
+int cwn_agnostic_head_f64(const cwn_agnostic_head_desc_f64* desc_host, cwn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Device-side batching (collate): build the arrays of a ComplexBatch from a dataset that is
  * resident in HBM in packed form, with ONE launch.
  *
