@@ -28,6 +28,7 @@ EXPORTS = ('cwn_abi_version', 'cwn_error_string', 'cwn_target_arch', 'cwn_csr_wo
            'cwn_linear_many_f64', 'cwn_update_chain_f64',
            'cwn_aggregate_act_f32', 'cwn_aggregate_act_f64',
            'cwn_embed_pool_f32', 'cwn_embed_pool_f64', 'cwn_agnostic_head_f32', 'cwn_agnostic_head_f64',
+           'cwn_gin_layer_f32',
            'cwn_gemm_tn_f32', 'cwn_gemm_tn_workspace_bytes', 'cwn_adam_f32', 'cwn_adam_dev_f32', 'cwn_loss_f32', 'cwn_loss_cols_f32', 'cwn_embedding_fwd_f32', 'cwn_embedding_bwd_f32', 'cwn_embed_front_f32', 'cwn_head_f32', 'cwn_head_bwd_f32', 'cwn_head_pool_floats', 'cwn_lift_create', 'cwn_lift_size', 'cwn_lift_copy', 'cwn_lift_destroy',
            'cwn_lift_many', 'cwn_lift_many_count', 'cwn_lift_many_lengths', 'cwn_lift_many_copy', 'cwn_lift_many_destroy',
            # the evaluation pass (csrc/cwn_metrics.hip)
@@ -341,6 +342,17 @@ class OrientedDesc(C.Structure):
                 ('w', C.c_int32), ('H', C.c_int32), ('act', C.c_int32), ('w_trans', C.c_int32), ('m_dev', C.c_void_p)]
 
 
+GIN_MAX_WIDTH, GIN_TM = 128, 32     # = CWN_GIN_MAX_WIDTH, CWN_GIN_TM (csrc/cwn_gin.hip)
+
+
+class GinDesc(C.Structure):
+    """cwn_gin_desc (include/cwn_hip.h): one GINConv layer in inference."""
+    _fields_ = [('x', C.c_void_p), ('rowptr', C.c_void_p), ('col', C.c_void_p), ('eps_dev', C.c_void_p), ('W1', C.c_void_p),
+                ('b1', C.c_void_p), ('scale1', C.c_void_p), ('shift1', C.c_void_p), ('W2', C.c_void_p), ('b2', C.c_void_p),
+                ('scale2', C.c_void_p), ('shift2', C.c_void_p), ('out', C.c_void_p), ('n', C.c_int64), ('ldx', C.c_int64),
+                ('ldout', C.c_int64), ('w', C.c_int32), ('H', C.c_int32), ('act', C.c_int32), ('act_post', C.c_int32)]
+
+
 # the float64 dense path (csrc/cwn_dense_f64.hip) = CWN_LINEAR_F64_* / CWN_CHAIN_F64_* / CWN_DENSE_F64_TILE_ROWS
 LINEAR_F64_MAX_DESCS, LINEAR_F64_MAX_WIDTH, CHAIN_F64_MAX_DIMS, CHAIN_F64_MAX_WIDTH, DENSE_F64_TILE_ROWS = 16, 128, 4, 64, 16
 
@@ -541,6 +553,8 @@ def lib():
     for fn in (L.cwn_agnostic_head_f32, L.cwn_agnostic_head_f64):
         fn.restype = C.c_int
         fn.argtypes = [C.POINTER(AgnosticHeadDesc), C.c_void_p]
+    L.cwn_gin_layer_f32.restype = C.c_int
+    L.cwn_gin_layer_f32.argtypes = [C.POINTER(GinDesc), C.c_void_p]
     L.cwn_target_head_bwd_workspace_bytes.restype = C.c_size_t
     L.cwn_target_head_bwd_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32]
     L.cwn_adam_dev_f32.restype = C.c_int
@@ -819,6 +833,12 @@ def oriented_dz(dout: torch.Tensor, out: torch.Tensor, act: int) -> torch.Tensor
     check(lib().cwn_oriented_dz_f32(dout.data_ptr(), out.data_ptr(), dz.data_ptr(), n, H, dout.stride(0), out.stride(0), H, int(act),
                                     dyn(n), stream_ptr(out.device)), 'cwn_oriented_dz_f32')
     return dz
+
+
+def gin_layer(desc: 'GinDesc', device) -> None:
+    """One GINConv layer in one launch (csrc/cwn_gin.hip).  The row count is a host count: the descriptor has no m_dev, so
+    nothing is looked up in DYN_ROWS (the callers decline under `dynamic_rows`)."""
+    check(lib().cwn_gin_layer_f32(C.byref(desc), stream_ptr(device)), 'cwn_gin_layer_f32')
 
 
 def target_head_served(H: int, K: int) -> bool:

@@ -1915,6 +1915,91 @@ class OrientedConv(CochainMessagePassing):
         return self._fused(down_adj_t, x, down_attr, self.aggr_down)
 
 
+# A GINConv in inference as ONE cwn_gin_layer_f32 launch (csrc/cwn_gin.hip; float32, widths up to 128, a stock two-stage
+# network with foldable norms) instead of one aggregation launch and the torch modules of its network (two GEMMs with
+# their bias adds, two BatchNorms, two activations).  CWN_FUSED_GIN=1 / =0 turns the route on / off; without it
+# FUSED_GIN_DEFAULT decides, which follows the project's rule: on only where the route has measured faster than the
+# torch-module route of the same commit by more than the larger run-to-run spread of the two (tools/bench_gin.py,
+# profiles/gin_layer.md, 32 rings per batch, both routes alternating in one process: one layer at (64, 64) 44.6 against
+# 121.7 us, spread 10.3 us, 1 kernel against 9; RingGIN with 16 layers on 32-rings 727.1 against 1812.7 us, spread 11.4 us,
+# 18 kernels against 147; 5 layers on 10-rings 279.2 against 660.7 us, spread 16.7 us).
+FUSED_GIN_DEFAULT = True
+FUSED_GIN = {'0': False, '1': True}.get(os.environ.get('CWN_FUSED_GIN'), FUSED_GIN_DEFAULT)
+
+
+class GINConv(torch.nn.Module):
+    """torch_geometric.nn.GINConv (the layer of mp/graph_models.py and of RingGIN, mp/ring_exp_models.py:76-130) with its
+    constructor and state: out_i = nn((1 + eps) * x_i + sum_{j -> i} x_j), `edge_index[0]` the source and `[1]` the target;
+    `eps` a [1] tensor -- a Parameter with train_eps, a registered buffer otherwise, in the state_dict either way.
+
+    forward has two routes; `last_route` names the one the last call took:
+      'fused'    autograd off, float32 on the GPU, `nn` a stock Sequential of two (Linear, norm, activation) groups whose
+                 norms fold (eval-mode BatchNorm1d or Identity), widths within 128, FUSED_GIN on, no static batch:
+                 csr.cached_adjacency + ONE ops.gin_layer launch.
+      'generic'  everything else (training, float64, LayerNorm, a custom nn, CPU tensors): on the GPU ops.aggregate with the
+                 self term folded in (differentiable, float32 and float64), then `self.nn`; on the CPU index_add_, then
+                 `self.nn`.
+    `out` (a [n, H] view, e.g. a column slice of a JumpingKnowledge('cat') buffer) is written by the fused route alone: the
+    caller sees from the result's data_ptr whether it was.  `act_post` names an activation applied to the result
+    (RingGIN's `act(conv1(x))`)."""
+
+    def __init__(self, nn: Callable, eps: float = 0., train_eps: bool = False):
+        super().__init__()
+        self.nn = nn
+        self.initial_eps = eps
+        if train_eps:
+            self.eps = torch.nn.Parameter(torch.Tensor([eps]))
+        else:
+            self.register_buffer('eps', torch.Tensor([eps]))
+        self.last_route = None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        reset(self.nn)
+        self.eps.data.fill_(self.initial_eps)
+
+    def fused_stages(self, x):
+        """([(W, b, scale, shift)] * 2, activation name) when the whole layer is ONE cwn_gin_layer_f32 launch, else None."""
+        if (not FUSED_GIN or torch.is_grad_enabled() or not isinstance(x, Tensor) or not x.is_cuda or x.dtype != torch.float32
+                or _ffi_dyn()):
+            return None
+        got = _f64_stages(self.nn, 2)
+        if got is None or not (self.eps.is_cuda and self.eps.dtype == torch.float32):
+            return None
+        stages = []
+        for lin, norm in got[0]:
+            fold = _fold_norm(norm, lin.out_features)
+            if fold is None:
+                return None
+            stages.append((lin.weight, lin.bias, fold[0], fold[1]))
+        return (stages, got[1]) if ops.gin_layer_applies(x, stages) else None
+
+    def forward(self, x: Tensor, edge_index: Optional[Tensor], out: Optional[Tensor] = None, act_post: str = 'id') -> Tensor:
+        n = x.size(0)
+        fused = self.fused_stages(x)
+        if fused is not None:
+            self.last_route = 'fused'
+            adj = None
+            if edge_index is not None and edge_index.numel():
+                adj = cached_adjacency(edge_index, n, n)
+            return ops.gin_layer(x, adj, self.eps, fused[0], fused[1], act_post=act_post, out=out)
+        self.last_route = 'generic'
+        if x.is_cuda:
+            adj = None
+            if edge_index is not None and edge_index.numel():
+                adj = cached_adjacency(edge_index, n, n)
+            s = ops.aggregate(adj, n, A=x, self_x=x, eps=self.eps)
+        else:
+            s = (1 + self.eps.to(x.dtype)) * x
+            if edge_index is not None and edge_index.numel():
+                s = torch.zeros_like(x).index_add_(0, edge_index[1], x[edge_index[0]]) + s
+        y = self.nn(s)
+        return y if act_post == 'id' else next(fn for fn, name in ACT_FUNCTIONS if name == act_post)(y)
+
+    def __repr__(self):
+        return f'{self.__class__.__name__}(nn={self.nn})'
+
+
 class InitReduceConv(torch.nn.Module):
     """mp/layers.py:473-487: initial features of d-cells = reduce of their boundary cells'.
 

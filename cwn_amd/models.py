@@ -937,3 +937,229 @@ class RingSparseCIN(torch.nn.Module):
 
     def __repr__(self):
         return self.__class__.__name__
+
+
+# ------------------------------------------------------------------------------------------------
+# The graph baselines (mp/graph_models.py, mp/ring_exp_models.py:76-130): GIN stacks over the vertex graph
+# ------------------------------------------------------------------------------------------------
+def _graph_of(data):
+    """(x, edge_index, batch, mask, number of graphs, target rows) of what a graph model is handed: any object with `x`,
+    `edge_index`, `batch` (and `mask` for RingGIN) as the reference's models take it, or a Complex / ComplexBatch, whose
+    graph is its vertex cochain (nodes.x, nodes.upper_index, nodes.batch, nodes.mask).  A None index is a graph without
+    edges; a missing batch vector is one graph; the number of graphs comes from the container where it knows it
+    (`num_complexes`, `num_graphs`) and from `batch.max() + 1` otherwise; the target rows (ComplexBatch.target_rows) are
+    None where the container has none."""
+    from .complex import Complex
+    if isinstance(data, Complex):
+        v = data.nodes
+        x, edge_index, batch, mask = v.x, v.upper_index, getattr(v, 'batch', None), getattr(v, 'mask', None)
+        size = getattr(data, 'num_complexes', None)
+        rows = data.target_rows(0) if hasattr(data, 'target_rows') else None
+    else:
+        x, edge_index, batch, mask = data.x, data.edge_index, getattr(data, 'batch', None), getattr(data, 'mask', None)
+        size, rows = getattr(data, 'num_graphs', None), None
+    if batch is None:
+        batch, size = torch.zeros(x.size(0), dtype=torch.long, device=x.device), 1
+    if size is None:
+        size = int(batch.max()) + 1 if batch.numel() else 0
+    return x, edge_index, batch, mask, int(size), rows
+
+
+class JumpingKnowledge(torch.nn.Module):
+    """torch_geometric.nn.JumpingKnowledge for the modes without parameters: 'cat' (the layers' outputs side by side) and
+    'max' (their element-wise maximum).  'lstm' is not implemented."""
+
+    def __init__(self, mode: str):
+        super().__init__()
+        self.mode = mode.lower()
+        if self.mode == 'lstm':
+            raise NotImplementedError("JumpingKnowledge mode 'lstm' is not implemented: 'cat' and 'max' are")
+        if self.mode not in ('cat', 'max'):
+            raise ValueError(f"JumpingKnowledge mode {mode!r}: 'cat' or 'max'")
+
+    def reset_parameters(self):
+        pass
+
+    def forward(self, xs):
+        if self.mode == 'cat':
+            return torch.cat(xs, dim=-1)
+        return torch.stack(xs, dim=-1).max(dim=-1)[0]
+
+    def __repr__(self):
+        return f'{self.__class__.__name__}({self.mode})'
+
+
+def _gin_network(k_in: int, hidden: int, norm, act_module):
+    return torch.nn.Sequential(Linear(k_in, hidden), norm(hidden), act_module(), Linear(hidden, hidden), norm(hidden), act_module())
+
+
+class _GINStack(torch.nn.Module):
+    """What GIN0, GIN, GIN0WithJK and GINWithJK (mp/graph_models.py) share: conv1 and convs of layers.GINConv over
+    Linear -> BatchNorm -> act -> Linear -> BatchNorm -> act, an optional JumpingKnowledge, the readout per graph,
+    act(lin1) -> dropout -> lin2.  In inference on the GPU every layer is one launch (layers.FUSED_GIN), JumpingKnowledge
+    'cat' costs nothing (layer l writes columns [l H, (l + 1) H) of one buffer and layer l + 1 reads them in place) and the
+    head of the models without JumpingKnowledge is one ops.agnostic_head launch over the one pooled matrix."""
+
+    def _build(self, num_features, num_layers, hidden, num_classes, readout, dropout_rate, nonlinearity, train_eps, mode=None):
+        if readout not in ('sum', 'mean'):
+            raise NotImplementedError(f'Readout {readout} is not currently supported.')
+        self.readout = readout
+        self.dropout_rate = dropout_rate
+        self.nonlinearity = nonlinearity
+        act_module = get_nonlinearity(nonlinearity, return_module=True)
+        self.conv1 = layers.GINConv(_gin_network(num_features, hidden, BN, act_module), train_eps=train_eps)
+        self.convs = torch.nn.ModuleList(layers.GINConv(_gin_network(hidden, hidden, BN, act_module), train_eps=train_eps)
+                                         for _ in range(num_layers - 1))
+        if mode is not None:
+            self.jump = JumpingKnowledge(mode)
+        self.lin1 = Linear(num_layers * hidden if mode is not None and self.jump.mode == 'cat' else hidden, hidden)
+        self.lin2 = Linear(hidden, num_classes)
+
+    def reset_parameters(self):
+        self.conv1.reset_parameters()
+        for conv in self.convs:
+            conv.reset_parameters()
+        if hasattr(self, 'jump'):
+            self.jump.reset_parameters()
+        self.lin1.reset_parameters()
+        self.lin2.reset_parameters()
+
+    def pooling_fn(self, x, batch, size: int):
+        """global_add_pool / global_mean_pool: the segmented-reduce kernel on the GPU, index_add_ on the CPU."""
+        mean = self.readout == 'mean'
+        if x.is_cuda:
+            return global_pool(x, batch, size, mean=mean)
+        p = torch.zeros(size, x.size(-1), dtype=x.dtype).index_add_(0, batch, x)
+        if mean:
+            p = p / torch.bincount(batch, minlength=size).clamp(min=1).to(x.dtype).unsqueeze(1)
+        return p
+
+    def _layers_cat(self, convs, x, edge_index):
+        """JumpingKnowledge('cat') through ONE [n, L H] buffer when every layer takes the fused route; torch.cat otherwise."""
+        H, L = self.lin2.in_features, len(convs)
+        buf = torch.empty(x.size(0), L * H, dtype=x.dtype, device=x.device) if convs[0].fused_stages(x) is not None else None
+        xs = []
+        for l, conv in enumerate(convs):
+            x = conv(x, edge_index, out=None if buf is None else buf[:, l * H:(l + 1) * H])
+            xs.append(x)
+        if buf is not None and all(conv.last_route == 'fused' for conv in convs):
+            return buf
+        return torch.cat(xs, dim=-1)
+
+    def _head_fused(self, pooled):
+        """lin2(act(lin1(pooled))) as one ops.agnostic_head launch (one pooled matrix: its sum over the dimensions is that
+        matrix's term), or None where it does not apply."""
+        if torch.is_grad_enabled() or (self.training and self.dropout_rate > 0) or hasattr(self, 'jump') or not pooled.is_cuda:
+            return None
+        H, O = self.lin1.out_features, self.lin2.out_features
+        ts = [t for t in (self.lin1.weight, self.lin1.bias, self.lin2.weight, self.lin2.bias) if t is not None]
+        if (self.nonlinearity not in ops.ACT_CODES or pooled.dtype not in _ffi.FLOAT_DTYPES or self.lin1.in_features != H
+                or not (1 <= H <= _ffi.AGNOSTIC_MAX_WIDTH and 1 <= O <= _ffi.AGNOSTIC_MAX_WIDTH)
+                or any(t.dtype != pooled.dtype or not t.is_cuda for t in ts)):
+            return None
+        return ops.agnostic_head([pooled], self.lin1.weight, self.lin1.bias, self.lin2.weight, self.lin2.bias, self.nonlinearity)
+
+    @_one_check
+    def forward(self, data):
+        x, edge_index, batch, _, size, _ = _graph_of(data)
+        convs = [self.conv1] + list(self.convs)
+        jump = getattr(self, 'jump', None)
+        if jump is not None and jump.mode == 'cat':
+            x = self._layers_cat(convs, x, edge_index)
+        else:
+            xs = []
+            for conv in convs:
+                x = conv(x, edge_index)
+                xs.append(x)
+            if jump is not None:
+                x = jump(xs)
+        x = self.pooling_fn(x, batch, size)
+        out = self._head_fused(x)
+        if out is not None:
+            return out
+        x = get_nonlinearity(self.nonlinearity, return_module=False)(self.lin1(x))
+        x = F.dropout(x, p=self.dropout_rate, training=self.training)
+        return self.lin2(x)
+
+    def __repr__(self):
+        return self.__class__.__name__
+
+
+class GIN0(_GINStack):
+    """mp/graph_models.py:33-85: GINConv layers with eps fixed at 0."""
+
+    def __init__(self, num_features, num_layers, hidden, num_classes, readout='sum', dropout_rate=0.5, nonlinearity='relu'):
+        super().__init__()
+        self._build(num_features, num_layers, hidden, num_classes, readout, dropout_rate, nonlinearity, train_eps=False)
+
+
+class GIN0WithJK(_GINStack):
+    """mp/graph_models.py:88-148: GIN0 with JumpingKnowledge over the layers' outputs."""
+
+    def __init__(self, num_features, num_layers, hidden, num_classes, mode='cat', readout='sum', dropout_rate=0.5,
+                 nonlinearity='relu'):
+        super().__init__()
+        self._build(num_features, num_layers, hidden, num_classes, readout, dropout_rate, nonlinearity, train_eps=False, mode=mode)
+
+
+class GIN(_GINStack):
+    """mp/graph_models.py:151-203: GINConv layers with a trained eps."""
+
+    def __init__(self, num_features, num_layers, hidden, num_classes, readout='sum', dropout_rate=0.5, nonlinearity='relu'):
+        super().__init__()
+        self._build(num_features, num_layers, hidden, num_classes, readout, dropout_rate, nonlinearity, train_eps=True)
+
+
+class GINWithJK(_GINStack):
+    """mp/graph_models.py:206-266: GIN with JumpingKnowledge over the layers' outputs."""
+
+    def __init__(self, num_features, num_layers, hidden, num_classes, mode='cat', readout='sum', dropout_rate=0.5,
+                 nonlinearity='relu'):
+        super().__init__()
+        self._build(num_features, num_layers, hidden, num_classes, readout, dropout_rate, nonlinearity, train_eps=True, mode=mode)
+
+
+class RingGIN(torch.nn.Module):
+    """mp/ring_exp_models.py:76-130, the graph baseline of the ring-transfer experiment (exp/run_ring_exp.py): init_linear,
+    act(conv1), the further GINConv layers, and the prediction read off the ONE marked vertex of every graph -- ops.target_head
+    on `data.target_rows(0)` where the batch has them, `lin1(x[mask])` literally otherwise.  Same constructor arguments,
+    attributes and state_dict keys as the reference.  A ring of n vertices needs n // 2 layers: a layer moves the label one
+    hop."""
+
+    def __init__(self, num_features, num_layers, hidden, num_classes, nonlinearity='relu', graph_norm='bn'):
+        super().__init__()
+        self.nonlinearity = nonlinearity
+        act_module = get_nonlinearity(nonlinearity, return_module=True)
+        self.init_linear = Linear(num_features, num_features)
+        self.graph_norm = get_graph_norm(graph_norm)
+        self.conv1 = layers.GINConv(_gin_network(num_features, hidden, self.graph_norm, act_module), train_eps=False)
+        self.convs = torch.nn.ModuleList(layers.GINConv(_gin_network(hidden, hidden, self.graph_norm, act_module), train_eps=False)
+                                         for _ in range(num_layers - 1))
+        self.lin1 = Linear(hidden, num_classes)
+
+    def reset_parameters(self):
+        self.init_linear.reset_parameters()
+        self.conv1.reset_parameters()
+        for conv in self.convs:
+            conv.reset_parameters()
+        self.lin1.reset_parameters()
+
+    def _init(self, x: torch.Tensor) -> torch.Tensor:
+        lin = self.init_linear
+        if x.is_cuda and x.dtype == torch.float32 and lin.weight.dtype == torch.float32 and lin.in_features <= ops.GEMM_MAX_K:
+            return ops.gemm_many([ops.Gemm(X=x, W=lin.weight, bias=lin.bias)])[0]
+        return lin(x)
+
+    @_one_check
+    def forward(self, data):
+        x, edge_index, _, mask, _, rows = _graph_of(data)
+        x = self._init(x)
+        x = self.conv1(x, edge_index, act_post=self.nonlinearity)        # act(conv1(x)), :121
+        for conv in self.convs:
+            x = conv(x, edge_index)
+        if rows is not None and x.is_cuda:
+            return ops.target_head(x, rows, self.lin1.weight, self.lin1.bias)
+        return self.lin1(x[mask])                                        # :125-126 literally
+
+    def __repr__(self):
+        return self.__class__.__name__

@@ -2432,6 +2432,111 @@ def agnostic_head(pooled, lin1_w: Tensor, lin1_b: Optional[Tensor], lin2_w: Tens
 
 
 # ------------------------------------------------------------------------------------------------
+# GINConv as one launch (csrc/cwn_gin.hip): the layer of the graph baselines, float32, inference only
+# ------------------------------------------------------------------------------------------------
+def _gin_f32(t, name: str, dim: int) -> Optional[Tensor]:
+    """An operand of cwn_gin_layer_f32: a float32 tensor on the GPU with contiguous rows (2-D: a row stride is allowed)."""
+    if t is None:
+        return None
+    if not isinstance(t, Tensor) or t.dtype != torch.float32:
+        raise TypeError(f'gin_layer: {name} must be float32 (got {getattr(t, "dtype", type(t).__name__)}): cwn_gin_layer_f32 computes '
+                        'in fp32 only (float64 and training run through ops.aggregate and the torch modules: layers.GINConv)')
+    if not t.is_cuda:
+        raise TypeError(f'gin_layer: {name} must be a float32 tensor on the GPU (got {t.dtype} on {t.device})')
+    if t.dim() != dim or (t.numel() and t.stride(-1) != 1) or (dim == 2 and t.size(0) > 1 and t.stride(0) < t.size(1)):
+        raise TypeError(f'gin_layer: {name} must be a {dim}-D float32 tensor with contiguous rows (shape {tuple(t.shape)}, '
+                        f'strides {tuple(t.stride())})')
+    return t
+
+
+def gin_layer_applies(x: Tensor, stages) -> bool:
+    """Does cwn_gin_layer_f32 take these operands?  `stages`: two (weight, bias, scale, shift) tuples, the two (Linear,
+    folded norm) groups of a GINConv's network.  float32 on the GPU, x [n, w] with contiguous rows, weights [H, w] and
+    [H, H] contiguous, 1 <= w, H <= 128, the vectors [H] or None."""
+    if not (isinstance(x, Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2
+            and (x.numel() == 0 or x.stride(1) == 1) and (x.size(0) <= 1 or x.stride(0) >= x.size(1))):
+        return False
+    if len(stages) != 2 or any(len(s) != 4 for s in stages):
+        return False
+    (W1, _, _, _), (W2, _, _, _) = stages
+    if not all(isinstance(W, Tensor) and W.dim() == 2 and W.is_contiguous() for W in (W1, W2)):
+        return False
+    H, w = int(W1.size(0)), int(W1.size(1))
+    if tuple(W2.shape) != (H, H) or x.size(1) != w or not (1 <= w <= _ffi.GIN_MAX_WIDTH and 1 <= H <= _ffi.GIN_MAX_WIDTH):
+        return False
+    for W, b, sc, sh in stages:
+        if not (W.is_cuda and W.dtype == torch.float32):
+            return False
+        for v in (b, sc, sh):
+            if v is not None and not (isinstance(v, Tensor) and v.is_cuda and v.dtype == torch.float32
+                                      and tuple(v.shape) == (H,) and v.is_contiguous()):
+                return False
+    return True
+
+
+def gin_layer(x: Tensor, adj: Optional[Adjacency], eps, stages, act, act_post='id', out: Optional[Tensor] = None) -> Tensor:
+    """A whole GINConv (torch_geometric's definition, `edge_index[0]` the source) in inference as ONE launch:
+
+        s   = A x + (1 + eps) * x          (A: `adj`, a destination-sorted plan over the rows of x; None: no edges)
+        h   = act((s W1^T + b1) * scale1 + shift1)
+        out = act_post(act((h W2^T + b2) * scale2 + shift2))
+
+    `stages`: [(W1, b1, scale1, shift1), (W2, b2, scale2, shift2)] -- weights as torch.nn.Linear holds them, an eval-mode
+    norm folded to a per-column affine (layers._fold_norm), any of bias / scale / shift None.  `eps`: a float32 tensor of
+    one element on the device (GINConv's buffer or Parameter: it is read by the kernel, never on the host), None or a
+    Python number.  `act` / `act_post`: 'id', 'relu', 'elu', 'tanh', 'sigmoid' or a CWN_ACT_* code.  `out`: a [n, H]
+    float32 view to write into -- a column slice of a JumpingKnowledge('cat') buffer, which x may be another slice of as long
+    as the two do not overlap; nothing outside it is written.  Inference only: under a recording autograd (an operand that
+    requires a gradient while gradients are enabled) this raises instead of detaching.  float32 on the GPU and widths up to
+    128 (`gin_layer_applies`); another dtype or device is a TypeError that names it, never a fallback."""
+    x = _gin_f32(x, 'x', 2)
+    if len(stages) != 2 or any(len(s) != 4 for s in stages):
+        raise ValueError('gin_layer: stages is [(W1, b1, scale1, shift1), (W2, b2, scale2, shift2)]')
+    named = []
+    for k, (W, b, sc, sh) in enumerate(stages, 1):
+        named.append((_gin_f32(W, f'W{k}', 2), _gin_f32(b, f'b{k}', 1), _gin_f32(sc, f'scale{k}', 1), _gin_f32(sh, f'shift{k}', 1)))
+    if isinstance(eps, Tensor):
+        eps = _gin_f32(eps.reshape(-1), 'eps', 1)
+        if eps.numel() != 1:
+            raise ValueError(f'gin_layer: eps holds {eps.numel()} elements, not one')
+    elif eps is not None:
+        eps = None if float(eps) == 0.0 else torch.full((1,), float(eps), dtype=torch.float32, device=x.device)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in [x, eps] + [t for s in named for t in s]):
+        raise RuntimeError('gin_layer is inference only (cwn_gin_layer_f32 has no backward) and an operand requires a gradient '
+                           'while autograd is recording: run it under torch.no_grad(), or use layers.GINConv, whose '
+                           'generic route is differentiable')
+    if _ffi.DYN_ROWS:
+        raise RuntimeError('gin_layer takes host row counts: it does not run under _ffi.dynamic_rows (a static batch)')
+    named = [tuple(None if t is None else t.contiguous() for t in s) for s in named]
+    if not gin_layer_applies(x, named):
+        raise ValueError(f'gin_layer takes x [n, w], W1 [H, w], W2 [H, H] with 1 <= w, H <= {_ffi.GIN_MAX_WIDTH} and vectors '
+                         f'[H]: x {tuple(x.shape)}, W1 {tuple(named[0][0].shape)}, W2 {tuple(named[1][0].shape)}')
+    n, w = int(x.size(0)), int(x.size(1))
+    H = int(named[0][0].size(0))
+    if out is None:
+        out = torch.empty(n, H, dtype=torch.float32, device=x.device)
+    else:
+        out = _gin_f32(out, 'out', 2)
+        if tuple(out.shape) != (n, H) or out.device != x.device:
+            raise ValueError(f'gin_layer: out is {tuple(out.shape)} on {out.device}, the result {(n, H)} on {x.device}')
+    if n == 0:
+        return out
+    d = _ffi.GinDesc(x=x.data_ptr(), eps_dev=_ffi.ptr(eps), out=out.data_ptr(), n=n, ldx=_ld(x), ldout=_ld(out), w=w, H=H,
+                     act=_act_code(act), act_post=_act_code(act_post))
+    (d.W1, d.b1, d.scale1, d.shift1), (d.W2, d.b2, d.scale2, d.shift2) = [[_ffi.ptr(t) for t in s] for s in named]
+    if adj is not None and adj.n_entries:
+        if adj.n_dst != n or adj.n_val != n:
+            raise ValueError(f'gin_layer: adjacency over {adj.n_val} -> {adj.n_dst} rows, x has {n}')
+        if not adj.built:
+            from .csr import build_many
+            build_many([adj])
+        wait_ready([adj])
+        d.rowptr, d.col = adj.rowptr.data_ptr(), adj.col.data_ptr()
+    _ffi.gin_layer(d, x.device)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # gemm_many + aggregate_many of one propagate step as ONE autograd node
 # ------------------------------------------------------------------------------------------------
 FUSED_PROPAGATE_NODE = os.environ.get('CWN_FUSED_PROPAGATE_NODE') != '0'     # A/B: '0' keeps the two nodes

@@ -1441,6 +1441,65 @@ int cwn_agnostic_head_f32(const cwn_agnostic_head_desc* desc_host, cwn_stream_t 
 int cwn_agnostic_head_f64(const cwn_agnostic_head_desc_f64* desc_host, cwn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * GINConv as one launch (csrc/cwn_gin.hip), float32, inference.
+ *
+ * Replaces the whole forward of a torch_geometric GINConv whose `nn` is the two-stage network of every graph baseline of
+ * the reference (mp/graph_models.py: GIN0, GIN, GIN0WithJK, GINWithJK; mp/ring_exp_models.py:76-130: RingGIN) -- the
+ * aggregation, two Linear maps, two eval-mode norms and two activations:
+ *
+ *     s   = (sum over the entries p of row i, in CSR order, of x[col[p], :]) + (1 + eps) * x[i, :]          [n, w]
+ *     h   = act( (s W1^T + b1) * scale1 + shift1 )                                                          [n, H]
+ *     out = act_post( act( (h W2^T + b2) * scale2 + shift2 ) )                                              [n, H]
+ *
+ * A workgroup of 256 owns CWN_GIN_TM destination rows: it folds their entries into an LDS panel, multiplies the panel with
+ * W1 on v_mfma_f32_16x16x4_f32 (exact fp32), keeps h in a second LDS panel and multiplies that with W2: s and h never reach
+ * memory.  A row's entries are added one after the other in CSR order whatever its length (rows above CWN_LONG_ROW
+ * included: there are no long-row lists), then (1 + eps) * x is added; a row without entries gets (1 + eps) * x.  No
+ * atomics: two launches on the same operands give the same bits.
+ *
+ *   - 1 <= w <= CWN_GIN_MAX_WIDTH and 1 <= H <= CWN_GIN_MAX_WIDTH, any value.  n == 0: nothing is launched.
+ *   - rowptr / col: the destination-sorted plan of cwn_csr_build over the n rows (col[p] in [0, n)).  rowptr == NULL: a
+ *     graph without edges.
+ *   - W1 [H, w] and W2 [H, H] row-major with row strides w and H, as torch.nn.Linear holds them; b1 / b2 [H] or NULL.
+ *   - scale / shift [H]: an eval-mode BatchNorm as a per-column affine (weight / sqrt(var + eps), bias - mean * scale);
+ *     NULL: identity (each of the four on its own).
+ *   - eps_dev: a DEVICE float (GINConv(train_eps=True) keeps eps in a Parameter; reading it on the host would
+ *     synchronise), or NULL: 0.
+ *   - act: the activation of both stages.  act_post: a second activation on the result (RingGIN's `act(conv1(x))`);
+ *     CWN_ACT_ID everywhere else.
+ *   - x and out carry row strides ldx >= w and ldout >= H: they may be two column slices of one [n, L * H] buffer
+ *     (JumpingKnowledge('cat')) as long as the slices do not overlap.  Nothing outside out[:, 0 .. H) is written.
+ *   - n is a HOST count: there is NO m_dev and no static batch reaches this launch.
+ * CWN_ERR_BAD_ARG: a NULL descriptor, a width outside [1, 128], n < 0, an unknown act / act_post, rowptr without col, and
+ * for n > 0 a NULL x / out / W1 / W2, ldx < w, ldout < H, out overlapping x (the same address, or column slices of one
+ * stride whose columns meet).  CWN_ERR_ALIGN: a pointer off 4 bytes.  CWN_ERR_TOO_LARGE: more than INT32_MAX - 1 tiles.
+ * All checks precede the first HIP call; the launcher neither allocates nor synchronises.
+ * ------------------------------------------------------------------------------------------ */
+#define CWN_GIN_MAX_WIDTH 128   /* widest x / out row of cwn_gin_layer_f32 */
+#define CWN_GIN_TM 32           /* destination rows per workgroup, at every width */
+
+typedef struct cwn_gin_desc {
+    const float* x;            /* [n, w] row stride ldx */
+    const int32_t* rowptr;     /* [n + 1], or NULL: no entries */
+    const int32_t* col;        /* [E] source row per CSR position */
+    const float* eps_dev;      /* device float, or NULL (0) */
+    const float* W1;           /* [H, w] */
+    const float* b1;           /* [H] or NULL */
+    const float* scale1;       /* [H] or NULL */
+    const float* shift1;       /* [H] or NULL */
+    const float* W2;           /* [H, H] */
+    const float* b2;
+    const float* scale2;
+    const float* shift2;
+    float* out;                /* [n, H] row stride ldout */
+    int64_t n, ldx, ldout;     /* n: host count */
+    int32_t w, H;
+    int32_t act;               /* CWN_ACT_*, both stages */
+    int32_t act_post;          /* CWN_ACT_*, applied to the result */
+} cwn_gin_desc;
+int cwn_gin_layer_f32(const cwn_gin_desc* desc_host, cwn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Device-side batching (collate): build the arrays of a ComplexBatch from a dataset that is
  * resident in HBM in packed form, with ONE launch.
  *
