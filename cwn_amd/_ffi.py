@@ -697,15 +697,20 @@ def require_gpu(t: torch.Tensor, name: str):
 FLOAT_DTYPES = (torch.float32, torch.float64)     # what the aggregate and gather kernels compute in
 
 
+def typed_entry(stem: str, dtype: torch.dtype):
+    """(function, name) of the entry point cwn_<stem>_f32 or cwn_<stem>_f64 that computes in `dtype`."""
+    L = lib()
+    if dtype not in FLOAT_DTYPES:
+        raise TypeError(f'{stem} computes in float32 or float64, not {dtype}')
+    name = f'cwn_{stem}_f32' if dtype == torch.float32 else f'cwn_{stem}_f64'
+    return getattr(L, name), name
+
+
 def aggregate(descs: Sequence[AggDesc], device, dtype: torch.dtype = torch.float32) -> None:
     """One kernel launch for up to MAX_DESCS descriptors; more are split into several calls.  Every operand of
     every descriptor has the one `dtype` (float32 or float64)."""
-    L = lib()
+    fn, name = typed_entry('aggregate', dtype)
     s = stream_ptr(device)
-    if dtype not in FLOAT_DTYPES:
-        raise TypeError(f'aggregate computes in float32 or float64, not {dtype}')
-    name = 'cwn_aggregate_f32' if dtype == torch.float32 else 'cwn_aggregate_f64'
-    fn = getattr(L, name)
     _set_dyn(descs, 'n_dst')
     for i in range(0, len(descs), MAX_DESCS):
         chunk = descs[i:i + MAX_DESCS]
@@ -717,12 +722,8 @@ def aggregate_act(descs: Sequence[AggActDesc], device, dtype: torch.dtype = torc
     """The activated two-operand message (csrc/cwn_aggregate_act.hip): one kernel launch for up to MAX_DESCS descriptors,
     more are split into several calls.  Every operand of every descriptor has the one `dtype`.  Row counts are host
     counts: the descriptor has no m_dev, so nothing is looked up in DYN_ROWS."""
-    L = lib()
+    fn, name = typed_entry('aggregate_act', dtype)
     s = stream_ptr(device)
-    if dtype not in FLOAT_DTYPES:
-        raise TypeError(f'aggregate_act computes in float32 or float64, not {dtype}')
-    name = 'cwn_aggregate_act_f32' if dtype == torch.float32 else 'cwn_aggregate_act_f64'
-    fn = getattr(L, name)
     for i in range(0, len(descs), MAX_DESCS):
         chunk = descs[i:i + MAX_DESCS]
         arr = (AggActDesc * len(chunk))(*chunk)

@@ -1,0 +1,53 @@
+// cwn_act.h -- the five activations of the CWN_ACT_* codes (include/cwn_hip.h), written once for every kernel that applies
+// one: the library's own functions, no fast intrinsics.  A kernel templated on the code calls activate<ACT>; one that
+// takes the code as an argument calls activate_rt.  File-local names, as the per-file copies were: include and call.
+#pragma once
+#include <hip/hip_runtime.h>
+#include "../../include/cwn_hip.h"
+
+namespace {
+
+template <int ACT>
+__device__ __forceinline__ float activate(float z) {
+    if constexpr (ACT == CWN_ACT_RELU) return fmaxf(z, 0.f);
+    else if constexpr (ACT == CWN_ACT_ELU) return z > 0.f ? z : expm1f(z);
+    else if constexpr (ACT == CWN_ACT_TANH) return tanhf(z);
+    else if constexpr (ACT == CWN_ACT_SIGMOID) return 1.0f / (1.0f + expf(-z));
+    else return z;
+}
+
+template <int ACT>
+__device__ __forceinline__ double activate(double v) {
+    if constexpr (ACT == CWN_ACT_RELU) return v < 0.0 ? 0.0 : v;
+    else if constexpr (ACT == CWN_ACT_ELU) return v > 0.0 ? v : expm1(v);
+    else if constexpr (ACT == CWN_ACT_TANH) return tanh(v);
+    else if constexpr (ACT == CWN_ACT_SIGMOID) return 1.0 / (1.0 + exp(-v));
+    else return v;
+}
+
+template <class real>
+__device__ __forceinline__ real activate_rt(real z, int act) {
+    switch (act) {
+        case CWN_ACT_RELU: return activate<CWN_ACT_RELU>(z);
+        case CWN_ACT_ELU: return activate<CWN_ACT_ELU>(z);
+        case CWN_ACT_TANH: return activate<CWN_ACT_TANH>(z);
+        case CWN_ACT_SIGMOID: return activate<CWN_ACT_SIGMOID>(z);
+        default: return z;
+    }
+}
+
+// act'(z) as a function of out = act(z)
+__device__ __forceinline__ float act_grad(int act, float o) {
+    switch (act) {
+        case CWN_ACT_RELU: return o > 0.f ? 1.f : 0.f;
+        case CWN_ACT_ELU: return o > 0.f ? 1.f : o + 1.f;
+        case CWN_ACT_TANH: return 1.f - o * o;
+        case CWN_ACT_SIGMOID: return o * (1.f - o);
+        default: return 1.f;
+    }
+}
+
+// is `act` one of the CWN_ACT_* codes?  (host)
+inline bool known_act(int act) { return act >= CWN_ACT_ID && act <= CWN_ACT_SIGMOID; }
+
+}  // namespace

@@ -139,8 +139,8 @@ extern "C" int cwn_aggregate_f32(const cwn_agg_desc* descs, int n, cwn_stream_t 
         for (const void* p : ptrs) {
             if (p == nullptr) continue;
             if (((uintptr_t)p & 3u) != 0) return CWN_ERR_ALIGN;
-            if (v == 4 && !aligned16(p)) v = aligned8(p) ? 2 : 1;
-            if (v == 2 && !aligned8(p)) v = 1;
+            if (v == 4 && !al16(p)) v = al8(p) ? 2 : 1;
+            if (v == 2 && !al8(p)) v = 1;
         }
         if (v < vec) vec = v;
     }
@@ -181,8 +181,8 @@ extern "C" int cwn_gather_rows_f32(const float* src, int64_t n_src, int64_t F, c
     if (src == nullptr || idx == nullptr || out == nullptr) return CWN_ERR_BAD_ARG;
     if ((((uintptr_t)src) | ((uintptr_t)out)) & 3u) return CWN_ERR_ALIGN;
     int vec = (F % 4 == 0) ? 4 : (F % 2 == 0 ? 2 : 1);
-    if (vec == 4 && !(aligned16(src) && aligned16(out))) vec = 2;
-    if (vec == 2 && !(aligned8(src) && aligned8(out))) vec = 1;
+    if (vec == 4 && !(al16(src) && al16(out))) vec = 2;
+    if (vec == 2 && !(al8(src) && al8(out))) vec = 1;
     const int G = pick_group((int)F, vec);
     const int rows_per_block = kThreads / G;
     const int64_t blocks = (n_idx + rows_per_block - 1) / rows_per_block;

@@ -21,6 +21,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/cwn_hip.h"
+#include "cwn_act.h"
+#include "cwn_check.h"
 #include "cwn_mem.h"
 
 namespace {
@@ -120,25 +122,6 @@ __device__ __forceinline__ const real* row_at(const real* base, int64_t idx, int
 template <bool SMALL, class real>
 __device__ __forceinline__ real* row_at(real* base, int64_t idx, int F, int f) {
     return const_cast<real*>(row_at<SMALL>(const_cast<const real*>(base), idx, F, f));
-}
-
-// the activations of cwn_oriented.hip (float) and cwn_dense_f64.hip (double): the library's own functions, no fast intrinsics
-template <int ACT>
-__device__ __forceinline__ float activate(float z) {
-    if constexpr (ACT == CWN_ACT_RELU) return fmaxf(z, 0.f);
-    else if constexpr (ACT == CWN_ACT_ELU) return z > 0.f ? z : expm1f(z);
-    else if constexpr (ACT == CWN_ACT_TANH) return tanhf(z);
-    else if constexpr (ACT == CWN_ACT_SIGMOID) return 1.0f / (1.0f + expf(-z));
-    else return z;
-}
-
-template <int ACT>
-__device__ __forceinline__ double activate(double v) {
-    if constexpr (ACT == CWN_ACT_RELU) return v < 0.0 ? 0.0 : v;
-    else if constexpr (ACT == CWN_ACT_ELU) return v > 0.0 ? v : expm1(v);
-    else if constexpr (ACT == CWN_ACT_TANH) return tanh(v);
-    else if constexpr (ACT == CWN_ACT_SIGMOID) return 1.0 / (1.0 + exp(-v));
-    else return v;
 }
 
 // acc += act(a + b): one add for the pre-activation, in the element type
@@ -417,8 +400,6 @@ inline int pow2_at_least(int v) {
     return p;
 }
 
-inline bool aligned_to(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 // Validation, the per-descriptor geometry and the launch.  Neither allocates nor synchronises.
 template <class real>
 int launch_act(const typename DescOf<real>::type* descs, int n, cwn_stream_t stream_) {
@@ -431,7 +412,7 @@ int launch_act(const typename DescOf<real>::type* descs, int n, cwn_stream_t str
     for (int i = 0; i < n; ++i) {
         const Desc& D = descs[i];
         if (D.F <= 0 || D.n_dst < 0 || (D.n_dst > 0 && D.out == nullptr)) return CWN_ERR_BAD_ARG;
-        if (D.act < CWN_ACT_ID || D.act > CWN_ACT_SIGMOID) return CWN_ERR_BAD_ARG;
+        if (!known_act(D.act)) return CWN_ERR_BAD_ARG;
         if (D.rowptr != nullptr && (D.ia == nullptr || D.ib == nullptr || D.A == nullptr || D.B == nullptr)) return CWN_ERR_BAD_ARG;
         if (D.n_dst >= INT32_MAX) return CWN_ERR_TOO_LARGE;
         // widest vector every pointer and the row stride allow: 16 bytes, 8, or one element

@@ -11,6 +11,7 @@
 // so the device assembly of both files is held fixed across edits here (tools/isa_diff.sh).
 // Aliases, not a template parameter, for that reason: nothing about a symbol's name changes.
 #pragma once
+#include "cwn_check.h"
 
 namespace {
 
@@ -371,9 +372,6 @@ inline int pick_group(int F, int vec) {
     int g = pow2_at_least((F + vec - 1) / vec);
     return g > 64 ? 64 : g;
 }
-
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-inline bool aligned8(const void* p) { return ((uintptr_t)p & 7u) == 0; }
 
 // CWN_OK, or why a descriptor is refused whatever its element type
 inline int check_desc(const desc_t& D) {

@@ -133,12 +133,12 @@ extern "C" int cwn_aggregate_f64(const cwn_agg_desc_f64* descs, int n, cwn_strea
                               D.self_pre, D.out, D.self_x2};
         for (const void* p : ptrs) {
             if (p == nullptr) continue;
-            if (!aligned8(p)) return CWN_ERR_ALIGN;
-            if (v == 2 && !aligned16(p)) v = 1;
+            if (!al8(p)) return CWN_ERR_ALIGN;
+            if (v == 2 && !al16(p)) v = 1;
         }
         const void* scalars[] = {D.b_width == 1 ? (const void*)D.B : nullptr, D.eps, D.eps2};
         for (const void* p : scalars)
-            if (p != nullptr && !aligned8(p)) return CWN_ERR_ALIGN;
+            if (p != nullptr && !al8(p)) return CWN_ERR_ALIGN;
         if (v < vec) vec = v;
     }
     for (int i = 0; i < n; ++i) {
@@ -176,7 +176,7 @@ extern "C" int cwn_gather_rows_f64(const double* src, int64_t n_src, int64_t F, 
     if (src == nullptr || idx == nullptr || out == nullptr) return CWN_ERR_BAD_ARG;
     if ((((uintptr_t)src) | ((uintptr_t)out)) & 7u) return CWN_ERR_ALIGN;
     int vec = (F % 2 == 0) ? 2 : 1;
-    if (vec == 2 && !(aligned16(src) && aligned16(out))) vec = 1;
+    if (vec == 2 && !(al16(src) && al16(out))) vec = 1;
     const int G = pick_group((int)F, vec);
     const int rows_per_block = kThreads / G;
     const int64_t blocks = (n_idx + rows_per_block - 1) / rows_per_block;

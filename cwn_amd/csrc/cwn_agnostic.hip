@@ -29,6 +29,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/cwn_hip.h"
+#include "cwn_act.h"
+#include "cwn_check.h"
 
 namespace {
 
@@ -61,36 +63,6 @@ struct PoolBatch {
 
 __device__ __forceinline__ float fmad(float a, float b, float c) { return fmaf(a, b, c); }
 __device__ __forceinline__ double fmad(double a, double b, double c) { return fma(a, b, c); }
-
-// the activations of cwn_aggregate_act.hip: the library's own functions, no fast intrinsics
-template <int ACT>
-__device__ __forceinline__ float activate(float z) {
-    if constexpr (ACT == CWN_ACT_RELU) return fmaxf(z, 0.f);
-    else if constexpr (ACT == CWN_ACT_ELU) return z > 0.f ? z : expm1f(z);
-    else if constexpr (ACT == CWN_ACT_TANH) return tanhf(z);
-    else if constexpr (ACT == CWN_ACT_SIGMOID) return 1.0f / (1.0f + expf(-z));
-    else return z;
-}
-
-template <int ACT>
-__device__ __forceinline__ double activate(double v) {
-    if constexpr (ACT == CWN_ACT_RELU) return v < 0.0 ? 0.0 : v;
-    else if constexpr (ACT == CWN_ACT_ELU) return v > 0.0 ? v : expm1(v);
-    else if constexpr (ACT == CWN_ACT_TANH) return tanh(v);
-    else if constexpr (ACT == CWN_ACT_SIGMOID) return 1.0 / (1.0 + exp(-v));
-    else return v;
-}
-
-template <class real>
-__device__ __forceinline__ real activate_rt(real z, int act) {
-    switch (act) {
-        case CWN_ACT_RELU: return activate<CWN_ACT_RELU>(z);
-        case CWN_ACT_ELU: return activate<CWN_ACT_ELU>(z);
-        case CWN_ACT_TANH: return activate<CWN_ACT_TANH>(z);
-        case CWN_ACT_SIGMOID: return activate<CWN_ACT_SIGMOID>(z);
-        default: return z;
-    }
-}
 
 // ---- cwn_embed_pool_* --------------------------------------------------------------------------------------------------
 
@@ -173,8 +145,6 @@ __global__ __launch_bounds__(kThreads) void embed_pool_kernel(PoolBatch<real> B)
     }
 }
 
-inline bool aligned_to(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 template <class real>
 int launch_pool(const typename PoolDescOf<real>::type* descs, int n, cwn_stream_t stream_) {
     using Desc = typename PoolDescOf<real>::type;
@@ -185,7 +155,7 @@ int launch_pool(const typename PoolDescOf<real>::type* descs, int n, cwn_stream_
     for (int i = 0; i < n; ++i) {
         const Desc& D = descs[i];
         if (D.K < 1 || D.K > CWN_EMBED_POOL_MAX_K || D.H < 1 || D.H > CWN_AGNOSTIC_MAX_WIDTH) return CWN_ERR_BAD_ARG;
-        if (D.act < CWN_ACT_ID || D.act > CWN_ACT_SIGMOID || (D.mean != 0 && D.mean != 1)) return CWN_ERR_BAD_ARG;
+        if (!known_act(D.act) || (D.mean != 0 && D.mean != 1)) return CWN_ERR_BAD_ARG;
         if (D.N < 0 || D.C < 0 || D.ldx < D.K || D.ldw < D.K || D.ldo < D.H) return CWN_ERR_BAD_ARG;
         if (D.N > 0 && (D.x == nullptr || D.W == nullptr)) return CWN_ERR_BAD_ARG;
         if (D.C > 0 && (D.cell_ptr == nullptr || D.out == nullptr)) return CWN_ERR_BAD_ARG;
@@ -287,7 +257,7 @@ int launch_head(const typename HeadDescOf<real>::type* desc, cwn_stream_t stream
     const auto& D = *desc;
     if (D.D < 1 || D.D > CWN_MAX_DESCS) return CWN_ERR_BAD_ARG;
     if (D.H < 1 || D.H > CWN_AGNOSTIC_MAX_WIDTH || D.O < 1 || D.O > CWN_AGNOSTIC_MAX_WIDTH) return CWN_ERR_BAD_ARG;
-    if (D.act < CWN_ACT_ID || D.act > CWN_ACT_SIGMOID || D.C < 0) return CWN_ERR_BAD_ARG;
+    if (!known_act(D.act) || D.C < 0) return CWN_ERR_BAD_ARG;
     if (D.ldw1 < D.H || D.ldw2 < D.H || D.ldo < D.O) return CWN_ERR_BAD_ARG;
     for (int d = 0; d < D.D; ++d)
         if (D.P[d] != nullptr && D.ldp[d] < D.H) return CWN_ERR_BAD_ARG;

@@ -22,6 +22,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/cwn_hip.h"
+#include "cwn_act.h"
+#include "cwn_check.h"
 
 namespace {
 
@@ -45,22 +47,12 @@ struct ChainBatch {
     int32_t n;
 };
 
-__device__ __forceinline__ double activate(double v, int act) {
-    switch (act) {
-        case CWN_ACT_RELU: return v < 0.0 ? 0.0 : v;
-        case CWN_ACT_ELU: return v > 0.0 ? v : expm1(v);
-        case CWN_ACT_TANH: return tanh(v);
-        case CWN_ACT_SIGMOID: return 1.0 / (1.0 + exp(-v));
-        default: return v;
-    }
-}
-
 // bias, affine, activation of column c
 __device__ __forceinline__ double finish(double v, int c, const double* bias, const double* scale, const double* shift,
                                          int act) {
     if (bias != nullptr) v += bias[c];
     if (scale != nullptr) v = fma(v, scale[c], shift[c]);
-    return activate(v, act);
+    return activate_rt(v, act);
 }
 
 // W[c, k0 + k] (row stride ldw) -> ws[k * wld + c] for c < n_cols, k < kn
@@ -199,9 +191,6 @@ __global__ __launch_bounds__(kThreads) void update_chain_f64_kernel(ChainBatch B
     else chain_tile<64>(D, row0, a, b, ws);
 }
 
-inline bool aligned8(const void* p) { return (((uintptr_t)p) & 7u) == 0; }
-inline bool known_act(int act) { return act >= CWN_ACT_ID && act <= CWN_ACT_SIGMOID; }
-
 }  // namespace
 
 extern "C" int cwn_linear_many_f64(const cwn_linear_desc_f64* descs, int n, cwn_stream_t stream_) {
@@ -216,7 +205,7 @@ extern "C" int cwn_linear_many_f64(const cwn_linear_desc_f64* descs, int n, cwn_
         if (D.M > 0) {
             if (D.X == nullptr || D.W == nullptr || D.Y == nullptr) return CWN_ERR_BAD_ARG;
             if (D.ldx < D.K || D.ldw < D.K || D.ldy < D.N) return CWN_ERR_BAD_ARG;
-            if (!aligned8(D.X) || !aligned8(D.W) || !aligned8(D.Y) || !aligned8(D.bias)) return CWN_ERR_ALIGN;
+            if (!al8(D.X) || !al8(D.W) || !al8(D.Y) || !al8(D.bias)) return CWN_ERR_ALIGN;
         }
         B.d[i] = D;
         B.blk_start[i] = (int32_t)blocks;
@@ -243,10 +232,10 @@ extern "C" int cwn_update_chain_f64(const cwn_chain_desc_f64* descs, int n_dims,
         if (D.n > 0) {
             if (D.in_up == nullptr || D.in_b == nullptr || D.out == nullptr) return CWN_ERR_BAD_ARG;
             if (D.ld_up < D.F || D.ld_b < D.F || D.ld_out < D.H) return CWN_ERR_BAD_ARG;
-            if (!aligned8(D.in_up) || !aligned8(D.in_b) || !aligned8(D.out)) return CWN_ERR_ALIGN;
+            if (!al8(D.in_up) || !al8(D.in_b) || !al8(D.out)) return CWN_ERR_ALIGN;
             for (int s = 0; s < 5; ++s) {
                 if (D.W[s] == nullptr) return CWN_ERR_BAD_ARG;
-                if (!aligned8(D.W[s]) || !aligned8(D.bias[s]) || !aligned8(D.scale[s]) || !aligned8(D.shift[s])) return CWN_ERR_ALIGN;
+                if (!al8(D.W[s]) || !al8(D.bias[s]) || !al8(D.scale[s]) || !al8(D.shift[s])) return CWN_ERR_ALIGN;
             }
         }
         B.d[i] = D;

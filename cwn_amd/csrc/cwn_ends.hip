@@ -27,6 +27,7 @@
 #include "../../include/cwn_hip.h"
 #include "cwn_mem.h"
 #include "cwn_dropout.h"
+#include "cwn_check.h"
 
 namespace {
 
@@ -320,8 +321,6 @@ __global__ __launch_bounds__(256) void front_reduce_kernel(FrontArgs A) {
         cwn::store_result4(dst, acc.x, acc.y, acc.z, acc.w);
     }
 }
-
-inline bool al16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 inline bool table_ok(const cwn_embed_table& T) {
     return T.W != nullptr && T.src != nullptr && T.cols > 0 && T.cols <= kMaxCols && T.V > 0 &&

@@ -34,6 +34,7 @@
 #include <stdlib.h>
 #include "../../include/cwn_hip.h"
 #include "cwn_mem.h"
+#include "cwn_check.h"
 
 namespace {
 
@@ -640,8 +641,6 @@ if (full && vec) {
         }
     }
 }
-
-inline bool al16(const void* p) { return p == nullptr || ((uintptr_t)p & 15u) == 0; }
 
 }  // namespace
 

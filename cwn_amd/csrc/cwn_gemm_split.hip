@@ -28,6 +28,7 @@
 #include "../../include/cwn_hip.h"
 #include "cwn_split.h"
 #include "cwn_mem.h"
+#include "cwn_check.h"
 
 namespace {
 
@@ -204,8 +205,6 @@ __global__ __launch_bounds__(256) void pack_gemm_weights_kernel(const float* __r
     *reinterpret_cast<uint4*>(dst + 1024) = pm;
     *reinterpret_cast<uint4*>(dst + 2048) = pl;
 }
-
-inline bool al16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 }  // namespace
 

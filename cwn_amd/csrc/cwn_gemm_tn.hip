@@ -24,6 +24,7 @@
 #include <stdlib.h>
 #include "../../include/cwn_hip.h"
 #include "cwn_split.h"
+#include "cwn_check.h"
 
 namespace {
 
@@ -546,8 +547,6 @@ __global__ __launch_bounds__(kThreads) void tn_reduce_kernel(TnBatch B) {
         else D.dW[(e / Ktot) * D.lddw + (e % Ktot)] += s;
     }
 }
-
-inline bool al16(const void* p) { return p == nullptr || ((uintptr_t)p & 15u) == 0; }
 
 inline size_t tn_ws_floats(const cwn_gemm_tn_desc& D) {
     const size_t bands = (size_t)((D.M + kBandRows - 1) / kBandRows);

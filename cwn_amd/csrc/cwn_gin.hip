@@ -25,6 +25,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/cwn_hip.h"
+#include "cwn_act.h"
+#include "cwn_check.h"
 
 namespace {
 
@@ -46,16 +48,6 @@ struct GinArgs {
     int32_t w2_vec;      // W2 likewise (H % 4 == 0, aligned)
     int32_t out_vec;     // out rows take 16-byte stores
 };
-
-__device__ __forceinline__ float act_fwd(int act, float z) {
-    switch (act) {
-        case CWN_ACT_RELU: return fmaxf(z, 0.f);
-        case CWN_ACT_ELU: return z > 0.f ? z : expm1f(z);
-        case CWN_ACT_TANH: return tanhf(z);
-        case CWN_ACT_SIGMOID: return 1.0f / (1.0f + expf(-z));
-        default: return z;
-    }
-}
 
 // Entries p0 .. p1 - 1 of one row, column c: acc += x[col[p]][c], one after the other (four entries' loads in flight,
 // added in entry order).
@@ -126,7 +118,7 @@ __device__ __forceinline__ float epilogue(float z, int n, const float* __restric
     if (bias != nullptr) z = z + bias[n];
     if (scale != nullptr) z = z * scale[n];
     if (shift != nullptr) z = z + shift[n];
-    return act_fwd(act, z);
+    return activate_rt(z, act);
 }
 
 __global__ __launch_bounds__(kThreads) void gin_layer_kernel(GinArgs P) {
@@ -199,7 +191,8 @@ __global__ __launch_bounds__(kThreads) void gin_layer_kernel(GinArgs P) {
             float y[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q)
-                y[q] = n0 + q < H ? act_fwd(act_post, epilogue(acc[ct][rt][q], n0 + q, P.d.b2, P.d.scale2, P.d.shift2, act)) : 0.f;
+                y[q] = n0 + q < H ? activate_rt(epilogue(acc[ct][rt][q], n0 + q, P.d.b2, P.d.scale2, P.d.shift2, act), act_post)
+                                  : 0.f;
             float* p = out + row * ldout + n0;
             if (P.out_vec && n0 + 3 < H) {
                 *reinterpret_cast<float4*>(p) = make_float4(y[0], y[1], y[2], y[3]);
@@ -211,9 +204,6 @@ __global__ __launch_bounds__(kThreads) void gin_layer_kernel(GinArgs P) {
         }
     }
 }
-
-inline bool al4(const void* p) { return ((uintptr_t)p & 3u) == 0; }       // (NULL counts as aligned)
-inline bool al16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 // Do the elements of out [n, H] (stride ldout) and of x [n, w] (stride ldx) share an address?  Equal base pointers always;
 // with one common row stride -- two column slices of one buffer -- when their column ranges meet.
@@ -231,7 +221,7 @@ int check(const cwn_gin_desc* desc) {
     if (desc == nullptr) return CWN_ERR_BAD_ARG;
     const cwn_gin_desc& D = *desc;
     if (D.w < 1 || D.w > kMaxWidth || D.H < 1 || D.H > kMaxWidth || D.n < 0) return CWN_ERR_BAD_ARG;
-    if (D.act < CWN_ACT_ID || D.act > CWN_ACT_SIGMOID || D.act_post < CWN_ACT_ID || D.act_post > CWN_ACT_SIGMOID) return CWN_ERR_BAD_ARG;
+    if (!known_act(D.act) || !known_act(D.act_post)) return CWN_ERR_BAD_ARG;
     if (D.rowptr != nullptr && D.col == nullptr) return CWN_ERR_BAD_ARG;
     if (D.n > 0 && (D.x == nullptr || D.out == nullptr || D.W1 == nullptr || D.W2 == nullptr || D.ldx < D.w || D.ldout < D.H))
         return CWN_ERR_BAD_ARG;

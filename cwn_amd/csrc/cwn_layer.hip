@@ -57,6 +57,7 @@
 #include <type_traits>
 #include "../../include/cwn_hip.h"
 #include "cwn_split.h"
+#include "cwn_check.h"
 
 namespace {
 
@@ -1325,8 +1326,6 @@ __global__ __launch_bounds__(256) void pack_weights_kernel(PackMany P) {
     *reinterpret_cast<uint4*>(dst + 2 * kPlane) = pl;
 }
 #endif
-
-inline bool al16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 #ifdef CWN_LAYER_TIMING
 unsigned long long* g_stamps = nullptr;

@@ -35,6 +35,7 @@
 #include <stdlib.h>
 #include "../../include/cwn_hip.h"
 #include "cwn_split.h"
+#include "cwn_check.h"
 
 namespace {
 
@@ -312,8 +313,6 @@ __global__ __launch_bounds__(kThreads) void layer_bwd_kernel(BwdArgs A) {
         }
     }
 }
-
-inline bool al16(const void* p) { return p == nullptr || ((uintptr_t)p & 15u) == 0; }
 
 template <int F>
 int launch(const BwdArgs& A, int64_t n_items, hipStream_t stream) {

@@ -28,6 +28,7 @@
 #include "../../include/cwn_hip.h"
 #include "cwn_split.h"
 #include "cwn_layer_bwd_own.h"
+#include "cwn_check.h"
 
 namespace {
 
@@ -675,8 +676,6 @@ __global__ __launch_bounds__(kThreads) void layer_bwd_own_kernel(const int32_t* 
 #ifdef CWN_LBWD_TIMING
 unsigned long long* g_stamps = nullptr;
 #endif
-
-inline bool al16(const void* p) { return p == nullptr || ((uintptr_t)p & 15u) == 0; }
 
 template <int F>
 int launch(const OwnArgs& A, int64_t n_items, hipStream_t stream) {

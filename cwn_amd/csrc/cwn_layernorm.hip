@@ -18,6 +18,7 @@
 // the same with the stored fp32 mean, so both passes see the same xhat.
 #include <hip/hip_runtime.h>
 #include "../../include/cwn_hip.h"
+#include "cwn_check.h"
 
 namespace {
 
@@ -323,9 +324,6 @@ __global__ __launch_bounds__(kThreads) void layernorm_bwd_sums_kernel(LnBatch B,
     if (D.dbeta != nullptr) D.dbeta[c] = D.accumulate ? D.dbeta[c] + s1 : s1;
     if (D.dgamma != nullptr) D.dgamma[c] = D.accumulate ? D.dgamma[c] + s2 : s2;
 }
-
-inline bool al16(const void* p) { return ((uintptr_t)p & 15u) == 0; }       // (NULL counts as aligned)
-inline bool al4(const void* p) { return ((uintptr_t)p & 3u) == 0; }
 
 inline int64_t bands_of(int64_t M) { return (M + kBand - 1) / kBand; }
 

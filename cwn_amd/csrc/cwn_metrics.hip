@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "../../include/cwn_hip.h"
+#include "cwn_check.h"
 
 namespace {
 
@@ -393,8 +394,6 @@ __global__ __launch_bounds__(kT) void loss_segments_kernel(int kind, const float
     if (threadIdx.x == 0) out[b] = cnt > 0 ? (float)(s / (double)cnt) : __int_as_float(0x7fc00000);
 }
 
-inline bool al8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
-inline bool al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 inline int launched() { return hipGetLastError() == hipSuccess ? CWN_OK : CWN_ERR_LAUNCH; }
 
 }  // namespace

@@ -242,8 +242,6 @@ __global__ __launch_bounds__(kThreads, SEQ ? 4 : 1) void update_mlp_kernel(int32
     MLP_STAMP(8);
 }
 
-using cwn::al16;
-
 }  // namespace
 
 #ifdef CWN_MLP_TIMING

@@ -146,8 +146,6 @@ __global__ __launch_bounds__(kThreads, 4) void update_mlp3_kernel(Mlp3Batch B) {
     finish(accC, cS, nullptr);
 }
 
-using cwn::al16;
-
 template <int F>
 int launch_mlp3(Mlp3Batch& B, int64_t blocks, hipStream_t stream) {
     return cwn::launch_tile<&update_mlp3_kernel<F>>(Shape3<F>::kLdsBytes, blocks, stream, B);

@@ -18,6 +18,7 @@
 #include "cwn_mem.h"
 #include "cwn_bn_live.h"
 #include "cwn_dropout.h"
+#include "cwn_check.h"
 
 namespace {
 
@@ -400,8 +401,6 @@ __global__ __launch_bounds__(kFT) void norm_bwd_fused_kernel(NormBatch B, int ac
         }
     }
 }
-
-inline bool al16(const void* p) { return p == nullptr || ((uintptr_t)p & 15u) == 0; }
 
 template <int MODE>
 int launch_norm(const cwn_norm_desc* descs, int n, cwn_stream_t stream_) {

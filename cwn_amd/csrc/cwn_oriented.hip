@@ -20,6 +20,8 @@
 // Absent streams (rowptr == NULL) and an absent self map (w_self == NULL) take no room in the panel.
 #include <hip/hip_runtime.h>
 #include "../../include/cwn_hip.h"
+#include "cwn_act.h"
+#include "cwn_check.h"
 
 namespace {
 
@@ -45,27 +47,6 @@ struct Plan {
     const int32_t* perm;
     const float* orient;
 };
-
-__device__ __forceinline__ float act_fwd(int act, float z) {
-    switch (act) {
-        case CWN_ACT_RELU: return fmaxf(z, 0.f);
-        case CWN_ACT_ELU: return z > 0.f ? z : expm1f(z);
-        case CWN_ACT_TANH: return tanhf(z);
-        case CWN_ACT_SIGMOID: return 1.0f / (1.0f + expf(-z));
-        default: return z;
-    }
-}
-
-// act'(z) as a function of out = act(z)
-__device__ __forceinline__ float act_grad(int act, float o) {
-    switch (act) {
-        case CWN_ACT_RELU: return o > 0.f ? 1.f : 0.f;
-        case CWN_ACT_ELU: return o > 0.f ? 1.f : o + 1.f;
-        case CWN_ACT_TANH: return 1.f - o * o;
-        case CWN_ACT_SIGMOID: return o * (1.f - o);
-        default: return 1.f;
-    }
-}
 
 // Entries p0, p0 + step, ... < p1 of one row, column c: acc += x[col[p]][c] * orient[perm[p]], one after the other (four
 // entries' loads in flight, added in entry order; mul and add stay separate instructions: -ffp-contract=off).
@@ -247,7 +228,7 @@ __global__ __launch_bounds__(kThreads) void oriented_layer_kernel(OrientedArgs P
             if (row >= m) continue;
             float y[4];
 #pragma unroll
-            for (int q = 0; q < 4; ++q) y[q] = act_fwd(act, acc[ct][rt][q]);
+            for (int q = 0; q < 4; ++q) y[q] = activate_rt(acc[ct][rt][q], act);
             float* p = out + row * ldout + n0;
             if (P.out_vec && n0 + 3 < H) {
                 *reinterpret_cast<float4*>(p) = make_float4(y[0], y[1], y[2], y[3]);
@@ -283,10 +264,6 @@ __global__ __launch_bounds__(kThreads) void oriented_dz_kernel(DzArgs P) {
     }
 }
 
-inline bool al4(const void* p) { return ((uintptr_t)p & 3u) == 0; }       // (NULL counts as aligned)
-inline bool al8(const void* p) { return ((uintptr_t)p & 7u) == 0; }
-inline bool al16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 inline int tile_rows(int w) { return CWN_ORIENTED_TM(w); }
 
 // The entry slots cwn_aggregate_f32 gives a row of width w (its vector width by w and the alignment of the gathered matrix
@@ -307,7 +284,7 @@ int check(const cwn_oriented_desc* desc) {
     if (desc == nullptr) return CWN_ERR_BAD_ARG;
     const cwn_oriented_desc& D = *desc;
     if (D.w < 1 || D.w > kMaxWidth || D.H < 1 || D.H > kMaxWidth || D.n < 0) return CWN_ERR_BAD_ARG;
-    if (D.act < CWN_ACT_ID || D.act > CWN_ACT_SIGMOID) return CWN_ERR_BAD_ARG;
+    if (!known_act(D.act)) return CWN_ERR_BAD_ARG;
     if ((D.up_rowptr == nullptr) != (D.w_up == nullptr) || (D.dn_rowptr == nullptr) != (D.w_dn == nullptr)) return CWN_ERR_BAD_ARG;
     if (D.up_rowptr != nullptr && (D.up_col == nullptr || (D.up_orient != nullptr && D.up_perm == nullptr))) return CWN_ERR_BAD_ARG;
     if (D.dn_rowptr != nullptr && (D.dn_col == nullptr || (D.dn_orient != nullptr && D.dn_perm == nullptr))) return CWN_ERR_BAD_ARG;
@@ -347,7 +324,7 @@ extern "C" int cwn_oriented_layer_f32(const cwn_oriented_desc* desc, cwn_stream_
 
 extern "C" int cwn_oriented_dz_f32(const float* dout, const float* out, float* dz, int64_t n, int32_t H, int64_t lddout,
                                    int64_t ldout, int64_t lddz, int32_t act, const int64_t* m_dev, cwn_stream_t stream_) {
-    if (n < 0 || H < 1 || H > kMaxWidth || act < CWN_ACT_ID || act > CWN_ACT_SIGMOID) return CWN_ERR_BAD_ARG;
+    if (n < 0 || H < 1 || H > kMaxWidth || !known_act(act)) return CWN_ERR_BAD_ARG;
     if (n > 0 && (dout == nullptr || out == nullptr || dz == nullptr || lddout < H || ldout < H || lddz < H)) return CWN_ERR_BAD_ARG;
     if (!al4(dout) || !al4(out) || !al4(dz) || !al8(m_dev)) return CWN_ERR_ALIGN;
     if (n == 0) return CWN_OK;

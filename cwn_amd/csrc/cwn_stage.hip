@@ -500,8 +500,6 @@ __global__ __launch_bounds__(kThreads, 4) void dense_stage_bwd_kernel(StageBwdBa
     }
 }
 
-using cwn::al16;
-
 template <int F>
 int launch_stage(const StageBatch& B, int64_t blocks, hipStream_t stream) {
     return cwn::launch_tile<&dense_stage_kernel<F>>(Shape<F>::kLdsBytes, blocks, stream, B);

@@ -23,6 +23,7 @@
 //     slices in group order.  No atomics: dW and db have the same bits on every run, and there is no second (ordered) form.
 #include <hip/hip_runtime.h>
 #include "../../include/cwn_hip.h"
+#include "cwn_check.h"
 
 namespace {
 
@@ -247,10 +248,6 @@ __global__ __launch_bounds__(kThreads) void target_head_sum_kernel(const float* 
     if (e < (int64_t)K * H) dW[e] = acc;
     else if (db != nullptr && e - (int64_t)K * H < K) db[e - (int64_t)K * H] = acc;
 }
-
-inline bool al4(const void* p) { return ((uintptr_t)p & 3u) == 0; }       // (NULL counts as aligned)
-inline bool al8(const void* p) { return ((uintptr_t)p & 7u) == 0; }
-inline bool al16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 inline int check_shape(int64_t N, int64_t C, int32_t H, int32_t K) {
     if (N < 0 || C < 0 || H < 4 || H > CWN_TARGET_HEAD_MAX_H || (H & 3) != 0 || K < 1 || K > CWN_TARGET_HEAD_MAX_K) return CWN_ERR_BAD_ARG;

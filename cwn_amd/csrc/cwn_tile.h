@@ -28,6 +28,7 @@
 #include <mutex>
 #include "../../include/cwn_hip.h"
 #include "cwn_split.h"
+#include "cwn_check.h"
 #include "cwn_mem.h"
 
 namespace cwn {
@@ -175,9 +176,6 @@ template <class S> struct WaveTile {
 };
 
 // ---- host side ----------------------------------------------------------------------------------------------------------
-
-// 16-byte aligned (a null pointer passes: optional arguments are checked for presence where they are required)
-inline bool al16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 // Kernel<<<blocks, 512 threads, lds_bytes of dynamic LDS>>>(args...), the kernel's limit of dynamic LDS raised to lds_bytes
 // once per process (above 64 KiB a launch fails without it)

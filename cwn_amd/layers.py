@@ -80,16 +80,35 @@ def _is_cat_linear_relu(nn) -> bool:
             and isinstance(nn[1], Linear) and isinstance(nn[2], ReLU))
 
 
-# the activation modules other than ReLU that models.get_nonlinearity hands out, by their ops.ACT_CODES name
-_MESSAGE_ACTS = {torch.nn.ELU: 'elu', torch.nn.Tanh: 'tanh', torch.nn.Sigmoid: 'sigmoid', torch.nn.Identity: 'id'}
+def identity(x):
+    """The 'id' nonlinearity (mp/nn.py:16-17) as ONE function object, so that a layer can recognise it."""
+    return x
+
+
+# The five nonlinearities of mp/nn.py:7-28 by their ops.ACT_CODES name, as (module class, function): what
+# models.get_nonlinearity hands out, and how a layer recognises what it was given.
+ACTIVATIONS = {'relu': (ReLU, torch.nn.functional.relu), 'elu': (torch.nn.ELU, torch.nn.functional.elu),
+               'id': (torch.nn.Identity, identity), 'sigmoid': (torch.nn.Sigmoid, torch.sigmoid), 'tanh': (torch.nn.Tanh, torch.tanh)}
+
+
+def _act_name(module) -> Optional[str]:
+    """The ACTIVATIONS name of an activation module; None for any other module and for an ELU whose alpha is not 1 (the
+    kernels compute expm1 alone)."""
+    name = next((n for n, (cls, _) in ACTIVATIONS.items() if type(module) is cls), None)
+    return None if name == 'elu' and module.alpha != 1.0 else name
+
+
+def _act_name_of_function(fn) -> Optional[str]:
+    return next((n for n, (_, f) in ACTIVATIONS.items() if f is fn), None)
 
 
 def _cat_linear_act(nn) -> Optional[str]:
-    """The activation's name when `nn` is Sequential(Catter, Linear, ELU | Tanh | Sigmoid | Identity), else None."""
+    """The activation's name when `nn` is Sequential(Catter, Linear, ELU | Tanh | Sigmoid | Identity), else None (ReLU
+    too: that form is `_is_cat_linear_relu`'s, with routes of its own)."""
     if not (isinstance(nn, Sequential) and len(nn) == 3 and isinstance(nn[0], Catter) and isinstance(nn[1], Linear)):
         return None
-    name = _MESSAGE_ACTS.get(type(nn[2]))
-    return None if name == 'elu' and nn[2].alpha != 1.0 else name
+    name = _act_name(nn[2])
+    return None if name == 'relu' else name
 
 
 # A coboundary message act(Linear(cat(x_j, up_attr))) with an activation other than ReLU as two per-cell products and one
@@ -270,9 +289,6 @@ def _fold_norm(norm, width: int):
     return fold
 
 
-_F64_ACTS = {torch.nn.Identity: 'id', ReLU: 'relu', torch.nn.ELU: 'elu', torch.nn.Tanh: 'tanh', torch.nn.Sigmoid: 'sigmoid'}
-
-
 def _f64_stages(nn, groups: int):
     """([(Linear, norm), ...], activation name) of a stock Sequential of `groups` (Linear, norm, act) groups whose
     activation modules are all the same one of the five of models.get_nonlinearity, or None."""
@@ -281,8 +297,8 @@ def _f64_stages(nn, groups: int):
     stages, acts = [], set()
     for i in range(0, len(nn), 3):
         lin, norm, act = nn[i], nn[i + 1], nn[i + 2]
-        name = _F64_ACTS.get(type(act))
-        if type(lin) is not Linear or name is None or (name == 'elu' and act.alpha != 1.0):
+        name = _act_name(act)
+        if type(lin) is not Linear or name is None:
             return None
         stages.append((lin, norm))
         acts.add(name)
@@ -1778,16 +1794,6 @@ class CINppConv(SparseCINConv):
 FUSED_ORIENTED = os.environ.get('CWN_FUSED_ORIENTED') != '0'    # False: OrientedConv as one aggregation launch + torch Linear / add / activation
 
 
-def identity(x):
-    """The 'id' nonlinearity (mp/nn.py:16-17) as ONE function object, so that a layer can recognise it."""
-    return x
-
-
-# what models.get_nonlinearity(name, return_module=False) returns -> the activation of cwn_oriented_layer_f32
-ACT_FUNCTIONS = ((identity, 'id'), (torch.nn.functional.relu, 'relu'), (torch.nn.functional.elu, 'elu'), (torch.tanh, 'tanh'),
-                 (torch.sigmoid, 'sigmoid'))
-
-
 class ZeroUpdate(torch.nn.Module):
     """An update map that discards its input: the recognisable, parameter-free form of the reference's
     `update_up = lambda x: 0` (EdgeMPNN, mp/models.py:569-570)."""
@@ -1854,7 +1860,7 @@ class OrientedConv(CochainMessagePassing):
         if (not FUSED_ORIENTED or not isinstance(x, Tensor) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2
                 or not self._own_hooks() or (self.aggr_up or 'add') != 'add' or (self.aggr_down or 'add') != 'add'):
             return None
-        act = next((name for fn, name in ACT_FUNCTIONS if self.act_fn is fn), None)
+        act = _act_name_of_function(self.act_fn)
         if act is None:
             return None
         ws = []
@@ -1994,7 +2000,7 @@ class GINConv(torch.nn.Module):
             if edge_index is not None and edge_index.numel():
                 s = torch.zeros_like(x).index_add_(0, edge_index[1], x[edge_index[0]]) + s
         y = self.nn(s)
-        return y if act_post == 'id' else next(fn for fn, name in ACT_FUNCTIONS if name == act_post)(y)
+        return y if act_post == 'id' else ACTIVATIONS[act_post][1](y)
 
     def __repr__(self):
         return f'{self.__class__.__name__}(nn={self.nn})'

@@ -40,12 +40,9 @@ def _one_check(forward):
 
 def get_nonlinearity(nonlinearity, return_module=True):
     """mp/nn.py:7-28."""
-    table = {'relu': (torch.nn.ReLU, F.relu), 'elu': (torch.nn.ELU, F.elu),
-             'id': (torch.nn.Identity, layers.identity), 'sigmoid': (torch.nn.Sigmoid, torch.sigmoid),
-             'tanh': (torch.nn.Tanh, torch.tanh)}
-    if nonlinearity not in table:
+    if nonlinearity not in layers.ACTIVATIONS:
         raise NotImplementedError(f'Nonlinearity {nonlinearity} is not currently supported.')
-    return table[nonlinearity][0 if return_module else 1]
+    return layers.ACTIVATIONS[nonlinearity][0 if return_module else 1]
 
 
 def get_graph_norm(norm):

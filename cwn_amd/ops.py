@@ -1824,17 +1824,13 @@ def gemm_many(gemms: Sequence[Gemm]) -> List[Tensor]:
 # ------------------------------------------------------------------------------------------------
 # LayerNorm (+ ReLU) over the rows of several matrices: graph_norm='ln' (csrc/cwn_layernorm.hip)
 # ------------------------------------------------------------------------------------------------
-def _ln_ld(t: Tensor) -> int:
-    return t.stride(0) if t.size(0) > 1 else t.size(1)
-
-
 def _ln_descs(zs, gammas, betas, outs, epss, relu: bool, stats=None) -> List['_ffi.LnDesc']:
     descs, off = [], 0
     for k, (z, out) in enumerate(zip(zs, outs)):
         M, N = z.shape
         if M:
             d = _ffi.LnDesc(z=z.data_ptr(), gamma=_ffi.ptr(gammas[k]), beta=_ffi.ptr(betas[k]), out=out.data_ptr(),
-                            M=M, ldz=_ln_ld(z), ldout=_ln_ld(out), N=N, relu=int(relu), eps=float(epss[k]))
+                            M=M, ldz=_ld(z), ldout=_ld(out), N=N, relu=int(relu), eps=float(epss[k]))
             if stats is not None:
                 d.mean, d.rstd = stats[0, off:].data_ptr(), stats[1, off:].data_ptr()
             descs.append(d)
@@ -1906,7 +1902,7 @@ class _LayerNormActMany(torch.autograd.Function):
                 descs.append(_ffi.LnDesc(
                     z=z.data_ptr(), gamma=_ffi.ptr(gamma), out=out.data_ptr(), mean=stats[0, row0:].data_ptr(),
                     rstd=stats[1, row0:].data_ptr(), dy=dy.data_ptr(), dz=dz.data_ptr(), dgamma=_ffi.ptr(dgamma),
-                    dbeta=_ffi.ptr(dbeta), M=M, ldz=_ln_ld(z), ldout=_ln_ld(out), lddy=_ln_ld(dy), lddz=_ln_ld(dz), N=N,
+                    dbeta=_ffi.ptr(dbeta), M=M, ldz=_ld(z), ldout=_ld(out), lddy=_ld(dy), lddz=_ld(dz), N=N,
                     relu=int(relu), eps=float(ctx.epss[k]), accumulate=int(bool(acc))))
         if descs:
             _ffi.layer_norm_bwd(descs, dev)
@@ -1961,9 +1957,6 @@ def layer_norm_act_many(zs: Sequence[Tensor], norms: Sequence[torch.nn.LayerNorm
 # ------------------------------------------------------------------------------------------------
 # OrientedConv as one launch (csrc/cwn_oriented.hip)
 # ------------------------------------------------------------------------------------------------
-ACTS = {'id': _ffi.ACT_ID, 'relu': _ffi.ACT_RELU, 'elu': _ffi.ACT_ELU, 'tanh': _ffi.ACT_TANH, 'sigmoid': _ffi.ACT_SIGMOID}
-
-
 def _oriented_launch(x: Tensor, up, dn, w_self, w_up, w_dn, act: int, H: int, agg_out: Optional[Tensor] = None,
                      trans: bool = False) -> Tensor:
     """One cwn_oriented_layer_f32 call.  `up` / `dn`: (built plan, orient [E] float32 or None), or None for an absent
@@ -2058,7 +2051,7 @@ def oriented_layer(x: Tensor, up_adj: Optional[Adjacency], up_orient: Optional[T
     `[H, w]` as torch.nn.Linear holds them (None: the map is absent -- EdgeMPNN's upper map).  `act`: 'id', 'relu', 'elu',
     'tanh', 'sigmoid'.  Differentiable w.r.t. x and the weights (the orientations get no gradient, as in the reference's
     data); float32, widths up to 128 (`oriented_layer_applies`) -- anything else is an error, not a fallback."""
-    act = ACTS[act] if isinstance(act, str) else int(act)
+    act = _act_code(act)
     x = _f32c(x, 'x')
     w_self, w_up, w_dn = _f32c(w_self, 'w_self'), _f32c(w_up, 'w_up'), _f32c(w_dn, 'w_dn')
     if not oriented_layer_applies(x, (w_self, w_up, w_dn)):
@@ -2172,7 +2165,7 @@ def target_head(x: Tensor, target_rows: Tensor, weight: Tensor, bias: Optional[T
 # ------------------------------------------------------------------------------------------------
 # The float64 dense path (csrc/cwn_dense_f64.hip): the Linear layers of a double model, inference only
 # ------------------------------------------------------------------------------------------------
-ACT_CODES = {'id': _ffi.ACT_ID, 'relu': _ffi.ACT_RELU, 'elu': _ffi.ACT_ELU, 'tanh': _ffi.ACT_TANH, 'sigmoid': _ffi.ACT_SIGMOID}
+ACT_CODES = ACTS = {'id': _ffi.ACT_ID, 'relu': _ffi.ACT_RELU, 'elu': _ffi.ACT_ELU, 'tanh': _ffi.ACT_TANH, 'sigmoid': _ffi.ACT_SIGMOID}
 
 
 def _act_code(act) -> int:
@@ -2184,19 +2177,40 @@ def _act_code(act) -> int:
     return code
 
 
-def _f64rows(t: Optional[Tensor], name: str, dim: int = 2) -> Optional[Tensor]:
-    """An operand of the float64 dense kernels: float64, on the GPU, rows contiguous (a row stride is allowed)."""
+def _rows_contiguous(t: Tensor, dim: int) -> bool:
+    """`dim`-D with unit stride along the last axis; a 2-D tensor may be a row-strided view whose rows do not overlap."""
+    return (t.dim() == dim and (t.numel() == 0 or t.stride(-1) == 1)
+            and (dim != 2 or t.size(0) <= 1 or t.stride(0) >= t.size(1)))
+
+
+def _operand_dtype(t, name: str, dtypes, what: str, hint: str) -> None:
+    if not isinstance(t, Tensor) or t.dtype not in dtypes:
+        kinds = ' or '.join(str(d)[len('torch.'):] for d in dtypes)
+        raise TypeError(f'{what}{name} must be {kinds} (got {getattr(t, "dtype", type(t).__name__)}): {hint}')
+
+
+def _rows_operand(t, name: str, dim: int, dtypes, what: str = '', hint: str = '', rows_got: bool = False) -> Optional[Tensor]:
+    """An operand of the inference kernels that take views: None, or a tensor of one of `dtypes`, on the GPU, rows
+    contiguous (a row stride is allowed).  Anything else is a TypeError `what` + `name` + ..., the dtype's with `hint`; an
+    op of one dtype names it bare, one of several as the tensor prints it."""
     if t is None:
         return None
-    if not isinstance(t, Tensor) or t.dtype != torch.float64:
-        raise TypeError(f'{name} must be float64 (got {getattr(t, "dtype", type(t).__name__)}): this kernel computes in fp64 only '
-                        '(float32 runs through the MFMA launches: gemm_many, update_mlp)')
+    _operand_dtype(t, name, dtypes, what, hint)
+    one = len(dtypes) == 1
+    kind = str(dtypes[0])[len('torch.'):] if one else t.dtype
     if not t.is_cuda:
-        raise TypeError(f'{name} must be a float64 tensor on the GPU (got {t.dtype} on {t.device})')
-    if t.dim() != dim or (t.numel() and t.stride(-1) != 1) or (dim == 2 and t.size(0) > 1 and t.stride(0) < t.size(1)):
-        raise TypeError(f'{name} must be a {dim}-D float64 tensor with contiguous rows (got {t.dtype}, shape {tuple(t.shape)}, '
+        where = f'got {t.dtype} on {t.device}' if one else f'it is on {t.device}'
+        raise TypeError(f'{what}{name} must be a {kind} tensor on the GPU ({where})')
+    if not _rows_contiguous(t, dim):
+        got = f'got {t.dtype}, ' if rows_got else ''
+        raise TypeError(f'{what}{name} must be a {dim}-D {kind} tensor with contiguous rows ({got}shape {tuple(t.shape)}, '
                         f'strides {tuple(t.stride())})')
     return t
+
+
+# an operand of the float64 dense kernels
+_F64_ROWS = dict(dtypes=(torch.float64,), rows_got=True,
+                 hint='this kernel computes in fp64 only (float32 runs through the MFMA launches: gemm_many, update_mlp)')
 
 
 def _ld(t: Tensor) -> int:
@@ -2219,7 +2233,8 @@ def _linear_many_f64(items) -> List[Tensor]:
     stay the ones a model's Linear layers make."""
     descs, outs, dev = [], [], None
     for i, (x, w, b, act) in enumerate(items):
-        x, w, b = _f64rows(x, f'x[{i}]'), _f64rows(w, f'weight[{i}]'), _f64rows(b, f'bias[{i}]', 1)
+        x, w, b = (_rows_operand(t, f'{name}[{i}]', dim, **_F64_ROWS)
+                   for t, name, dim in ((x, 'x', 2), (w, 'weight', 2), (b, 'bias', 1)))
         M, K = int(x.size(0)), int(x.size(1))
         N = int(w.size(0))
         if int(w.size(1)) != K or (b is not None and b.numel() != N):
@@ -2281,7 +2296,7 @@ def update_chain_f64_applies(dims: Sequence[ChainDim]) -> bool:
         if shp is None or not (1 <= shp[1] <= _ffi.CHAIN_F64_MAX_WIDTH and 1 <= shp[2] <= _ffi.CHAIN_F64_MAX_WIDTH):
             return False
         ts = [d.in_up, d.in_b, d.out] + list(d.weights) + list(d.biases) + [t for f in d.folds for t in f]
-        if not all(t is None or (t.dtype == torch.float64 and t.is_cuda and (t.numel() == 0 or t.stride(-1) == 1)) for t in ts):
+        if not all(t is None or (t.dtype == torch.float64 and t.is_cuda and _rows_contiguous(t, t.dim())) for t in ts):
             return False
         if not all(w.is_contiguous() for w in d.weights):
             return False
@@ -2298,13 +2313,11 @@ def update_chain_f64(dims: Sequence[ChainDim]) -> List[Tensor]:
     TypeError, shapes the launch does not take (`update_chain_f64_applies`) a ValueError."""
     descs, outs, dev = [], [], None
     for i, d in enumerate(dims):
-        named = [('in_up', d.in_up), ('in_b', d.in_b)] + [(f'weights[{s}]', w) for s, w in enumerate(d.weights)]
-        for name, t in named:
-            _f64rows(t, f'dims[{i}].{name}')
-        for name, t in [(f'biases[{s}]', b) for s, b in enumerate(d.biases)] + \
-                       [(f'folds[{s}]', t) for s, f in enumerate(d.folds) for t in f]:
-            _f64rows(t, f'dims[{i}].{name}', 1)
-        _f64rows(d.out, f'dims[{i}].out')
+        named = [('in_up', d.in_up, 2), ('in_b', d.in_b, 2)] + [(f'weights[{s}]', w, 2) for s, w in enumerate(d.weights)] + \
+                [(f'biases[{s}]', b, 1) for s, b in enumerate(d.biases)] + \
+                [(f'folds[{s}]', t, 1) for s, f in enumerate(d.folds) for t in f] + [('out', d.out, 2)]
+        for name, t, dim in named:
+            _rows_operand(t, f'dims[{i}].{name}', dim, **_F64_ROWS)
     if not update_chain_f64_applies(dims):
         raise ValueError('update_chain_f64: 1 to 4 dimensions of the five-stage shapes [H, F], [H, H], [H, F], [H, H], [H, 2H] '
                          f'with 1 <= F, H <= {_ffi.CHAIN_F64_MAX_WIDTH}, contiguous weights, a known activation')
@@ -2331,25 +2344,16 @@ def update_chain_f64(dims: Sequence[ChainDim]) -> List[Tensor]:
 def _agnostic_dtype(named, what: str) -> torch.dtype:
     """The one dtype of the operands of an `embed_pool` / `agnostic_head` call: float32 or float64, on the GPU, rows
     contiguous (a row stride is allowed).  Anything else is a TypeError that names the dtype."""
+    named = [(name, t, dim) for name, t, dim in named if t is not None]
     dtype = None
-    for name, t, dim in named:
-        if t is None:
-            continue
-        if not isinstance(t, Tensor) or t.dtype not in _ffi.FLOAT_DTYPES:
-            raise TypeError(f'{what}: {name} must be float32 or float64 (got {getattr(t, "dtype", type(t).__name__)}): '
-                            'the kernels of csrc/cwn_agnostic.hip compute in fp32 or fp64 only')
+    for name, t, dim in named:               # every dtype ahead of any device or shape
+        _operand_dtype(t, name, _ffi.FLOAT_DTYPES, f'{what}: ', 'the kernels of csrc/cwn_agnostic.hip compute in fp32 or fp64 only')
         if dtype is None:
             dtype = t.dtype
         if t.dtype != dtype:
             raise TypeError(f'{what}: {name} is {t.dtype}, the operands before it {dtype}: all operands of a call share one dtype')
     for name, t, dim in named:
-        if t is None:
-            continue
-        if not t.is_cuda:
-            raise TypeError(f'{what}: {name} must be a {t.dtype} tensor on the GPU (it is on {t.device})')
-        if t.dim() != dim or (t.numel() and t.stride(-1) != 1) or (dim == 2 and t.size(0) > 1 and t.stride(0) < t.size(1)):
-            raise TypeError(f'{what}: {name} must be a {dim}-D {t.dtype} tensor with contiguous rows (shape {tuple(t.shape)}, '
-                            f'strides {tuple(t.stride())})')
+        _rows_operand(t, name, dim, _ffi.FLOAT_DTYPES, f'{what}: ')
     if dtype is None:
         raise ValueError(f'{what}: no operand')
     return dtype
@@ -2385,8 +2389,7 @@ def embed_pool(xs, cell_ptrs, n_complexes: int, weights, biases, act, mean: bool
         descs.append(_ffi.EmbedPoolDesc(x=x.data_ptr() if N else None, cell_ptr=ptr.data_ptr(), W=w.data_ptr(), bias=_ffi.ptr(b),
                                         out=out.data_ptr(), N=N, C=C_, ldx=_ld(x), ldw=_ld(w), ldo=H, K=K, H=H, act=code,
                                         mean=int(bool(mean))))
-    name = 'cwn_embed_pool_f32' if dtype == torch.float32 else 'cwn_embed_pool_f64'
-    fn = getattr(_ffi.lib(), name)
+    fn, name = _ffi.typed_entry('embed_pool', dtype)
     for lo in range(0, len(descs), _ffi.MAX_DESCS):
         part = descs[lo:lo + _ffi.MAX_DESCS]
         _ffi.check(fn((_ffi.EmbedPoolDesc * len(part))(*part), len(part), _ffi.stream_ptr(dev)), name)
@@ -2426,35 +2429,24 @@ def agnostic_head(pooled, lin1_w: Tensor, lin1_b: Optional[Tensor], lin2_w: Tens
                               act=_act_code(act))
     for d, p in enumerate(pooled):
         D.P[d], D.ldp[d] = (p.data_ptr() if p is not None and C_ else None), (_ld(p) if p is not None else H)
-    name = 'cwn_agnostic_head_f32' if dtype == torch.float32 else 'cwn_agnostic_head_f64'
-    _ffi.check(getattr(_ffi.lib(), name)(C.byref(D), _ffi.stream_ptr(dev)), name)
+    fn, name = _ffi.typed_entry('agnostic_head', dtype)
+    _ffi.check(fn(C.byref(D), _ffi.stream_ptr(dev)), name)
     return out
 
 
 # ------------------------------------------------------------------------------------------------
 # GINConv as one launch (csrc/cwn_gin.hip): the layer of the graph baselines, float32, inference only
 # ------------------------------------------------------------------------------------------------
-def _gin_f32(t, name: str, dim: int) -> Optional[Tensor]:
-    """An operand of cwn_gin_layer_f32: a float32 tensor on the GPU with contiguous rows (2-D: a row stride is allowed)."""
-    if t is None:
-        return None
-    if not isinstance(t, Tensor) or t.dtype != torch.float32:
-        raise TypeError(f'gin_layer: {name} must be float32 (got {getattr(t, "dtype", type(t).__name__)}): cwn_gin_layer_f32 computes '
-                        'in fp32 only (float64 and training run through ops.aggregate and the torch modules: layers.GINConv)')
-    if not t.is_cuda:
-        raise TypeError(f'gin_layer: {name} must be a float32 tensor on the GPU (got {t.dtype} on {t.device})')
-    if t.dim() != dim or (t.numel() and t.stride(-1) != 1) or (dim == 2 and t.size(0) > 1 and t.stride(0) < t.size(1)):
-        raise TypeError(f'gin_layer: {name} must be a {dim}-D float32 tensor with contiguous rows (shape {tuple(t.shape)}, '
-                        f'strides {tuple(t.stride())})')
-    return t
+# an operand of cwn_gin_layer_f32
+_GIN_ROWS = dict(dtypes=(torch.float32,), what='gin_layer: ', hint='cwn_gin_layer_f32 computes in fp32 only (float64 and training '
+                 'run through ops.aggregate and the torch modules: layers.GINConv)')
 
 
 def gin_layer_applies(x: Tensor, stages) -> bool:
     """Does cwn_gin_layer_f32 take these operands?  `stages`: two (weight, bias, scale, shift) tuples, the two (Linear,
     folded norm) groups of a GINConv's network.  float32 on the GPU, x [n, w] with contiguous rows, weights [H, w] and
     [H, H] contiguous, 1 <= w, H <= 128, the vectors [H] or None."""
-    if not (isinstance(x, Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2
-            and (x.numel() == 0 or x.stride(1) == 1) and (x.size(0) <= 1 or x.stride(0) >= x.size(1))):
+    if not (isinstance(x, Tensor) and x.is_cuda and x.dtype == torch.float32 and _rows_contiguous(x, 2)):
         return False
     if len(stages) != 2 or any(len(s) != 4 for s in stages):
         return False
@@ -2489,14 +2481,15 @@ def gin_layer(x: Tensor, adj: Optional[Adjacency], eps, stages, act, act_post='i
     as the two do not overlap; nothing outside it is written.  Inference only: under a recording autograd (an operand that
     requires a gradient while gradients are enabled) this raises instead of detaching.  float32 on the GPU and widths up to
     128 (`gin_layer_applies`); another dtype or device is a TypeError that names it, never a fallback."""
-    x = _gin_f32(x, 'x', 2)
+    x = _rows_operand(x, 'x', 2, **_GIN_ROWS)
     if len(stages) != 2 or any(len(s) != 4 for s in stages):
         raise ValueError('gin_layer: stages is [(W1, b1, scale1, shift1), (W2, b2, scale2, shift2)]')
     named = []
     for k, (W, b, sc, sh) in enumerate(stages, 1):
-        named.append((_gin_f32(W, f'W{k}', 2), _gin_f32(b, f'b{k}', 1), _gin_f32(sc, f'scale{k}', 1), _gin_f32(sh, f'shift{k}', 1)))
+        named.append(tuple(_rows_operand(t, f'{name}{k}', dim, **_GIN_ROWS)
+                           for t, name, dim in ((W, 'W', 2), (b, 'b', 1), (sc, 'scale', 1), (sh, 'shift', 1))))
     if isinstance(eps, Tensor):
-        eps = _gin_f32(eps.reshape(-1), 'eps', 1)
+        eps = _rows_operand(eps.reshape(-1), 'eps', 1, **_GIN_ROWS)
         if eps.numel() != 1:
             raise ValueError(f'gin_layer: eps holds {eps.numel()} elements, not one')
     elif eps is not None:
@@ -2516,7 +2509,7 @@ def gin_layer(x: Tensor, adj: Optional[Adjacency], eps, stages, act, act_post='i
     if out is None:
         out = torch.empty(n, H, dtype=torch.float32, device=x.device)
     else:
-        out = _gin_f32(out, 'out', 2)
+        out = _rows_operand(out, 'out', 2, **_GIN_ROWS)
         if tuple(out.shape) != (n, H) or out.device != x.device:
             raise ValueError(f'gin_layer: out is {tuple(out.shape)} on {out.device}, the result {(n, H)} on {x.device}')
     if n == 0:

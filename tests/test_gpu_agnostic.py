@@ -407,3 +407,29 @@ def test_other_dtypes_are_a_type_error_that_names_the_dtype():
         ops.agnostic_head([z(1, 8, dtype=F64)], z(8, 8, dtype=F64), z(8), z(2, 8, dtype=F64), None, 'elu')
     with pytest.raises(ValueError):
         ops.embed_pool([z(4, 3)], [ptr], 1, [z(8, 3)], [z(8)], 'gelu')
+
+
+@pytest.mark.parametrize('dtype', [F32, F64], ids=['f32', 'f64'])
+def test_operands_without_contiguous_rows_are_refused_with_their_whole_message(dtype):
+    """The shape / stride clause of the operand check (the dtype and device clauses: tests/test_operand_messages_host.py), the
+    messages as literals recorded before the ops shared one checker.  Nothing is launched."""
+    from cwn_amd import ops
+    ptr = torch.tensor([0, 4], device=DEV)
+    z = lambda *s: torch.zeros(*s, dtype=dtype, device=DEV)
+    kind = {F32: 'torch.float32', F64: 'torch.float64'}[dtype]        # (these messages print the dtype as torch does)
+    embed = lambda x, w: ops.embed_pool([x], [ptr], 1, [w], [z(8)], 'elu')
+    head = lambda p, w2: ops.agnostic_head([p], z(3, 3), z(3), w2, None, 'elu')
+    cases = [
+        (lambda: embed(z(3, 4).t(), z(8, 3)),
+         f'embed_pool: xs[0] must be a 2-D {kind} tensor with contiguous rows (shape (4, 3), strides (1, 4))'),
+        (lambda: embed(z(4, 3), z(3)),
+         f'embed_pool: weights[0] must be a 2-D {kind} tensor with contiguous rows (shape (3,), strides (1,))'),
+        (lambda: head(z(3, 4).t(), z(2, 3)),
+         f'agnostic_head: pooled[0] must be a 2-D {kind} tensor with contiguous rows (shape (4, 3), strides (1, 4))'),
+        (lambda: head(z(4, 3), z(3)),
+         f'agnostic_head: lin2_w must be a 2-D {kind} tensor with contiguous rows (shape (3,), strides (1,))'),
+    ]
+    for call, message in cases:
+        with pytest.raises(TypeError) as got:
+            call()
+        assert type(got.value) is TypeError and str(got.value) == message

@@ -195,6 +195,33 @@ def test_update_chain_allocates_its_outputs_and_takes_strided_inputs():
     gate(y, _reference(nets, wide_up[:, 2:2 + F], wide_b[:, :F]), 'update_chain_f64, strided inputs, own output', tol=TOL)
 
 
+def test_operands_without_contiguous_rows_are_refused_with_their_whole_message():
+    """The shape / stride clause of the operand check (the dtype and device clauses: tests/test_operand_messages_host.py), the
+    messages as literals recorded before the ops shared one checker.  Nothing is launched."""
+    from cwn_amd import ops
+    z = lambda *s: torch.zeros(*s, dtype=F64, device=DEV)
+    x, w, b = z(4, 3), z(2, 3), z(2)
+    F, H, n = 3, 4, 5
+    chain = lambda **over: [ops.ChainDim(**{**dict(
+        in_up=z(n, F), in_b=z(n, F), weights=[z(H, F), z(H, H), z(H, F), z(H, H), z(H, 2 * H)], biases=[z(H) for _ in range(5)],
+        folds=[(z(H), z(H)) for _ in range(5)], act='relu'), **over})]
+    cases = [
+        (lambda: ops.linear_many_f64([(z(3, 4).t(), w, b, 'id')]),
+         'x[0] must be a 2-D float64 tensor with contiguous rows (got torch.float64, shape (4, 3), strides (1, 4))'),
+        (lambda: ops.linear_many_f64([(x, z(3), b, 'id')]),
+         'weight[0] must be a 2-D float64 tensor with contiguous rows (got torch.float64, shape (3,), strides (1,))'),
+        (lambda: ops.update_chain_f64(chain(in_b=z(F, n).t())),
+         'dims[0].in_b must be a 2-D float64 tensor with contiguous rows (got torch.float64, shape (5, 3), strides (1, 5))'),
+        (lambda: ops.update_chain_f64(chain(weights=[z(H, F), z(H), z(H, F), z(H, H), z(H, 2 * H)])),
+         'dims[0].weights[1] must be a 2-D float64 tensor with contiguous rows (got torch.float64, shape (4,), strides (1,))'),
+    ]
+    for call, message in cases:
+        with pytest.raises(TypeError) as got:
+            call()
+        assert type(got.value) is TypeError and str(got.value) == message
+    assert not ops.update_chain_f64_applies(chain(in_b=z(F, n).t()))
+
+
 # ------------------------------------------------------------------------------------------------
 # 3. row independence, bit for bit
 # ------------------------------------------------------------------------------------------------

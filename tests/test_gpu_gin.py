@@ -169,6 +169,25 @@ def test_op_raises_under_a_recording_autograd_and_on_other_dtypes():
         ops.gin_layer(x.to(DEV), None, None, sd, 'relu', out=torch.empty(10, 9, device=DEV))
 
 
+def test_operands_without_contiguous_rows_are_refused_with_their_whole_message():
+    """The shape / stride clause of the operand check (the dtype and device clauses: tests/test_operand_messages_host.py), the
+    messages as literals recorded before the ops shared one checker.  Nothing is launched."""
+    z = lambda *s: torch.zeros(*s, device=DEV)
+    gin = lambda x, W1=None, b1=None: ops.gin_layer(x, None, None, [(z(5, 3) if W1 is None else W1, b1, None, None),
+                                                                    (z(5, 5), None, None, None)], 'relu')
+    cases = [
+        (lambda: gin(z(3, 4).t()), 'gin_layer: x must be a 2-D float32 tensor with contiguous rows (shape (4, 3), strides (1, 4))'),
+        (lambda: gin(z(4, 3), W1=z(3)), 'gin_layer: W1 must be a 2-D float32 tensor with contiguous rows (shape (3,), strides (1,))'),
+        (lambda: gin(z(4, 3), b1=z(5, 1)),
+         'gin_layer: b1 must be a 1-D float32 tensor with contiguous rows (shape (5, 1), strides (1, 1))'),
+    ]
+    for call, message in cases:
+        with pytest.raises(TypeError) as got:
+            call()
+        assert type(got.value) is TypeError and str(got.value) == message
+    assert not ops.gin_layer_applies(z(3, 4).t(), [(z(5, 3), None, None, None), (z(5, 5), None, None, None)])
+
+
 # ---- layers.GINConv -------------------------------------------------------------------------------------------------------------
 def _conv(w, H, act='relu', norm='bn', train_eps=True, seed=0):
     torch.manual_seed(seed)
