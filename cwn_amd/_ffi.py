@@ -29,7 +29,7 @@ EXPORTS = ('cwn_abi_version', 'cwn_error_string', 'cwn_target_arch', 'cwn_csr_wo
            'cwn_aggregate_act_f32', 'cwn_aggregate_act_f64',
            'cwn_embed_pool_f32', 'cwn_embed_pool_f64', 'cwn_agnostic_head_f32', 'cwn_agnostic_head_f64',
            'cwn_gin_layer_f32',
-           'cwn_gemm_tn_f32', 'cwn_gemm_tn_workspace_bytes', 'cwn_adam_f32', 'cwn_adam_dev_f32', 'cwn_loss_f32', 'cwn_loss_cols_f32', 'cwn_embedding_fwd_f32', 'cwn_embedding_bwd_f32', 'cwn_embed_front_f32', 'cwn_head_f32', 'cwn_head_bwd_f32', 'cwn_head_pool_floats', 'cwn_lift_create', 'cwn_lift_size', 'cwn_lift_copy', 'cwn_lift_destroy',
+           'cwn_gemm_tn_f32', 'cwn_gemm_tn_workspace_bytes', 'cwn_gemm_tn_would_split', 'cwn_adam_f32', 'cwn_adam_dev_f32', 'cwn_loss_f32', 'cwn_loss_cols_f32', 'cwn_embedding_fwd_f32', 'cwn_embedding_bwd_f32', 'cwn_embed_front_f32', 'cwn_head_f32', 'cwn_head_bwd_f32', 'cwn_head_pool_floats', 'cwn_lift_create', 'cwn_lift_size', 'cwn_lift_copy', 'cwn_lift_destroy',
            'cwn_lift_many', 'cwn_lift_many_count', 'cwn_lift_many_lengths', 'cwn_lift_many_copy', 'cwn_lift_many_destroy',
            # the evaluation pass (csrc/cwn_metrics.hip)
            'cwn_metric_rank_workspace_bytes', 'cwn_metric_rank_f32', 'cwn_metric_abs_err_workspace_bytes', 'cwn_metric_abs_err_f32',
@@ -529,6 +529,8 @@ def lib():
     L.cwn_gemm_tn_f32.argtypes = [C.POINTER(GemmTnDesc), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
     L.cwn_gemm_tn_workspace_bytes.restype = C.c_size_t
     L.cwn_gemm_tn_workspace_bytes.argtypes = [C.POINTER(GemmTnDesc), C.c_int]
+    L.cwn_gemm_tn_would_split.restype = C.c_int
+    L.cwn_gemm_tn_would_split.argtypes = [C.POINTER(GemmTnDesc), C.c_int]
     L.cwn_adam_f32.restype = C.c_int
     L.cwn_adam_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float,
                                C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -973,6 +975,12 @@ def _flush_descs(descs, device) -> None:
     for part in (fast, slow):
         if part:
             gemm_tn(part, device)               # (the operands stay referenced by `q` until here)
+
+
+def gemm_tn_would_split(descs: Sequence[GemmTnDesc]) -> bool:
+    """Would cwn_gemm_tn_f32 run this launch (<= MAX_TN_DESCS descriptors) on its bf16-split kernel?"""
+    arr = (GemmTnDesc * len(descs))(*descs)
+    return bool(lib().cwn_gemm_tn_would_split(arr, len(descs)))
 
 
 def gemm_tn(descs: Sequence[GemmTnDesc], device, keep=None, deferrable: bool = False) -> None:

@@ -7,9 +7,23 @@
 
 namespace {
 
+// ReLU and the max fold, the one spelling for every kernel: a NaN operand gives NaN, as torch.relu and scatter amax do.
+// fmaxf / fmax return the operand that is NOT NaN (v_max_f32), which turns a diverged value into 0.  In float32 the
+// propagating maximum is one instruction as well (v_maximum3_f32); float64 has none, so its ReLU is the compare and select
+// and its cwn_max is what the compiler expands the builtin to: v_max_f64, an unordered compare and two selects.
+// (cwn_relu, not relu: kernels keep a flag of that name.)
+__device__ __forceinline__ float cwn_relu(float z) { return __builtin_elementwise_maximum(z, 0.f); }
+__device__ __forceinline__ double cwn_relu(double z) { return z < 0.0 ? 0.0 : z; }
+// ... and its gradient, from the activation's argument (or its output) y: the gradient passes unless y <= 0, torch's
+// threshold_backward, so where y is NaN the gradient that arrives is handed on and not replaced by 0.
+__device__ __forceinline__ float cwn_relu_bwd(float y, float dy) { return y <= 0.f ? 0.f : dy; }
+__device__ __forceinline__ double cwn_relu_bwd(double y, double dy) { return y <= 0.0 ? 0.0 : dy; }
+__device__ __forceinline__ float cwn_max(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+__device__ __forceinline__ double cwn_max(double a, double b) { return __builtin_elementwise_maximum(a, b); }
+
 template <int ACT>
 __device__ __forceinline__ float activate(float z) {
-    if constexpr (ACT == CWN_ACT_RELU) return fmaxf(z, 0.f);
+    if constexpr (ACT == CWN_ACT_RELU) return cwn_relu(z);
     else if constexpr (ACT == CWN_ACT_ELU) return z > 0.f ? z : expm1f(z);
     else if constexpr (ACT == CWN_ACT_TANH) return tanhf(z);
     else if constexpr (ACT == CWN_ACT_SIGMOID) return 1.0f / (1.0f + expf(-z));
@@ -18,7 +32,7 @@ __device__ __forceinline__ float activate(float z) {
 
 template <int ACT>
 __device__ __forceinline__ double activate(double v) {
-    if constexpr (ACT == CWN_ACT_RELU) return v < 0.0 ? 0.0 : v;
+    if constexpr (ACT == CWN_ACT_RELU) return cwn_relu(v);
     else if constexpr (ACT == CWN_ACT_ELU) return v > 0.0 ? v : expm1(v);
     else if constexpr (ACT == CWN_ACT_TANH) return tanh(v);
     else if constexpr (ACT == CWN_ACT_SIGMOID) return 1.0 / (1.0 + exp(-v));

@@ -35,7 +35,7 @@ struct AggBatch {
 
 using real = float;
 using desc_t = cwn_agg_desc;
-constexpr real kRealMax = FLT_MAX;
+constexpr real kNegInf = -__builtin_huge_valf();
 
 }  // namespace
 

@@ -4,7 +4,7 @@
 // per element type: cwn_aggregate.hip and cwn_aggregate_f64.hip each define, ahead of the include,
 //     using real = float | double;                  the element type
 //     using desc_t = cwn_agg_desc | cwn_agg_desc_f64;   the descriptor (one layout, `real` pointers)
-//     constexpr real kRealMax = FLT_MAX | DBL_MAX;
+//     constexpr real kNegInf = -infinity of the type;   where a max fold starts: a row of -Inf messages gives -Inf, as amax does
 // and, after it, the two functions that differ in more than the type: ld<VEC> / st<VEC> (declared
 // below).  The kernels stay in their files under their own names: the f32 kernel's speed is decided
 // by its register count and its instantiation names are pinned by tests/test_kernel_resources.py,
@@ -12,6 +12,7 @@
 // Aliases, not a template parameter, for that reason: nothing about a symbol's name changes.
 #pragma once
 #include "cwn_check.h"
+#include "cwn_act.h"
 
 namespace {
 
@@ -58,12 +59,12 @@ __device__ __forceinline__ Acc<VEC> message(const Acc<VEC>& a, const Acc<VEC>& b
         if constexpr (OP == CWN_MSG_A) m.v[k] = a.v[k];
         else if constexpr (OP == CWN_MSG_A_PLUS_B) m.v[k] = a.v[k] + b.v[k];
         else if constexpr (OP == CWN_MSG_A_TIMES_B) m.v[k] = a.v[k] * b.v[k];
-        else if constexpr (OP == CWN_MSG_RELU_A_PLUS_B) m.v[k] = fmax(a.v[k] + b.v[k], real(0.0));
+        else if constexpr (OP == CWN_MSG_RELU_A_PLUS_B) m.v[k] = cwn_relu(a.v[k] + b.v[k]);
         else if constexpr (OP == CWN_MSG_RELU_A_PLUS_B_SQ) {
-            const real r = fmax(a.v[k] + b.v[k], real(0.0));
+            const real r = cwn_relu(a.v[k] + b.v[k]);
             m.v[k] = r * r;
-        } else if constexpr (OP == CWN_MSG_A_TIMES_2RELU) m.v[k] = real(2.0) * a.v[k] * fmax(pre.v[k] + b.v[k], real(0.0));
-        else m.v[k] = (pre.v[k] + b.v[k] > real(0.0)) ? a.v[k] : real(0.0);
+        } else if constexpr (OP == CWN_MSG_A_TIMES_2RELU) m.v[k] = real(2.0) * a.v[k] * cwn_relu(pre.v[k] + b.v[k]);
+        else m.v[k] = cwn_relu_bwd(pre.v[k] + b.v[k], a.v[k]);
     }
     return m;
 }
@@ -72,7 +73,7 @@ template <int VEC, int RED>
 __device__ __forceinline__ void combine(Acc<VEC>& acc, const Acc<VEC>& m) {
 #pragma unroll
     for (int k = 0; k < VEC; ++k) {
-        if constexpr (RED == CWN_REDUCE_MAX) acc.v[k] = fmax(acc.v[k], m.v[k]);
+        if constexpr (RED == CWN_REDUCE_MAX) acc.v[k] = cwn_max(acc.v[k], m.v[k]);
         else acc.v[k] = acc.v[k] + m.v[k];
     }
 }
@@ -87,7 +88,7 @@ __device__ __forceinline__ Acc<VEC> fold_range(const desc_t& D, int start, int e
     constexpr bool kUsesB = (OP != CWN_MSG_A);
     const int F = D.F;
     const bool b_scalar = kUsesB && D.b_width == 1;
-    Acc<VEC> acc = splat<VEC>(RED == CWN_REDUCE_MAX ? -kRealMax : real(0.0));
+    Acc<VEC> acc = splat<VEC>(RED == CWN_REDUCE_MAX ? kNegInf : real(0.0));
     for (int base = start; base < end; base += G) {
         // cooperative index fetch: lane gl holds the indices of CSR position base+gl
         const int mine = base + gl;
@@ -158,7 +159,7 @@ __device__ __forceinline__ Acc<VEC> fold_range_split(const Operands D, int start
     const bool b_scalar = kUsesB && D.b_width == 1;
     const int S = G / GF, e = gl / GF, f = (gl % GF) * VEC;
     const bool active = f < F;
-    Acc<VEC> acc = splat<VEC>(RED == CWN_REDUCE_MAX ? -kRealMax : real(0.0));
+    Acc<VEC> acc = splat<VEC>(RED == CWN_REDUCE_MAX ? kNegInf : real(0.0));
     for (int base = start; base < end; base += G) {
         const int mine = base + gl;
         int my_ia = 0, my_ib = 0;

@@ -32,7 +32,7 @@ struct AggBatch64 {
 
 using real = double;
 using desc_t = cwn_agg_desc_f64;
-constexpr real kRealMax = DBL_MAX;
+constexpr real kNegInf = -__builtin_huge_val();
 
 }  // namespace
 

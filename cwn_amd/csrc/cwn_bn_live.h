@@ -53,7 +53,7 @@ __device__ __forceinline__ void bn_live_finish(const cwn_bn_live& L, const BnLiv
     invM = invM * (2.0 - Md * invM);
     const double mean = s * invM;
     double var = sq * invM - mean * mean;     // biased, as BatchNorm normalises
-    var = var > 0.0 ? var : 0.0;
+    var = var < 0.0 ? 0.0 : var;          // (this way round a NaN variance stays NaN, as in cwn_bn_finalize_f32)
     const double x = var + (double)L.eps;
     double y = (double)rsqrtf((float)x);
     y = y * (1.5 - 0.5 * x * y * y);

@@ -28,6 +28,7 @@
 #include "cwn_mem.h"
 #include "cwn_dropout.h"
 #include "cwn_check.h"
+#include "cwn_act.h"
 
 namespace {
 
@@ -540,7 +541,7 @@ __global__ __launch_bounds__(kHeadThreads) void head_kernel(HeadArgs A) {
             for (int q = 0; q < S; ++q) h += hpart[(size_t)d * 4 * kHeadThreads + q * H2 + tid];
             if (A.d[d].b1 != nullptr) h += A.d[d].b1[tid];
             if (A.d[d].h_out != nullptr) A.d[d].h_out[c * H2 + tid] = h;      // pre-activation: the backward's ReLU mask
-            float a = fmaxf(h, 0.f);
+            float a = cwn_relu(h);
             if (dpos == CWN_HEAD_DROP_FINAL) a *= drop.mul1(((uint64_t)d * (uint64_t)A.C + (uint64_t)c) * (uint64_t)H2 + (uint64_t)tid);
             s += a;
         }

@@ -35,6 +35,7 @@
 #include "../../include/cwn_hip.h"
 #include "cwn_mem.h"
 #include "cwn_check.h"
+#include "cwn_act.h"
 
 namespace {
 
@@ -164,7 +165,7 @@ __device__ __forceinline__ void stage_store(float* lds, Staged<ROWS, KP>& st, co
             float x = v[t];
             if constexpr (PRO) {
                 if (C.affine) x = x * C.sc[t] + C.sh[t];
-                if (C.relu) x = fmaxf(x, 0.f);
+                if (C.relu) x = cwn_relu(x);
             }
             v[t] = C.kk + t < C.kmax ? x : 0.f;
         }
@@ -243,7 +244,7 @@ __device__ __forceinline__ void stage_store_bnb(float* lds, const Staged<ROWS, K
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             const float y = z[t] * scale[t] + shift[t];
-            const float dyh = (!F.relu || y > 0.f) ? dy[t] : 0.f;
+            const float dyh = F.relu ? cwn_relu_bwd(y, dy[t]) : dy[t];
             const float d = scale[t] * dyh + c0[t] + c1[t] * (z[t] - mean[t]);
             v[t] = 4 * c + t < K ? d : 0.f;
         }
@@ -544,7 +545,7 @@ __global__ __launch_bounds__(kThreads, (KP <= 128 && RT == 2 && !(CWN_GEMM_NOSPI
                         csq[r] += (double)y * (double)y;
                     }
                     y = y * sc[r] + sh[r];
-                    acc[ct][rt][r] = D.relu ? fmaxf(y, 0.f) : y;
+                    acc[ct][rt][r] = D.relu ? cwn_relu(y) : y;
                 }
             }
             if (D.col_sum != nullptr && n0 < N) {

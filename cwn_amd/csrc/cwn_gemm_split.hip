@@ -29,6 +29,7 @@
 #include "cwn_split.h"
 #include "cwn_mem.h"
 #include "cwn_check.h"
+#include "cwn_act.h"
 
 namespace {
 
@@ -179,7 +180,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_split_kernel(SplitBatch B) {
                     }
                     if (relu) {
 #pragma unroll
-                        for (int q = 0; q < 4; ++q) y[q] = fmaxf(y[q], 0.0f);
+                        for (int q = 0; q < 4; ++q) y[q] = cwn_relu(y[q]);
                     }
                     cwn::store_result4(D.Y + row * D.ldy + n0, y[0], y[1], y[2], y[3]);
                 }

@@ -25,6 +25,7 @@
 #include "../../include/cwn_hip.h"
 #include "cwn_split.h"
 #include "cwn_check.h"
+#include "cwn_act.h"
 
 namespace {
 
@@ -153,7 +154,7 @@ __device__ __forceinline__ void tile_store(float* lds, const f32x4 (&v)[kU], con
             float y = x[t];
             const bool ok = row_ok && P.cc + t < P.cmax;
             if (P.affine) y = y * P.sc[t] + P.sh[t];
-            if (P.relu) y = fmaxf(y, 0.f);
+            if (P.relu) y = cwn_relu(y);
             x[t] = ok ? y : 0.f;      // rows past the band and columns past the matrix add nothing
         }
         *reinterpret_cast<f32x4*>(lds + r * kLd + 4 * c) = x;
@@ -365,7 +366,7 @@ __device__ __forceinline__ f32x4 chunk_store_one(uint16_t* planes, const f32x4 (
             const bool ok = row_ok && P.cc + t < P.cmax;
             if constexpr (!PLAIN) {
                 if (P.affine) y = y * P.sc[t] + P.sh[t];
-                if (P.relu) y = fmaxf(y, 0.f);
+                if (P.relu) y = cwn_relu(y);
             }
             x[t] = ok ? y : 0.f;
         }
@@ -553,7 +554,33 @@ inline size_t tn_ws_floats(const cwn_gemm_tn_desc& D) {
     return bands * (size_t)D.N * (size_t)(D.K + D.K2) + bands * (size_t)D.N;
 }
 
+// operands the vector loads of both kernels need: 16-byte aligned, strides and widths multiples of 4
+bool tn_fast(const cwn_gemm_tn_desc& D) {
+    return al16(D.dZ) && al16(D.X) && al16(D.X2) && D.lddz % 4 == 0 && D.ldx % 4 == 0 && (D.K2 == 0 || D.ldx2 % 4 == 0) &&
+           D.N % 4 == 0 && D.K % 4 == 0 && D.K2 % 4 == 0;
+}
+
+// Which kernel serves a launch.  The bf16-split kernel (128 x 128 tiles, 32-row chunks) when most descriptors fill its tile: at
+// hidden 64 -- every dW at most 64 rows -- a 128 x 128 tile is a quarter full and the launch is the same memory pipeline for half
+// the useful bytes; the fp32-MFMA kernel's 64 x 64 tiles, four workgroups deep per CU, are faster there (round 5, graph-replayed
+// training steps: molhiv-512 0.802 -> 0.756 ms, reddit-32 1.597 -> 1.449 ms with CWN_TN_SPLIT=0; ZINC-128 at hidden 128 keeps the
+// split form) (by majority: a hidden-64 model's launch holds forty gradients of 64 rows and the head's three of 128)
+bool tn_split(const cwn_gemm_tn_desc* descs, int n, bool fast) {
+    static const bool split_off = getenv("CWN_TN_SPLIT") != nullptr && atoi(getenv("CWN_TN_SPLIT")) == 0;
+    static const bool split_force = getenv("CWN_TN_SPLIT") != nullptr && atoi(getenv("CWN_TN_SPLIT")) == 2;
+    int n_wide = 0;
+    for (int i = 0; i < n; ++i) n_wide += descs[i].N > 64 ? 1 : 0;
+    return fast && !split_off && (2 * n_wide >= n || split_force);
+}
+
 }  // namespace
+
+extern "C" int cwn_gemm_tn_would_split(const cwn_gemm_tn_desc* descs, int n) {
+    if (descs == nullptr || n <= 0 || n > CWN_GEMM_TN_MAX_DESCS) return 0;
+    bool fast = true;
+    for (int i = 0; i < n; ++i) fast = fast && tn_fast(descs[i]);
+    return tn_split(descs, n, fast) ? 1 : 0;
+}
 
 extern "C" size_t cwn_gemm_tn_workspace_bytes(const cwn_gemm_tn_desc* descs, int n) {
     if (descs == nullptr || n <= 0 || n > CWN_GEMM_TN_MAX_DESCS) return 0;
@@ -581,20 +608,10 @@ extern "C" int cwn_gemm_tn_f32(const cwn_gemm_tn_desc* descs, int n, void* works
         const void* ptrs[] = {D.dZ, D.X, D.X2, D.dW, D.db};
         for (const void* p : ptrs)
             if (p != nullptr && ((uintptr_t)p & 3u)) return CWN_ERR_ALIGN;
-        fast = fast && al16(D.dZ) && al16(D.X) && al16(D.X2) && D.lddz % 4 == 0 && D.ldx % 4 == 0 &&
-               (D.K2 == 0 || D.ldx2 % 4 == 0) && D.N % 4 == 0 && D.K % 4 == 0 && D.K2 % 4 == 0;
+        fast = fast && tn_fast(D);
         B.d[i] = D;
     }
-    static const bool split_off = getenv("CWN_TN_SPLIT") != nullptr && atoi(getenv("CWN_TN_SPLIT")) == 0;
-    // the bf16-split kernel (128 x 128 tiles, 32-row chunks) when most descriptors fill its tile: at hidden 64 -- every dW at most
-    // 64 rows -- a 128 x 128 tile is a quarter full and the launch is the same memory pipeline for half the useful bytes; the
-    // fp32-MFMA kernel's 64 x 64 tiles, four workgroups deep per CU, are faster there (round 5, graph-replayed training steps:
-    // molhiv-512 0.802 -> 0.756 ms, reddit-32 1.597 -> 1.449 ms with CWN_TN_SPLIT=0; ZINC-128 at hidden 128 keeps the split form)
-    // (by majority: a hidden-64 model's launch holds forty gradients of 64 rows and the head's three of 128)
-    int n_wide = 0;
-    for (int i = 0; i < n; ++i) n_wide += descs[i].N > 64 ? 1 : 0;
-    static const bool split_force = getenv("CWN_TN_SPLIT") != nullptr && atoi(getenv("CWN_TN_SPLIT")) == 2;
-    const bool split = fast && !split_off && (2 * n_wide >= n || split_force);
+    const bool split = tn_split(descs, n, fast);
     const int tile = split ? kTile2 : kTile;
     for (int i = 0; i < n; ++i) {
         if ((descs[i].N + tile - 1) / tile > INT16_MAX || (descs[i].K + descs[i].K2 + tile - 1) / tile > INT16_MAX) return CWN_ERR_TOO_LARGE;

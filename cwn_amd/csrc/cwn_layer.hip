@@ -58,6 +58,7 @@
 #include "../../include/cwn_hip.h"
 #include "cwn_split.h"
 #include "cwn_check.h"
+#include "cwn_act.h"
 
 namespace {
 
@@ -402,10 +403,10 @@ __device__ __forceinline__ void gather_relu_sum(float4 (&acc)[NR], const RowSet<
         for (int u = 0; u < NR; ++u)
 #pragma unroll
             for (int v = 0; v < 2; ++v) {
-                acc[u].x += fmaxf(a[u][v].x + b[u][v].x, 0.0f);
-                acc[u].y += fmaxf(a[u][v].y + b[u][v].y, 0.0f);
-                acc[u].z += fmaxf(a[u][v].z + b[u][v].z, 0.0f);
-                acc[u].w += fmaxf(a[u][v].w + b[u][v].w, 0.0f);
+                acc[u].x += cwn_relu(a[u][v].x + b[u][v].x);
+                acc[u].y += cwn_relu(a[u][v].y + b[u][v].y);
+                acc[u].z += cwn_relu(a[u][v].z + b[u][v].z);
+                acc[u].w += cwn_relu(a[u][v].w + b[u][v].w);
             }
     }
 }
@@ -727,8 +728,8 @@ __global__ __launch_bounds__(kThreads) CWN_LAYER_OCCUPANCY void layer_kernel(con
 #pragma unroll
                             for (int u = 0; u < 4; ++u)
                                 if (p + u < e_) {
-                                    au.x += fmaxf(y[u].x + z[u].x, 0.0f); au.y += fmaxf(y[u].y + z[u].y, 0.0f);
-                                    au.z += fmaxf(y[u].z + z[u].z, 0.0f); au.w += fmaxf(y[u].w + z[u].w, 0.0f);
+                                    au.x += cwn_relu(y[u].x + z[u].x); au.y += cwn_relu(y[u].y + z[u].y);
+                                    au.z += cwn_relu(y[u].z + z[u].z); au.w += cwn_relu(y[u].w + z[u].w);
                                 }
                         }
                     }

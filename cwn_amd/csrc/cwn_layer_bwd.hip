@@ -36,6 +36,7 @@
 #include "../../include/cwn_hip.h"
 #include "cwn_split.h"
 #include "cwn_check.h"
+#include "cwn_act.h"
 
 namespace {
 
@@ -184,10 +185,10 @@ __global__ __launch_bounds__(kThreads) void layer_bwd_kernel(BwdArgs A) {
                         const float4 a = *reinterpret_cast<const float4*>(S + (size_t)j * G::kYStride + f);
                         const float4 b = *reinterpret_cast<const float4*>(S + (size_t)(R1 + c) * G::kYStride + f);
                         const float4 mm = *reinterpret_cast<const float4*>(T + (size_t)i * G::kYStride + f);
-                        acc.x += a.x + b.x > 0.f ? mm.x : 0.f;
-                        acc.y += a.y + b.y > 0.f ? mm.y : 0.f;
-                        acc.z += a.z + b.z > 0.f ? mm.z : 0.f;
-                        acc.w += a.w + b.w > 0.f ? mm.w : 0.f;
+                        acc.x += cwn_relu_bwd(a.x + b.x, mm.x);
+                        acc.y += cwn_relu_bwd(a.y + b.y, mm.y);
+                        acc.z += cwn_relu_bwd(a.z + b.z, mm.z);
+                        acc.w += cwn_relu_bwd(a.w + b.w, mm.w);
                     }
                 }
                 own[k] = acc;

@@ -29,6 +29,7 @@
 #include "cwn_split.h"
 #include "cwn_layer_bwd_own.h"
 #include "cwn_check.h"
+#include "cwn_act.h"
 
 namespace {
 
@@ -106,10 +107,10 @@ __device__ __forceinline__ void walk_matches(const int* key, int n4, int e_first
 }
 
 __device__ __forceinline__ void add_masked(float4& acc, const float4& a, const float4& b, const float4& m) {
-    acc.x += a.x + b.x > 0.f ? m.x : 0.f;
-    acc.y += a.y + b.y > 0.f ? m.y : 0.f;
-    acc.z += a.z + b.z > 0.f ? m.z : 0.f;
-    acc.w += a.w + b.w > 0.f ? m.w : 0.f;
+    acc.x += cwn_relu_bwd(a.x + b.x, m.x);
+    acc.y += cwn_relu_bwd(a.y + b.y, m.y);
+    acc.z += cwn_relu_bwd(a.z + b.z, m.z);
+    acc.w += cwn_relu_bwd(a.w + b.w, m.w);
 }
 
 template <int F>
@@ -593,7 +594,7 @@ __global__ __launch_bounds__(kThreads) void layer_bwd_own_kernel(const int32_t* 
 #pragma unroll
         for (int q = 0; q < 4; ++q) {                    // (cwn_stage.hip's producer epilogue: the same arithmetic)
             const float y = z_[q] * sc[q] + sh[q];
-            const float dyh = y > 0.f ? d_[q] : 0.f;
+            const float dyh = cwn_relu_bwd(y, d_[q]);
             a1[q] += dyh;
             a2[q] += dyh * ((z_[q] - mu[q]) * rs[q]);
         }

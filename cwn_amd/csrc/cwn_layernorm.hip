@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include "../../include/cwn_hip.h"
 #include "cwn_check.h"
+#include "cwn_act.h"
 
 namespace {
 
@@ -141,14 +142,14 @@ __device__ __forceinline__ void fwd_band(const cwn_ln_desc& D, int64_t row0, int
             // one ulp of the mean (a correction of the two-pass variance, not E[x^2] - mean^2)
             const float c = s1 / fN;
             float var = s2 / fN - c * c;
-            var = var > 0.f ? var : 0.f;
+            var = var < 0.f ? 0.f : var;              // (a NaN variance stays NaN)
             mean += c;
             const float rstd = 1.0f / sqrtf(var + D.eps);
             float o[4 * C];
 #pragma unroll
             for (int e = 0; e < 4 * C; ++e) {
                 const float y = (x[q][e] - c) * rstd * gm[e] + bt[e];
-                o[e] = relu ? fmaxf(y, 0.f) : y;
+                o[e] = relu ? cwn_relu(y) : y;
             }
             st_row<VEC, C>(D.out + r * D.ldout, o, lane, N);
             if (lane == 0 && D.mean != nullptr) D.mean[r] = mean;

@@ -19,6 +19,7 @@
 #include "cwn_bn_live.h"
 #include "cwn_dropout.h"
 #include "cwn_check.h"
+#include "cwn_act.h"
 
 namespace {
 
@@ -94,7 +95,7 @@ __global__ __launch_bounds__(kFinThreads) void bn_finalize_kernel(BnBatch B) {
     const double invM = 1.0 / (double)(Mv > 0 ? Mv : 1);
     const double mean = s * invM;
     double var = sq * invM - mean * mean;     // biased, as BatchNorm normalises
-    var = var > 0.0 ? var : 0.0;
+    var = var < 0.0 ? 0.0 : var;          // (this way round a NaN variance stays NaN: Inf - Inf of an overflowed column)
     const float rstd = (float)(1.0 / sqrt(var + (double)D.eps));
     const float g = D.gamma != nullptr ? D.gamma[n] : 1.0f;
     const float beta = D.beta != nullptr ? D.beta[n] : 0.0f;
@@ -253,9 +254,9 @@ __global__ __launch_bounds__(kThreads) void norm_kernel(NormBatch B) {
             for (int v = 0; v < VEC; ++v) {
                 const float y = z[i][v] * scale[v] + shift[v];
                 if constexpr (MODE == 0) {
-                    o[v] = relu ? fmaxf(y, 0.f) : y;
+                    o[v] = relu ? cwn_relu(y) : y;
                 } else {
-                    const float dyh = (!relu || y > 0.f) ? g[i][v] : 0.f;
+                    const float dyh = relu ? cwn_relu_bwd(y, g[i][v]) : g[i][v];
                     const float xhat = (z[i][v] - mean[v]) * rstd[v];
                     if constexpr (MODE == 1) {
                         if (ok) {
@@ -346,7 +347,7 @@ __global__ __launch_bounds__(kFT) void norm_bwd_fused_kernel(NormBatch B, int ac
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
             const float y = z[i][v] * scale[v] + shift[v];
-            const float dyh = (!relu || y > 0.f) ? g[i][v] : 0.f;
+            const float dyh = relu ? cwn_relu_bwd(y, g[i][v]) : g[i][v];
             const float xhat = (z[i][v] - mean[v]) * rstd[v];
             g[i][v] = dyh;
             z[i][v] = xhat;
@@ -822,7 +823,7 @@ __global__ __launch_bounds__(256) void loss_kernel(const float* __restrict__ pre
         float l, gr;
         if (kind == CWN_LOSS_L1) {
             l = fabsf(d);
-            gr = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);             // torch: sign(0) = 0
+            gr = d > 0.f ? 1.f : (d < 0.f ? -1.f : d + 0.f);         // torch: sign(+-0) = +0 (-0 + 0 = +0), sign(NaN) = NaN
         } else if (kind == CWN_LOSS_MSE) {
             l = d * d;
             gr = 2.f * d;

@@ -131,7 +131,7 @@ __device__ __forceinline__ void dense_stage_body(const BatchT& B) {
             const int idx = threadIdx.x + i * kThreads, r = idx / (F / 4), c4 = idx % (F / 4);
             float4 x = v[i];
             if (p.affine) x = make_float4(x.x * p.sc.x + p.sh.x, x.y * p.sc.y + p.sh.y, x.z * p.sc.z + p.sh.z, x.w * p.sc.w + p.sh.w);
-            if (p.relu) x = make_float4(fmaxf(x.x, 0.f), fmaxf(x.y, 0.f), fmaxf(x.z, 0.f), fmaxf(x.w, 0.f));
+            if (p.relu) x = make_float4(cwn_relu(x.x), cwn_relu(x.y), cwn_relu(x.z), cwn_relu(x.w));
             WT::store_planes(buf, r, c4 * 4, x);
         }
     };
@@ -405,7 +405,7 @@ __global__ __launch_bounds__(kThreads, 4) void dense_stage_bwd_kernel(StageBwdBa
         const float4 dy = vy[i], z = vz[i];
         auto one = [&](float dyv, float zv, float s, float h, float m, float a0, float a1) {
             const float y = zv * s + h;
-            const float dyh = (!relu || y > 0.f) ? dyv : 0.f;
+            const float dyh = relu ? cwn_relu_bwd(y, dyv) : dyv;
             return s * dyh + a0 + a1 * (zv - m);
         };
         const float4 d = make_float4(one(dy.x, z.x, sc.x, sh.x, mu.x, c0.x, c1.x), one(dy.y, z.y, sc.y, sh.y, mu.y, c0.y, c1.y),
@@ -455,7 +455,7 @@ __global__ __launch_bounds__(kThreads, 4) void dense_stage_bwd_kernel(StageBwdBa
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const float y = zv[q] * sc[q] + sh[q];
-                const float dyh = (ok && y > 0.f) ? acc[rt][q] : 0.f;
+                const float dyh = ok ? cwn_relu_bwd(y, acc[rt][q]) : 0.f;
                 a1[q] += dyh;
                 a2[q] += dyh * ((zv[q] - mu[q]) * rs[q]);
             }

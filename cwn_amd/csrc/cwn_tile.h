@@ -29,6 +29,7 @@
 #include "../../include/cwn_hip.h"
 #include "cwn_split.h"
 #include "cwn_check.h"
+#include "cwn_act.h"
 #include "cwn_mem.h"
 
 namespace cwn {
@@ -167,7 +168,7 @@ template <class S> struct WaveTile {
                 o[3] = o[3] * sc.w + sh.w;
             }
 #pragma unroll
-            for (int q = 0; q < 4; ++q) o[q] = fmaxf(o[q], 0.0f);
+            for (int q = 0; q < 4; ++q) o[q] = cwn_relu(o[q]);
             const int r = (rt0 + rt) * 16 + l15;
             if (buf != nullptr) store_planes<1>(buf, r, n0, make_float4(o[0], o[1], o[2], o[3]));
             else if (row0 + r < Mv) store_result4(D.y + (row0 + r) * D.ldy + n0, o[0], o[1], o[2], o[3]);

@@ -166,7 +166,8 @@ int cwn_gather_rows_f32(const float* src, int64_t n_src, int64_t F, const int64_
  *                                                            ReLU(Linear(cat(x_j, up_attr))),
  *                                                            mp/layers.py:290-293, restructured as
  *                                                            A = X_d W1^T + b, B = X_{d+1} W2^T
- *     CWN_MSG_A_MASK_RELU  A[ia[p], :] * step(self_pre[i,:] + B[ib[p], :] > 0)
+ *     CWN_MSG_A_MASK_RELU  self_pre[i,:] + B[ib[p], :] <= 0 ? 0 : A[ia[p], :]      ReLU's gradient as torch's threshold_backward
+ *                                                            has it: where the argument is NaN the gradient A passes
  *     CWN_MSG_RELU_A_PLUS_B_SQ  relu(A[ia[p], :] + B[ib[p], :])^2   the second moment of the CIN messages: BatchNorm(train) over
  *                               the ENTRIES of an adjacency (mp/models.py:40-47 conv_up / conv_down in training mode) needs
  *                               sum_e r_e and sum_e r_e^2 per column -- the column sums of two aggregations
@@ -1066,6 +1067,10 @@ typedef struct cwn_gemm_tn_desc {
 size_t cwn_gemm_tn_workspace_bytes(const cwn_gemm_tn_desc* descs_host, int n);
 int cwn_gemm_tn_f32(const cwn_gemm_tn_desc* descs_host, int n, void* workspace, size_t workspace_bytes,
                     cwn_stream_t stream);
+/* 1 when cwn_gemm_tn_f32 would run these descriptors on its bf16-split kernel (most of them have N > 64 and every operand is
+ * 16-byte aligned with strides and widths that are multiples of 4; the environment's CWN_TN_SPLIT = 0 / 2 forbids / forces
+ * it), else 0: there, as in cwn_gemm_would_split's launches, an Inf operand gives NaN.  Launches nothing. */
+int cwn_gemm_tn_would_split(const cwn_gemm_tn_desc* descs_host, int n);
 
 /* ------------------------------------------------------------------------------------------
  * OrientedConv as one launch (csrc/cwn_oriented.hip).

@@ -286,6 +286,16 @@ def _bn(h: Tensor, p: Dict, prefix: str, training: bool, eps: float = 1e-5) -> T
     return (h - mean) / torch.sqrt(var + eps) * w + b
 
 
+def _norm(h: Tensor, p: Dict, prefix: str, training: bool, norm: str) -> Tensor:
+    """The graph norm of a sub-network: 'bn' (BatchNorm1d), 'ln' (torch.nn.LayerNorm over the features, the same in
+    training and eval), anything else: Identity."""
+    if norm == 'bn':
+        return _bn(h, p, prefix, training)
+    if norm == 'ln':
+        return torch.nn.functional.layer_norm(h, (h.size(-1),), p[prefix + '.weight'], p[prefix + '.bias'])
+    return h
+
+
 def _lin(h: Tensor, p: Dict, prefix: str) -> Tensor:
     return h @ p[prefix + '.weight'].t() + p[prefix + '.bias']
 
@@ -294,12 +304,10 @@ def _mlp2(h: Tensor, p: Dict, prefix: str, training: bool, norm: str) -> Tensor:
     """mp/layers.py:303-321: Linear -> norm -> ReLU -> Linear -> norm -> ReLU (Sequential ids
     0..5)."""
     h = _lin(h, p, prefix + '.0')
-    if norm == 'bn':
-        h = _bn(h, p, prefix + '.1', training)
+    h = _norm(h, p, prefix + '.1', training, norm)
     h = torch.relu(h)
     h = _lin(h, p, prefix + '.3')
-    if norm == 'bn':
-        h = _bn(h, p, prefix + '.4', training)
+    h = _norm(h, p, prefix + '.4', training, norm)
     return torch.relu(h)
 
 
@@ -328,8 +336,7 @@ def sparse_cin_cochain_conv(p: Dict, prm: Dict, use_coboundaries: bool, training
     out_up = _mlp2(out_up, p, 'update_up_nn', training, norm)
     out_b = _mlp2(out_b, p, 'update_boundaries_nn', training, norm)
     h = _lin(torch.cat([out_up, out_b], dim=-1), p, 'combine_nn.0')
-    if norm == 'bn':
-        h = _bn(h, p, 'combine_nn.1', training)
+    h = _norm(h, p, 'combine_nn.1', training, norm)
     return torch.relu(h)
 
 

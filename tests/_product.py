@@ -46,6 +46,39 @@ def gate(got, ref, what: str = '', tol: float = 1e-5) -> float:
     return err
 
 
+def gate_nonfinite(got, ref, what: str = '', tol: float = 1e-5, exact_mask: bool = True, local: bool = True,
+                   require_nonfinite: bool = True) -> float:
+    """The non-finite contract ("Non-finite values"), `ref` being the same operation in plain torch, in float64
+    on the CPU:
+      (a) wherever `ref` is non-finite, `got` is non-finite;
+      (b) with `exact_mask`, wherever `got` is non-finite, `ref` is: a poison does not leak into another row or complex;
+      (c) on the entries finite in both, gate()'s bound, its scale taken over the finite entries of `ref`;
+      (d) the case says something: `ref` has a non-finite entry and, where the operation is row- or complex-local (`local`),
+          a finite one as well.  `require_nonfinite=False` leaves (d) out: for a tensor of a launch that the poison does not
+          reach (another dimension's network, another complex), which is still held to (a) - (c).
+    The counts are printed as gate() prints its error.  Returns the error of (c)."""
+    g = got.detach().cpu().double()
+    r = ref.detach().cpu().double()
+    assert g.shape == r.shape, (what, tuple(g.shape), tuple(r.shape))
+    gn, rn = ~torch.isfinite(g), ~torch.isfinite(r)
+    missed, leaked, both = int((rn & ~gn).sum()), int((gn & ~rn).sum()), ~gn & ~rn
+    scale = max(1.0, float(r[~rn].abs().max())) if bool((~rn).any()) else 1.0
+    err = float((g[both] - r[both]).abs().max()) if bool(both.any()) else 0.0
+    print(f'[gate_nonfinite] {what}: ref non-finite {int(rn.sum())} of {r.numel()}, got non-finite {int(gn.sum())}; '
+          f'finite where ref is not: {missed}; non-finite where ref is finite: {leaked} '
+          f'({"checked" if exact_mask else "allowed here"}); on the {int(both.sum())} finite entries max|delta| = {err:.3e}, '
+          f'|ref|_inf = {scale:.3g}, bound = {tol * scale:.3e}')
+    if require_nonfinite:
+        assert bool(rn.any()), f'{what}: the reference has no non-finite entry, the case checks nothing'
+        if local:
+            assert bool((~rn).any()), f'{what}: the reference has no finite entry, a leak could not show'
+    assert missed == 0, f'{what}: {missed} entries are finite where the reference is NaN / Inf'
+    if exact_mask:
+        assert leaked == 0, f'{what}: {leaked} entries are non-finite where the reference is finite'
+    assert err <= tol * scale, f'{what}: max|delta| {err:.3e} > {tol * scale:.3e} on the finite entries'
+    return err
+
+
 def deviation(t, ref64) -> float:
     """max |t - ref64| in float64 (0 for empty tensors)."""
     r = ref64.detach().cpu().double()

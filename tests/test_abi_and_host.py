@@ -934,3 +934,20 @@ def test_by_module_mapping_forgets_dead_modules_and_never_answers_for_a_recycled
     net = torch.nn.Sequential(torch.nn.Linear(2, 2))
     c[net] = 'x'
     assert copy.deepcopy(net) not in c           # a copy is another module: it has no prepared launches
+
+
+def test_gemm_tn_would_split_is_the_launchers_rule():
+    """cwn_gemm_tn_would_split (a pure function of the descriptors, CWN_TN_SPLIT unset; nothing is launched or dereferenced):
+    the bf16-split kernel when most descriptors are wider than 64 and every operand suits its vector loads."""
+    lib = _ffi.lib()
+
+    def d(N, K, X=1 << 20, ldx=None):
+        return _ffi.GemmTnDesc(dZ=1 << 21, X=X, dW=1 << 22, M=70, lddz=N, ldx=ldx or K, lddw=K, N=N, K=K, K2=0)
+
+    def would(*ds):
+        return lib.cwn_gemm_tn_would_split((_ffi.GemmTnDesc * len(ds))(*ds), len(ds))
+
+    assert would(d(128, 128)) == 1 and would(d(64, 64)) == 0 and would(d(40, 24)) == 0
+    assert would(d(128, 128, X=(1 << 20) + 4)) == 0 and would(d(128, 128, ldx=130)) == 0       # alignment, stride
+    assert would(d(128, 128), d(64, 64)) == 1 and would(d(128, 128), d(64, 64), d(64, 64)) == 0    # by majority
+    assert lib.cwn_gemm_tn_would_split(None, 1) == 0 and would(*[d(128, 128)] * (_ffi.MAX_TN_DESCS + 1)) == 0
