@@ -18,6 +18,11 @@ import numpy as np
 import torch
 
 ITEM_INTS = 32                 # = CWN_LAYER_ITEM_INTS
+# fields of a forward record: = csrc/cwn_items.h (layout: include/cwn_hip.h); task t at I_TASK0 + t * T_INTS
+I_FLAGS, I_G, I_GR0, I_GN, I_CR0, I_CN, I_UE0, I_UNE, I_NT, I_TASK0 = range(10)
+I_R1, I_ROWS, I_B1, I_B2, I_TOTAL = range(23, 28)
+T_DIM, T_R0, T_N, T_BE0, T_BNE, T_SR0, T_SN, T_INTS = range(8)
+ITEM_BIG = 2                   # = CWN_LAYER_ITEM_BIG (a bit of I_FLAGS)
 TASK_ROWS = 192                # = CWN_LAYER_TASK_ROWS
 MAX_ENTRIES = 1024             # = CWN_LAYER_MAX_ENTRIES
 CSR_SLOT_BYTES = 5264          # = CWN_LAYER_CSR_SLOT_BYTES
@@ -57,7 +62,7 @@ class ItemTable:
         self.lds_bytes = int(lds_bytes)    # variant 1: dynamic LDS of the launch (the largest per-item need)
         self.n_big = int(n_big)            # BIG records: complexes a workgroup streams (include/cwn_hip.h)
         # (set, complex) of every BIG record and what the launch needs for them (ops.LayerLaunch fills it in)
-        self.big_records = table[(table[:, 0] & 2) != 0].copy() if n_big else None
+        self.big_records = table[(table[:, I_FLAGS] & ITEM_BIG) != 0].copy() if n_big else None
         self.big_ctx = None
         self.n_items = int(table.shape[0])
         self.items = torch.from_numpy(table)

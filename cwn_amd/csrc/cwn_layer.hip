@@ -59,6 +59,7 @@
 #include "cwn_split.h"
 #include "cwn_check.h"
 #include "cwn_act.h"
+#include "cwn_items.h"
 
 namespace {
 
@@ -114,9 +115,8 @@ constexpr int kEcap = CWN_LAYER_MAX_ENTRIES;
 constexpr int kEI = kEcap / kThreads;       // COO entries per thread
 constexpr int kTaskRows = CWN_LAYER_TASK_ROWS;
 
-// item record fields (include/cwn_hip.h)
-enum { I_FLAGS = 0, I_G, I_GR0, I_GN, I_CR0, I_CN, I_UE0, I_UNE, I_NT, I_TASK0, I_R1 = 23, I_ROWS, I_B1, I_B2, I_TOTAL };
-enum { T_DIM = 0, T_R0, T_N, T_BE0, T_BNE, T_SR0, T_SN, T_INTS };
+// item record fields I_* / T_* (layout: include/cwn_hip.h) and the rule of the derived ones: cwn_items.h
+using namespace cwn_items;
 
 // One SET = the items that share a GEMM dimension (cwn_amd/blockplan.py): the launcher resolves every
 // pointer such an item needs into one flat record of 8-byte fields, and a workgroup reads the record
@@ -1397,14 +1397,11 @@ extern "C" size_t CWN_FN(lds_bytes)(int32_t F, int32_t max_gemm_rows, int32_t ma
 }
 
 // Host-side check of a HOST copy of the item table against its plan: every derived field is what
-// include/cwn_hip.h defines, every range lies inside the plan's summary, every item fits the caps.  The
+// cwn_items.h derives (layout: include/cwn_hip.h), every range lies inside the plan's summary, every item fits the caps.  The
 // kernel itself re-checks only what keeps a workgroup inside its LDS.
 extern "C" int CWN_FN(items_check)(const int32_t* items, int64_t n_items, int32_t F, const cwn_layer_plan* plan) {
     if (plan == nullptr || n_items < 0 || (n_items > 0 && items == nullptr) || (F != 64 && F != 128)) return CWN_ERR_BAD_ARG;
     if (plan->n_items != n_items) return CWN_ERR_BAD_ARG;
-    const int ng = kThreads / (F / 4);
-    auto pad16 = [](int64_t n) { return (n + 15) / 16 * 16; };
-    auto pad4 = [](int64_t n) { return (n + 3) / 4 * 4; };
     int64_t n_big = 0;
     for (int64_t it = 0; it < n_items; ++it) {
         const int32_t* r = items + it * CWN_LAYER_ITEM_INTS;
@@ -1456,11 +1453,9 @@ extern "C" int CWN_FN(items_check)(const int32_t* items, int64_t n_items, int32_
             ++n_big;
             continue;
         }
-        const int64_t r1 = pad16(n0);                      // (round 4: no longer a whole number of rounds of `ng` rows)
-        (void)ng;
-        const int64_t rows = nc > 0 ? r1 + pad16(nc) : pad16(n0);
-        const int64_t b1 = pad4(une), b2 = pad4(b1 + bne[0]), total = pad4(b2 + bne[1]);
-        if (r[I_R1] != r1 || r[I_ROWS] != rows || r[I_B1] != b1 || r[I_B2] != b2 || r[I_TOTAL] != total) return CWN_ERR_BAD_ARG;
+        const Derived D = derived(n0, nc, une, bne[0], bne[1]);         // the builders' own rule (cwn_items.h)
+        const int64_t rows = D.rows, total = D.total;
+        if (r[I_R1] != D.r1 || r[I_ROWS] != rows || r[I_B1] != D.b1 || r[I_B2] != D.b2 || r[I_TOTAL] != total) return CWN_ERR_BAD_ARG;
         for (int k = I_TOTAL + 1; k < CWN_LAYER_ITEM_INTS; ++k)
             if (r[k] != 0) return CWN_ERR_BAD_ARG;
         // sources that take LDS: both tasks' in the 16-wave form, task 0's in the two-per-CU form

@@ -37,6 +37,7 @@
 #include "cwn_split.h"
 #include "cwn_check.h"
 #include "cwn_act.h"
+#include "cwn_items.h"
 
 namespace {
 
@@ -45,8 +46,7 @@ using cwn::frag_cd;
 constexpr int kThreads = 1024;
 constexpr int kWaves = kThreads / 64;
 
-enum { I_FLAGS = 0, I_G, I_GR0, I_GN, I_CR0, I_CN, I_UE0, I_UNE, I_NT, I_TASK0, I_R1 = 23, I_ROWS };
-enum { T_DIM = 0, T_R0, T_N, T_BE0, T_BNE, T_SR0, T_SN, T_INTS };
+using namespace cwn_items;            // the forward record's fields I_* / T_* (this launch runs over the forward's table)
 
 struct BwdArgs {
     cwn_layer_bwd_dim d[CWN_LAYER_MAX_DIMS];

@@ -1,6 +1,6 @@
 // cwn_layer_bwd_own.h -- record fields and LDS layout of the OWNER form of the blocked backward launch
-// (cwn_layer_bwd_own_f32): shared by the kernel (cwn_layer_bwd_own.hip) and the host table builder
-// (cwn_blockplan.cpp: cwn_layer_bwd_items_build), so that both derive one item's layout from its record the same way.
+// (cwn_layer_bwd_own_f32): shared by the kernel (cwn_layer_bwd_own.hip) and the rule that writes the records
+// (cwn_items.h: BwdRule, which the host and the device table builders call), so that all derive one item's layout the same way.
 // Record layout: include/cwn_hip.h.
 #pragma once
 #include <stdint.h>

@@ -28,6 +28,7 @@ from torch import Tensor
 from torch.nn import BatchNorm1d as BN, Linear, ReLU, Sequential
 
 from . import ops
+from .blockplan import I_CN, I_TASK0, T_N
 from .cell_mp import CochainMessagePassing, CochainMessagePassingParams, IndexedRows, _zero_dtype, dense
 from .csr import Adjacency, cached_adjacency
 
@@ -159,7 +160,7 @@ def _streaming_pays(table, F: int) -> bool:
     / two-kernel path): molhiv-512 with 5 % giants of 60 - 200 atoms 0.87 / 0.43, ZINC-512 0.77 / 0.67, ZINC-128 0.38 /
     0.54 -- the one case that keeps the two-kernel path: a launch of 9 us cannot hide a 30-us workgroup."""
     recs = table.big_records
-    rows = max(int(r[11]) + int(r[5]) for r in recs)
+    rows = max(int(r[I_TASK0 + T_N]) + int(r[I_CN]) for r in recs)
     t_big = (0.07 if F == 128 else 0.035) * rows
     rounds = max(1, -(-(table.n_items - table.n_big) // TWO_PER_CU_MIN_ITEMS))
     return t_big < 1.9 * 8.7 * rounds

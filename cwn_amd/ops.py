@@ -3695,6 +3695,7 @@ class LayerLaunch:
         needs (a) the destination-sorted CSR of THEIR entries of every adjacency, in global cell numbers -- built here
         once per batch from slices of the batch's own index tensors (the table records where each complex's entries
         lie), cached on the table for all layers -- and (b) scratch matrices for Y1 / Y2."""
+        from .blockplan import I_FLAGS, I_G, I_NT, I_TASK0, I_UE0, I_UNE, T_BE0, T_BNE, T_DIM, T_INTS
         from .csr import Adjacency, build_many
         key = tuple((id(t), _ffi.tver(t)) for D in dims for t in (D.up_index, D.up_shared, D.b_index) if t is not None)
         ctx = table.big_ctx
@@ -3708,7 +3709,7 @@ class LayerLaunch:
                 N = int(D.x.size(0))
                 c = ctx['dims'][d]
                 if D.up_index is not None and D.up_index.size(1) > 0:
-                    sl = [(int(r[6]), int(r[7])) for r in recs if (r[0] & 1) and int(r[1]) == d and r[7] > 0]
+                    sl = [(int(r[I_UE0]), int(r[I_UNE])) for r in recs if (r[I_FLAGS] & 1) and int(r[I_G]) == d and r[I_UNE] > 0]
                     if sl:
                         idx = torch.cat([D.up_index[:, a:a + m] for a, m in sl], 1).contiguous()
                         sh = torch.cat([D.up_shared[a:a + m] for a, m in sl]).contiguous()
@@ -3722,10 +3723,10 @@ class LayerLaunch:
                 if D.b_index is not None and D.b_index.size(1) > 0 and d > 0:
                     sl = []
                     for r in recs:
-                        for t in range(int(r[8])):
-                            o = 9 + 7 * t
-                            if int(r[o]) == d and r[o + 4] > 0:
-                                sl.append((int(r[o + 3]), int(r[o + 4])))
+                        for t in range(int(r[I_NT])):
+                            o = I_TASK0 + T_INTS * t
+                            if int(r[o + T_DIM]) == d and r[o + T_BNE] > 0:
+                                sl.append((int(r[o + T_BE0]), int(r[o + T_BNE])))
                     if sl:
                         idx = torch.cat([D.b_index[:, a:a + m] for a, m in sl], 1).contiguous()
                         adj = Adjacency.from_index(idx, N, int(dims[d - 1].x.size(0)), build=False)

@@ -286,7 +286,7 @@ int cwn_gather_rows_f64(const double* src, int64_t n_src, int64_t F, const int64
  * The item table (device, int32[n_items][CWN_LAYER_ITEM_INTS]) is a property of the BATCH, built
  * once from the per-complex sizes the reference's collate keeps (`ptr`, `__slices__`,
  * data/complex.py:344-441): cwn_layer_items_build below.  Record layout (all offsets are into the batched
- * tensors):
+ * tensors; the field names and the rule that writes a record, here and for the backward's: csrc/cwn_items.h):
  *   [0] flags      bit 0: the item has a GEMM dimension g (an upper adjacency with coboundary features);
  *                  bits 8-9: its SET (informative; the kernel derives it from cwn_layer_plan.set_start)
  *                  -- sets are numbered over the dimensions in ascending order: a dimension with

@@ -166,6 +166,48 @@ def test_device_item_tables_pass_the_host_check_and_cover_every_cell_once(F, gro
                 assert rec[live, 5].sum() == n[2]
 
 
+@pytest.mark.parametrize('F', [64, 128])
+def test_device_item_tables_hold_the_records_of_the_host_tables(F):
+    """The contract of csrc/cwn_items_dev.hip, record for record: with one complex per item (group = 1 on the device; on the
+    host C / 128 < 1 complexes per item at these batch sizes) both builders cut the same ranges, and the caps do not enter a
+    record -- so the device table without its empty records and the host table of the same complexes hold the same records
+    per set, all 32 ints of the forward table and all 16 of the backward one, once both are sorted (the host orders heavy
+    items first, the device by complex).  The pool holds molecules whose rings are not lifted (no cells of dimension 2:
+    the second task of their edge items has no rows) and the batch of 13 leaves empty records behind every set's own."""
+    from cwn_amd.blockplan import BlockPlan
+    from cwn_amd.packed import PackedComplexes
+    from cwn_amd.static_batch import StaticBatch
+    from cwn_amd.synthetic import zinc_like_complexes
+    n_hi = 28 if F == 128 else 45
+    pool = zinc_like_complexes(212, seed=3, max_ring=6, n_lo=9, n_hi=n_hi) + zinc_like_complexes(8, seed=4, max_ring=4, n_lo=9, n_hi=n_hi)
+    p = PackedComplexes(pool, DEV, max_dim=2, with_csr=True)
+    B = 40
+    sb = StaticBatch(p, B, group=1)
+    has_up, has_b = [True, True, False], [False, True, True]
+    lex = lambda rec: rec[np.lexsort(rec.T[::-1])]
+    ringless = 0
+    for idx in _batches(len(pool), B, 5, sizes=[B, 13, B]):
+        sb.set_batch(idx)
+        sb.fill()
+        dev_f = sb.plan.items(F, has_up, has_b).items
+        dev_b = sb.plan.bwd_items(F, has_up, has_b).items
+        torch.cuda.synchronize()
+        dev_f, dev_b = dev_f.cpu().numpy(), dev_b.cpu().numpy()
+        host = BlockPlan.from_batch(p.collate(idx))
+        ringless += int((np.diff(np.asarray(host.cell_ptr[2])) == 0).sum())
+        host_f = host.items(F, has_up, has_b).items.cpu().numpy()
+        host_b = host.bwd_items(F, has_up, has_b).items.cpu().numpy()
+        assert dev_f.shape == (2 * B, 32) and dev_b.shape == (2 * B, 16) and host_f.shape[1] == 32 and host_b.shape[1] == 16
+        for s in range(2):
+            d, h = dev_f[s * B:(s + 1) * B], host_f[(host_f[:, 0] >> 8) == s]
+            d = d[d[:, 8] != 0]
+            assert len(d) == len(idx) and np.array_equal(lex(d), lex(h)), (F, len(idx), s, 'forward')
+            d, h = dev_b[s * B:(s + 1) * B], host_b[(host_b[:, 0] >> 8) == s]
+            d = d[d[:, 3] != 0]
+            assert len(d) == len(idx) and np.array_equal(lex(d), lex(h)), (F, len(idx), s, 'backward')
+    assert ringless > 0
+
+
 def _model(hidden=128, layers=2, seed=0):
     from cwn_amd.models import EmbedSparseCIN
     torch.manual_seed(seed)
