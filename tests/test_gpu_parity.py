@@ -1403,7 +1403,8 @@ def test_gemm_split_path_has_fp32_accuracy(M):
     """N = K = 128 launches run as six bf16 MFMAs per product on exactly-split operands: the
     error against float64 must be at the level of the fp32-MFMA kernel (a few 1e-7 of |x|.|w|;
     plain bf16 would be 4e-3), with bias, BatchNorm-eval affine, ReLU, a column slice of a wider
-    weight and several GEMMs in one launch."""
+    weight and several GEMMs in one launch.
+    (A tolerance cannot tell whether all six terms are there: tests/test_gpu_split_terms.py pins each term and plane.)"""
     from cwn_amd import ops
     g = torch.Generator().manual_seed(M)
     W2 = (torch.randn(128, 256, generator=g) / 16).to(DEV)          # [N, 2F]: two column halves
@@ -1438,7 +1439,8 @@ def test_gemm_split_packed_weight_is_bit_identical(M):
     instead of in every workgroup -- the same numbers in the same MFMA order, so the results are the
     fp32-weight launch's bit for bit (bias, BatchNorm-eval affine, ReLU, several GEMMs per launch); a packed
     weight in a launch that does not run on the split path is an argument error, and the Python layer
-    falls back to the fp32 weight there."""
+    falls back to the fp32 weight there.
+    (Packed = unpacked links two kernels to each other; tests/test_gpu_split_terms.py pins the packed planes to the integers.)"""
     import ctypes as C
     from cwn_amd import _ffi, ops
     g = torch.Generator().manual_seed(100 + M)
