@@ -117,19 +117,18 @@ def _norm_desc(z: Tensor, *, dy: Optional[Tensor] = None, out: Optional[Tensor] 
 
 
 class _Plan:
-    """Static description of one layer's dense networks: per dimension, `depth` update stages for
-    each of the branches (SparseCINConv: two, upper and boundary) and one combine stage over the K-concatenation of the
-    two.  `chains` (round 4, CINppConv): two to four branches per dimension; with `cb` the combine stage takes the third /
-    fourth branch as extra K-blocks (cwn_dense_stage_ex_f32; live BatchNorm mode only -- CombineNeedsStageKernel otherwise),
-    without it the Function returns every branch's activated output and the caller concatenates and combines them."""
+    """Static description of one layer's dense networks: `chains[dim][branch]`, `depth` update stages for each of the two
+    (SparseCINConv: upper, boundary) to four (CINppConv) branches of a dimension, and `cb[dim]`, one combine stage over the
+    K-concatenation of the branches -- the third / fourth as extra K-blocks (cwn_dense_stage_ex_f32; live BatchNorm mode
+    only, CombineNeedsStageKernel otherwise).  Without `cb` the Function returns every branch's activated output and the
+    caller concatenates and combines them."""
 
-    def __init__(self, up: Optional[List[List[Stage]]], bd: Optional[List[List[Stage]]], cb: Optional[List[Stage]],
-                 chains: Optional[List[List[List[Stage]]]] = None, out_drop: float = 0.0):
+    def __init__(self, chains: List[List[List[Stage]]], cb: Optional[List[Stage]], out_drop: float = 0.0):
         # out_drop: dropout probability of the layer's OUTPUT (OGBEmbedSparseCIN drops out after every conv layer,
         # mp/molec_models.py:298-300): applied by the activation launch of the combine stage, re-derived by the reduce launch of
         # its backward (ops: "dropout without a mask tensor"); plans with a combine stage only
         self.out_drop = float(out_drop) if cb is not None else 0.0
-        self.chains = chains if chains is not None else [[u, b] for u, b in zip(up, bd)]     # [dim][branch] -> stages
+        self.chains = chains
         self.cb = cb
         assert cb is None or all(2 <= len(c) <= 4 for c in self.chains)
         self.nd = len(self.chains)

@@ -319,6 +319,14 @@ def _mlp_stages(nn):
     return stages
 
 
+def _combine_folds(combine):
+    """[dim] -> `_fold_norm` of a combine network that is one stage, or None when some dimension's is another form."""
+    if any(cb is None or len(cb) != 1 for cb in combine):
+        return None
+    folds = [_fold_norm(cb[0][1], cb[0][0].out_features) for cb in combine]
+    return None if any(f is None for f in folds) else folds
+
+
 # ------------------------------------------------------------------------------------------------
 # test / toy layers
 # ------------------------------------------------------------------------------------------------
@@ -1183,14 +1191,39 @@ class SparseCINConv(torch.nn.Module):
         """The eps tensors a prepared launch reads in place (its marks follow their versions)."""
         return [t for d in range(n) for t in (self.mp_levels[d].eps1, self.mp_levels[d].eps2)]
 
+    @staticmethod
+    def _n_streams(plan) -> int:
+        """How many matrices of `outs` belong to a dimension with this entry of `plans`."""
+        return 2
+
+    def _update_nets(self, lvl, nb: int):
+        """The update networks of a level in the order of `outs`."""
+        return [lvl.update_up_nn, lvl.update_boundaries_nn]
+
+    def _update_chains(self, plans, outs, start: int):
+        """(active dimensions, branches per dimension, [dim][branch] -> update network, [dim] -> combine network) of the
+        dimensions from `start` on, each network as `_mlp_stages` reads it ([(Linear, norm), ...], or None for another
+        form), the branches in the order of `outs`.  None when a dimension has no fused streams or `outs` is not the same
+        number of matrices for every dimension."""
+        active = list(range(start, len(plans)))
+        if not active or any(plans[d] is None for d in active):
+            return None
+        nb = self._n_streams(plans[active[0]])
+        if any(self._n_streams(plans[d]) != nb for d in active) or len(outs) != nb * len(active):
+            return None
+        levels = [self.mp_levels[d] for d in active]
+        return (active, nb, [[_mlp_stages(net) for net in self._update_nets(lvl, nb)] for lvl in levels],
+                [_mlp_stages(lvl.combine_nn) for lvl in levels])
+
     def _dense_eval(self, plans, outs, start: int = 0) -> Optional[List[Tensor]]:
-        """The update / combine networks of ALL dimensions (mp/layers.py:193-199) as three grouped
-        MFMA launches -- [Linear+norm+ReLU] x2 for both branches, then combine with its torch.cat
-        folded into the K-concatenation -- with eval-mode BatchNorm folded into the epilogue.
-        Inference only (no autograd, running statistics); returns None when it does not apply and
-        the caller runs the torch modules instead."""
+        """Inference: the update / combine networks of ALL dimensions (mp/layers.py:193-199, :255-260) with eval-mode
+        BatchNorm and the ReLU folded into the epilogue -- in ONE launch where `_one_launch` has a kernel for them, else
+        as one grouped MFMA launch per update stage over every branch and dimension, then the combine: two branches as a
+        grouped launch with torch.cat folded into the K-concatenation, three or four as torch.cat + combine_nn.  No
+        autograd, running statistics; returns None when it does not apply and the caller runs the torch modules instead."""
+        from . import _ffi
         if torch.is_grad_enabled() or any(o.dtype != torch.float32 for o in outs):
-            return None                  # (float64: the torch modules)
+            return None                  # (float64: _dense_f64 / the torch modules)
         ent = _MLP_CACHE.get(self)
         if ent is not None:
             # the prepared launch of this layer's networks (ops.MlpLaunch): per call only the rows are looked at
@@ -1202,68 +1235,65 @@ class SparseCINConv(torch.nn.Module):
                     return res
             else:
                 del _MLP_CACHE[self]
-        active = list(range(start, len(plans)))
-        if not active or any(plans[d] is None for d in active) or len(outs) != 2 * len(active):
+        got = self._update_chains(plans, outs, start)
+        if got is None:
             return None
-        levels = [self.mp_levels[d] for d in active]
-        chains = []
-        for lvl in levels:
-            up, bd, cb = (_mlp_stages(lvl.update_up_nn), _mlp_stages(lvl.update_boundaries_nn),
-                          _mlp_stages(lvl.combine_nn))
-            if up is None or bd is None or cb is None or len(up) != len(bd) or len(cb) != 1:
-                return None
-            if any(lin.in_features > ops.GEMM_MAX_K for lin, _ in up + bd + cb):
-                return None
-            folds = []
-            for stages in (up, bd, cb):
-                fs = [_fold_norm(norm, lin.out_features) for lin, norm in stages]
-                if any(f is None for f in fs):
-                    return None
-                folds.append(fs)
-            chains.append((up, bd, cb, folds))
-        dev = outs[0].device
-        hs_up = [outs[2 * i] for i in range(len(levels))]
-        hs_bd = [outs[2 * i + 1] for i in range(len(levels))]
-        depth = len(chains[0][0])
-        if any(len(c[0]) != depth for c in chains):
+        active, nb, chains, combine = got
+        flat = [st for sts in chains for st in sts]                      # [dim][branch] flattened, as `outs`
+        if any(st is None for st in flat) or len({len(st) for st in flat}) != 1:
             return None
-        if FUSED_UPDATE_MLP and depth == 2 and not ops.GEMM_EXACT:
-            # all five Linear layers of every dimension in ONE launch (csrc/cwn_mlp.hip): the activations
-            # between them stay in LDS
-            mdims = [ops.MlpDim(x_up=hs_up[i], x_b=hs_bd[i],
-                                linears=[up[0][0], up[1][0], bd[0][0], bd[1][0], cb[0][0]],
-                                folds=[folds[0][0], folds[0][1], folds[1][0], folds[1][1], folds[2][0]])
-                     for i, (up, bd, cb, folds) in enumerate(chains)]
-            if ops.update_mlp_applies(mdims):
-                sources, norms = [], []
-                for up, bd, cb, _ in chains:
-                    for lin, norm in up + bd + cb:
-                        sources += [lin.weight, lin.bias]
-                        if isinstance(norm, BN):
-                            norms.append(norm)
-                            sources += [norm.weight, norm.bias, norm.running_mean, norm.running_var, norm.num_batches_tracked]
-                launch = ops.MlpLaunch(mdims, sources)
-                _MLP_CACHE[self] = (launch, (start, len(plans), len(outs)), norms)
-                res = launch.run(hs_up, hs_bd)
-                if res is not None:
-                    return res
-                return ops.update_mlp(mdims)
-        for st in range(depth):
-            gemms = []
-            for i, (up, bd, cb, folds) in enumerate(chains):
-                for hs, stages, fs in ((hs_up, up, folds[0]), (hs_bd, bd, folds[1])):
-                    lin = stages[st][0]
-                    gemms.append(ops.Gemm(X=hs[i], W=lin.weight, bias=lin.bias, relu=True,
-                                          out_scale=fs[st][0], out_shift=fs[st][1],
-                                          w_packed=ops.pack_gemm_weight(lin.weight)))
-            res = ops.run_gemm(gemms, dev)
-            hs_up, hs_bd = res[0::2], res[1::2]
-        gemms = []
-        for i, (up, bd, cb, folds) in enumerate(chains):
-            lin = cb[0][0]
-            gemms.append(ops.Gemm(X=hs_up[i], X2=hs_bd[i], W=lin.weight, bias=lin.bias, relu=True,
-                                  out_scale=folds[2][0][0], out_shift=folds[2][0][1]))
-        return ops.run_gemm(gemms, dev)
+        # (two branches: the combine is a launch of this path, so its network has to be one foldable stage within the
+        #  GEMM's K; three or four: it is needed in that form by the one-launch kernel only)
+        if nb == 2 and any(cb is None or len(cb) != 1 for cb in combine):
+            return None
+        if any(lin.in_features > ops.GEMM_MAX_K for st in flat + (combine if nb == 2 else []) for lin, _ in st):
+            return None
+        folds = [[_fold_norm(norm, lin.out_features) for lin, norm in st] for st in flat]
+        if any(f is None for fs in folds for f in fs):
+            return None
+        depth = len(flat[0])
+        fused = FUSED_UPDATE_MLP and not ops.GEMM_EXACT and depth == 2 and nb < 4
+        cfolds = _combine_folds(combine) if nb == 2 or fused else None
+        if nb == 2 and cfolds is None:
+            return None
+        if fused and cfolds is not None:
+            # every Linear layer of every dimension in ONE launch: the activations between them stay in LDS.  Per
+            # dimension: its matrices of `outs`, the stages (branch by branch, then the combine) and their folds
+            dims = [(list(outs[nb * k: nb * (k + 1)]), [s for st in flat[nb * k: nb * (k + 1)] for s in st] + combine[k],
+                     [f for fs in folds[nb * k: nb * (k + 1)] for f in fs] + [cfolds[k]]) for k in range(len(active))]
+            res = self._one_launch(dims, (start, len(plans), len(outs)))
+            if res is not None:
+                return res
+        hs, dev = list(outs), outs[0].device
+        for s in range(depth):
+            gemms = [ops.Gemm(X=h, W=st[s][0].weight, bias=st[s][0].bias, relu=True, out_scale=fs[s][0], out_shift=fs[s][1],
+                              w_packed=ops.pack_gemm_weight(st[s][0].weight)) for h, st, fs in zip(hs, flat, folds)]
+            hs = []
+            for lo in range(0, len(gemms), _ffi.MAX_DESCS):
+                hs += ops.run_gemm(gemms[lo: lo + _ffi.MAX_DESCS], dev)
+        if nb == 2:
+            return ops.run_gemm([ops.Gemm(X=hs[2 * k], X2=hs[2 * k + 1], W=cb[0][0].weight, bias=cb[0][0].bias, relu=True,
+                                          out_scale=cf[0], out_shift=cf[1])
+                                 for k, (cb, cf) in enumerate(zip(combine, cfolds))], dev)
+        return [self.mp_levels[d].combine_nn(torch.cat(hs[nb * k: nb * (k + 1)], dim=-1)) for k, d in enumerate(active)]
+
+    def _one_launch(self, dims, shape) -> Optional[List[Tensor]]:
+        """Hook of `_dense_eval`: two-stage update networks + the combine of every dimension in one launch (here
+        csrc/cwn_mlp.hip: five Linear layers per dimension, prepared once per layer in _MLP_CACHE), or None."""
+        mdims = [ops.MlpDim(x_up=xs[0], x_b=xs[1], linears=[lin for lin, _ in stages], folds=fs) for xs, stages, fs in dims]
+        if not ops.update_mlp_applies(mdims):
+            return None
+        sources, norms = [], []
+        for _, stages, _ in dims:
+            for lin, norm in stages:
+                sources += [lin.weight, lin.bias]
+                if isinstance(norm, BN):
+                    norms.append(norm)
+                    sources += [norm.weight, norm.bias, norm.running_mean, norm.running_var, norm.num_batches_tracked]
+        launch = ops.MlpLaunch(mdims, sources)
+        _MLP_CACHE[self] = (launch, shape, norms)
+        res = launch.run([D.x_up for D in mdims], [D.x_b for D in mdims])
+        return res if res is not None else ops.update_mlp(mdims)
 
     def _f64_chain(self, lvl):
         """(weights, biases, folds, activation) of one dimension's three networks in the order of ops.ChainDim, or None when
@@ -1324,42 +1354,39 @@ class SparseCINConv(torch.nn.Module):
         Returns None when it does not apply (LayerNorm, custom networks, fewer than two cells in
         a dimension) and the caller runs the torch modules instead."""
         from . import dense_train as DT
-        if not torch.is_grad_enabled() or not FUSED_DENSE_TRAINING or any(o.dtype != torch.float32 for o in outs):
+        got = self._train_chains(plans, outs, start)
+        if got is None or any(cb is None or len(cb) != 1 for cb in got[3]):
             return None
-        active = list(range(start, len(plans)))
-        if not active or any(plans[d] is None for d in active) or len(outs) != 2 * len(active):
-            return None
-        if any(o.size(0) < 2 for o in outs):
-            return None      # BatchNorm1d(train) needs more than one row; let torch raise as the reference does
-        ups, bds, cbs = [], [], []
-        for d in active:
-            lvl = self.mp_levels[d]
-            up, bd, cb = (_mlp_stages(lvl.update_up_nn), _mlp_stages(lvl.update_boundaries_nn),
-                          _mlp_stages(lvl.combine_nn))
-            if up is None or bd is None or cb is None or len(up) != len(bd) or len(cb) != 1:
-                return None
-            chains = [[DT.Stage(lin, norm) for lin, norm in st] for st in (up, bd, cb)]
-            if not all(DT.supported(c) for c in chains):
-                return None
-            if any(isinstance(s.norm, BN) and not s.norm.training for c in chains for s in c):
-                return None
-            ups.append(chains[0])
-            bds.append(chains[1])
-            cbs.append(chains[2][0])
-        if len({len(u) for u in ups}) != 1:
+        cbs = [DT.Stage(*cb[0]) for cb in got[3]]
+        if not DT.supported(cbs):
             return None
         p = self._out_drop
         self._out_dropped = p > 0.0              # (the combine stage's activation launch applies it: dense_train._Plan.out_drop)
-        return DT.dense_train(DT._Plan(ups, bds, cbs, out_drop=p), outs)
+        return DT.dense_train(DT._Plan(got[2], cbs, p), outs)
+
+    def _train_chains(self, plans, outs, start: int):
+        """What `_update_chains` returns, with the update networks as dense_train.Stage lists, when the training launches
+        serve them: autograd recording, float32, at least two rows everywhere, equally deep Linear -> BatchNorm(train) /
+        Identity -> ReLU networks.  None otherwise."""
+        from . import dense_train as DT
+        if (not torch.is_grad_enabled() or not FUSED_DENSE_TRAINING or any(o.dtype != torch.float32 for o in outs)
+                or any(o.size(0) < 2 for o in outs)):
+            return None      # (one row: BatchNorm1d(train) needs more; let torch raise as the reference does)
+        got = self._update_chains(plans, outs, start)
+        if got is None:
+            return None
+        active, nb, raw, combine = got
+        if any(st is None for sts in raw for st in sts) or len({len(st) for sts in raw for st in sts}) != 1:
+            return None
+        chains = [[[DT.Stage(lin, norm) for lin, norm in st] for st in sts] for sts in raw]
+        if not all(DT.supported(c) for cs in chains for c in cs):       # (refuses a BatchNorm in eval mode too)
+            return None
+        return active, nb, chains, combine
 
     def _ln_chains(self, plans, outs, start: int):
-        """([dim][branch] -> stages, [dim] -> combine stages) of the active dimensions, or None."""
-        active = list(range(start, len(plans)))
-        if not active or any(plans[d] is None for d in active) or len(outs) != 2 * len(active):
-            return None
-        levels = [self.mp_levels[d] for d in active]
-        return ([[_mlp_stages(lvl.update_up_nn), _mlp_stages(lvl.update_boundaries_nn)] for lvl in levels],
-                [_mlp_stages(lvl.combine_nn) for lvl in levels])
+        """([dim][branch] -> stages, [dim] -> combine stages) of the active dimensions as `_mlp_stages` reads them, or None."""
+        got = self._update_chains(plans, outs, start)
+        return None if got is None else got[2:]
 
     def _dense_ln(self, plans, outs, start: int = 0) -> Optional[List[Tensor]]:
         """The same networks built with graph_norm='ln', in inference and in training: one grouped GEMM and one LayerNorm +
@@ -1387,6 +1414,7 @@ class SparseCINConv(torch.nn.Module):
         return [x if dim < start or x is None else ops.dropout(x, p, True) for dim, x in enumerate(out)]
 
     def forward(self, *cochain_params: CochainMessagePassingParams, start_to_process=0, out_dropout: float = 0.0):
+        """mp/layers.py:333-342 (CINppConv: :418-427)."""
         assert len(cochain_params) <= self.max_dim + 1
         n = len(cochain_params)
         self.__dict__['_out_drop'], self.__dict__['_out_dropped'] = (float(out_dropout) if self.training else 0.0), False
@@ -1410,8 +1438,9 @@ class SparseCINConv(torch.nn.Module):
             elif plans[dim] is None:
                 out.append(self.mp_levels[dim].forward_unfused(cochain_params[dim]))
             else:
-                out.append(self.mp_levels[dim].finish(outs[k], outs[k + 1]))
-                k += 2
+                m = self._n_streams(plans[dim])
+                out.append(self.mp_levels[dim].finish(*outs[k:k + m]))
+                k += m
         return self._finish_dropout(out, start_to_process)
 
 
@@ -1637,99 +1666,30 @@ class CINppConv(SparseCINConv):
     def _n_streams(plan) -> int:
         return 3 if isinstance(plan, str) else len(plan)       # ('blocked': the launch's three outputs)
 
-    def _update_chains(self, plans, outs, start: int):
-        """(active dimensions, streams per dimension, [dim][stream] -> [(Linear, norm), ...]) or None."""
-        active = list(range(start, len(plans)))
-        if not active or any(plans[d] is None for d in active):
-            return None
-        nb = self._n_streams(plans[active[0]])
-        if any(self._n_streams(plans[d]) != nb for d in active) or len(outs) != nb * len(active):
-            return None
-        chains = []
-        for d in active:
-            lvl = self.mp_levels[d]
-            nets = [lvl.update_up_nn, lvl.update_down_nn, lvl.update_boundaries_nn]
-            if nb == 4:
-                nets.append(lvl.update_coboundaries_nn)
-            sts = [_mlp_stages(net) for net in nets]
-            if any(st is None for st in sts):
-                return None
-            chains.append(sts)
-        if len({len(st) for sts in chains for st in sts}) != 1:
-            return None
-        return active, nb, chains
+    def _update_nets(self, lvl, nb: int):
+        nets = [lvl.update_up_nn, lvl.update_down_nn, lvl.update_boundaries_nn]
+        return nets + [lvl.update_coboundaries_nn] if nb == 4 else nets
 
-    def _ln_chains(self, plans, outs, start: int):
-        got = self._update_chains(plans, outs, start)
-        if got is None:
-            return None
-        return got[2], [_mlp_stages(self.mp_levels[d].combine_nn) for d in got[0]]
-
-    def _dense_eval(self, plans, outs, start: int = 0) -> Optional[List[Tensor]]:
-        """Inference: the update networks of every stream and dimension as grouped MFMA launches, one per stage, with
-        eval-mode BatchNorm and the ReLU folded into the epilogue (SparseCINConv._dense_eval's form); torch.cat + combine_nn
-        as torch modules."""
-        from . import _ffi
-        if torch.is_grad_enabled() or any(o.dtype != torch.float32 for o in outs):
-            return None
-        got = self._update_chains(plans, outs, start)
-        if got is None:
-            return None
-        active, nb, chains = got
-        flat = [st for sts in chains for st in sts]                      # [dim][stream] flattened, as `outs`
-        folds = [[_fold_norm(norm, lin.out_features) for lin, norm in st] for st in flat]
-        if any(f is None for fs in folds for f in fs) or any(lin.in_features > ops.GEMM_MAX_K for st in flat for lin, _ in st):
-            return None
-        if nb == 3 and FUSED_UPDATE_MLP and not ops.GEMM_EXACT and all(len(st) == 2 for st in flat):
-            # three update networks + the 3F-wide combine of every dimension in ONE launch (csrc/cwn_mlp3.hip, round 6): the
-            # activations between the seven Linear layers stay in LDS, the combine is accumulated branch by branch
-            mdims = []
-            for k, d in enumerate(active):
-                cb = _mlp_stages(self.mp_levels[d].combine_nn)
-                cfold = None if cb is None or len(cb) != 1 else _fold_norm(cb[0][1], cb[0][0].out_features)
-                if cfold is None:
-                    mdims = None
-                    break
-                sts, fs = flat[nb * k: nb * (k + 1)], folds[nb * k: nb * (k + 1)]
-                mdims.append(ops.Mlp3Dim(xs=list(outs[nb * k: nb * (k + 1)]),
-                                         linears=[st[j][0] for st in sts for j in range(2)] + [cb[0][0]],
-                                         folds=[f[j] for f in fs for j in range(2)] + [cfold]))
-            if mdims and ops.update_mlp3_applies(mdims):
-                return ops.update_mlp3(mdims)
-        hs, dev = list(outs), outs[0].device
-        for s in range(len(flat[0])):
-            gemms = [ops.Gemm(X=h, W=st[s][0].weight, bias=st[s][0].bias, relu=True, out_scale=fs[s][0], out_shift=fs[s][1],
-                              w_packed=ops.pack_gemm_weight(st[s][0].weight)) for h, st, fs in zip(hs, flat, folds)]
-            hs = []
-            for lo in range(0, len(gemms), _ffi.MAX_DESCS):
-                hs += ops.run_gemm(gemms[lo: lo + _ffi.MAX_DESCS], dev)
-        return [self.mp_levels[d].combine_nn(torch.cat(hs[nb * k: nb * (k + 1)], dim=-1)) for k, d in enumerate(active)]
+    def _one_launch(self, dims, shape) -> Optional[List[Tensor]]:
+        """Three update networks + the 3F-wide combine of every dimension in ONE launch (csrc/cwn_mlp3.hip, round 6): the
+        activations between the seven Linear layers stay in LDS, the combine is accumulated branch by branch."""
+        mdims = [ops.Mlp3Dim(xs=xs, linears=[lin for lin, _ in stages], folds=fs) for xs, stages, fs in dims]
+        return ops.update_mlp3(mdims) if ops.update_mlp3_applies(mdims) else None
 
     def _dense_train(self, plans, outs, start: int = 0) -> Optional[List[Tensor]]:
         """Training mode: the update networks of EVERY stream and dimension (three or four chains of Linear ->
-        BatchNorm(train) -> ReLU stages per dimension) through dense_train's stage launches, forward and backward -- a plan
-        without combine stages, at most _ffi.MAX_DESCS chains per autograd node -- then torch.cat + combine_nn as torch
-        modules (mp/layers.py:255-260).  None when it does not apply (LayerNorm, custom networks, fewer than two cells)."""
+        BatchNorm(train) -> ReLU stages per dimension) through dense_train's stage launches, forward and backward -- at most
+        _ffi.MAX_DESCS chains per autograd node -- with the combine stage in the same node, or without combine stages and then
+        torch.cat + combine_nn as torch modules (mp/layers.py:255-260).  None when it does not apply (LayerNorm, custom
+        networks, fewer than two cells)."""
         from . import _ffi, dense_train as DT
-        if (not torch.is_grad_enabled() or not FUSED_DENSE_TRAINING or any(o.size(0) < 2 for o in outs)
-                or any(o.dtype != torch.float32 for o in outs)):
-            return None
-        got = self._update_chains(plans, outs, start)
+        got = self._train_chains(plans, outs, start)
         if got is None:
             return None
-        active, nb, raw = got
-        chains = []
-        for sts in raw:
-            cs = [[DT.Stage(lin, norm) for lin, norm in st] for st in sts]
-            if not all(DT.supported(c) for c in cs) or any(isinstance(s.norm, BN) and not s.norm.training for c in cs for s in c):
-                return None
-            chains.append(cs)
+        active, nb, chains, combine = got
         per = max(1, _ffi.MAX_DESCS // nb)                    # dimensions per autograd node
         # the combine stage in the same node (its third / fourth branch as extra K-blocks of cwn_dense_stage_ex_f32) ...
-        cbs = []
-        for d in active:
-            cb = _mlp_stages(self.mp_levels[d].combine_nn)
-            cbs.append(DT.Stage(*cb[0]) if cb is not None and len(cb) == 1 else None)
+        cbs = [DT.Stage(*cb[0]) if cb is not None and len(cb) == 1 else None for cb in combine]
         full = (FUSED_CINPP_COMBINE and ops.STAGE_KERNEL and all(c is not None and DT.supported([c], max_k=4 * 128) and c.is_bn and c.norm.training
                                                                 for c in cbs))
         if ops.STAGE_KERNEL:
@@ -1747,8 +1707,7 @@ class CINppConv(SparseCINConv):
             try:
                 for lo in range(0, len(active), per):
                     grp = chains[lo: lo + per]
-                    res += DT.dense_train(DT._Plan(None, None, cbs[lo: lo + per], chains=grp, out_drop=self._out_drop),
-                                          outs[nb * lo: nb * (lo + len(grp))])
+                    res += DT.dense_train(DT._Plan(grp, cbs[lo: lo + per], self._out_drop), outs[nb * lo: nb * (lo + len(grp))])
                 self._out_dropped = self._out_drop > 0.0
                 return res
             except DT.CombineNeedsStageKernel:
@@ -1759,34 +1718,8 @@ class CINppConv(SparseCINConv):
         hs: List[Tensor] = []
         for lo in range(0, len(active), per):
             grp = chains[lo: lo + per]
-            hs += DT.dense_train(DT._Plan(None, None, None, chains=grp), outs[nb * lo: nb * (lo + len(grp))])
+            hs += DT.dense_train(DT._Plan(grp, None), outs[nb * lo: nb * (lo + len(grp))])
         return [self.mp_levels[d].combine_nn(torch.cat(hs[nb * k: nb * (k + 1)], dim=-1)) for k, d in enumerate(active)]
-
-    def forward(self, *cochain_params: CochainMessagePassingParams, start_to_process=0, out_dropout: float = 0.0):
-        """mp/layers.py:418-427."""
-        assert len(cochain_params) <= self.max_dim + 1
-        self.__dict__['_out_drop'], self.__dict__['_out_dropped'] = (float(out_dropout) if self.training else 0.0), False
-        plans, outs = self.propagate_all(*cochain_params, start_to_process=start_to_process)
-        dense = self._dense_eval(plans, outs, start_to_process)
-        if dense is None:
-            dense = self._dense_train(plans, outs, start_to_process)
-        if dense is None:
-            dense = self._dense_ln(plans, outs, start_to_process)
-        if dense is not None:
-            it = iter(dense)
-            return self._finish_dropout([c.x if dim < start_to_process else next(it) for dim, c in enumerate(cochain_params)],
-                                        start_to_process)
-        out, k = [], 0
-        for dim, cochain in enumerate(cochain_params):
-            if dim < start_to_process:
-                out.append(cochain.x)
-            elif plans[dim] is None:
-                out.append(self.mp_levels[dim].forward_unfused(cochain))
-            else:
-                m = self._n_streams(plans[dim])
-                out.append(self.mp_levels[dim].finish(*outs[k:k + m]))
-                k += m
-        return self._finish_dropout(out, start_to_process)
 
 
 # ------------------------------------------------------------------------------------------------

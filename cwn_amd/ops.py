@@ -2971,6 +2971,33 @@ def _mlp_first_weight(weight: Tensor, F: int) -> Tensor:
     return pad
 
 
+def _mlp_epilogues(a, D) -> list:
+    """The bias / scale / shift pointers of a cwn_mlp_dim / cwn_mlp3_dim record `a`, one per Linear of D; returns the
+    tensors behind them (to be kept alive with the record)."""
+    keep = []
+    for s_, (lin, (sc, sh)) in enumerate(zip(D.linears, D.folds)):
+        b = None if lin.bias is None else _f32c(lin.bias, 'bias')
+        a.bias[s_], a.scale[s_], a.shift[s_] = _ffi.ptr(b), _ffi.ptr(sc), _ffi.ptr(sh)
+        keep += [b, sc, sh]
+    return keep
+
+
+def _mlp_dim_static(a, D: MlpDim, F: int) -> list:
+    """The half of a cwn_mlp_dim record that does not depend on the rows of a call: in_width, ldy, the packed weights (the
+    first stages' padded to [F, F]) and the epilogues; returns the tensors behind the pointers."""
+    w_in = int(D.x_up.size(1))
+    a.in_width, a.ldy = (w_in if w_in < F else 0), F
+    keep, k = [], 0
+    for j, l in enumerate(D.linears):
+        w = _mlp_first_weight(l.weight, F) if j in (0, 2) else l.weight
+        keep.append(w)
+        for pk in pack_mlp_weight(w):               # (the combine weight: its two F-column blocks)
+            a.w_packed[k] = pk.data_ptr()
+            keep.append(pk)
+            k += 1
+    return keep + _mlp_epilogues(a, D)
+
+
 def update_mlp(dims: Sequence[MlpDim]) -> List[Tensor]:
     """mp/layers.py:193-199 for every dimension in ONE launch (csrc/cwn_mlp.hip); inference only."""
     dev = dims[0].x_up.device
@@ -2986,20 +3013,8 @@ def update_mlp(dims: Sequence[MlpDim]) -> List[Tensor]:
         a.x_up, a.x_b, a.y, a.M = xu.data_ptr(), xb.data_ptr(), y.data_ptr(), xu.size(0)
         a.ldx_up = xu.stride(0) if xu.size(0) > 1 else w_in
         a.ldx_b = xb.stride(0) if xb.size(0) > 1 else w_in
-        a.ldy = F
-        a.in_width = w_in if w_in < F else 0
         a.m_dev = _ffi.dyn(xu.size(0))
-        packed = []
-        for k_, l in enumerate(D.linears[:4]):
-            packed += list(pack_mlp_weight(_mlp_first_weight(l.weight, F) if k_ in (0, 2) else l.weight))
-        packed += list(pack_mlp_weight(D.linears[4].weight))
-        for k, pk in enumerate(packed):
-            a.w_packed[k] = pk.data_ptr()
-        for s_, (lin, (sc, sh)) in enumerate(zip(D.linears, D.folds)):
-            b = None if lin.bias is None else _f32c(lin.bias, 'bias')
-            a.bias[s_], a.scale[s_], a.shift[s_] = _ffi.ptr(b), _ffi.ptr(sc), _ffi.ptr(sh)
-            keep += [b, sc, sh]
-        keep += packed + [xu, xb]
+        keep += _mlp_dim_static(a, D, F) + [xu, xb]
     _ffi.check(_ffi.lib().cwn_update_mlp_f32(arr, len(dims), F, _ffi.stream_ptr(dev)), 'cwn_update_mlp_f32')
     return outs
 
@@ -3056,10 +3071,7 @@ def update_mlp3(dims: Sequence[Mlp3Dim]) -> List[Tensor]:
             a.w_packed[3 * k] = pack_mlp_weight(D.linears[2 * k].weight)[0].data_ptr()
             a.w_packed[3 * k + 1] = pack_mlp_weight(D.linears[2 * k + 1].weight)[0].data_ptr()
             a.w_packed[3 * k + 2] = wc[k].data_ptr()
-        for s_, (lin, (sc, sh)) in enumerate(zip(D.linears, D.folds)):
-            b = None if lin.bias is None else _f32c(lin.bias, 'bias')
-            a.bias[s_], a.scale[s_], a.shift[s_] = _ffi.ptr(b), _ffi.ptr(sc), _ffi.ptr(sh)
-            keep += [b, sc, sh]
+        keep += _mlp_epilogues(a, D)
     _ffi.check(_ffi.lib().cwn_update_mlp3_f32(arr, n, F, _ffi.stream_ptr(dev)), 'cwn_update_mlp3_f32')
     return outs
 
@@ -3079,22 +3091,7 @@ class MlpLaunch:
         self.keep = []
         self.w_in = [int(D.x_up.size(1)) for D in dims]            # input columns per dimension (< F: cwn_mlp_dim.in_width)
         for i, D in enumerate(dims):
-            a = self.arr[i]
-            a.in_width = self.w_in[i] if self.w_in[i] < F else 0
-            packed = []
-            for k_, l in enumerate(D.linears[:4]):
-                first = _mlp_first_weight(l.weight, F) if k_ in (0, 2) else l.weight
-                self.keep.append(first)
-                packed += list(pack_mlp_weight(first))
-            packed += list(pack_mlp_weight(D.linears[4].weight))
-            for k, pk in enumerate(packed):
-                a.w_packed[k] = pk.data_ptr()
-            for s_, (lin, (sc, sh)) in enumerate(zip(D.linears, D.folds)):
-                b = None if lin.bias is None else _f32c(lin.bias, 'bias')
-                a.bias[s_], a.scale[s_], a.shift[s_] = _ffi.ptr(b), _ffi.ptr(sc), _ffi.ptr(sh)
-                self.keep += [b, sc, sh]
-            a.ldy = F
-            self.keep += packed
+            self.keep += _mlp_dim_static(self.arr[i], D, F)
         self.sources = [t for t in sources if t is not None]
         self.marks = [(t.data_ptr(), _ffi.tver(t)) for t in self.sources]
         self.epochs = (STATE_EPOCH, STRUCT_EPOCH)
