@@ -28,7 +28,7 @@ EXPORTS = ('cwn_abi_version', 'cwn_error_string', 'cwn_target_arch', 'cwn_csr_wo
            'cwn_linear_many_f64', 'cwn_update_chain_f64',
            'cwn_aggregate_act_f32', 'cwn_aggregate_act_f64',
            'cwn_embed_pool_f32', 'cwn_embed_pool_f64', 'cwn_agnostic_head_f32', 'cwn_agnostic_head_f64',
-           'cwn_gin_layer_f32',
+           'cwn_gin_layer_f32', 'cwn_gine_layer_f32',
            'cwn_gemm_tn_f32', 'cwn_gemm_tn_workspace_bytes', 'cwn_gemm_tn_would_split', 'cwn_adam_f32', 'cwn_adam_dev_f32', 'cwn_loss_f32', 'cwn_loss_cols_f32', 'cwn_embedding_fwd_f32', 'cwn_embedding_bwd_f32', 'cwn_embed_front_f32', 'cwn_head_f32', 'cwn_head_bwd_f32', 'cwn_head_pool_floats', 'cwn_lift_create', 'cwn_lift_size', 'cwn_lift_copy', 'cwn_lift_destroy',
            'cwn_lift_many', 'cwn_lift_many_count', 'cwn_lift_many_lengths', 'cwn_lift_many_copy', 'cwn_lift_many_destroy',
            # the evaluation pass (csrc/cwn_metrics.hip)
@@ -353,6 +353,11 @@ class GinDesc(C.Structure):
                 ('ldout', C.c_int64), ('w', C.c_int32), ('H', C.c_int32), ('act', C.c_int32), ('act_post', C.c_int32)]
 
 
+class GineDesc(C.Structure):
+    """cwn_gine_desc (include/cwn_hip.h): one GINEConv layer in inference -- a GinDesc and the edge operand."""
+    _fields_ = [('g', GinDesc), ('e', C.c_void_p), ('eidx', C.c_void_p), ('lde', C.c_int64), ('n_e', C.c_int64)]
+
+
 # the float64 dense path (csrc/cwn_dense_f64.hip) = CWN_LINEAR_F64_* / CWN_CHAIN_F64_* / CWN_DENSE_F64_TILE_ROWS
 LINEAR_F64_MAX_DESCS, LINEAR_F64_MAX_WIDTH, CHAIN_F64_MAX_DIMS, CHAIN_F64_MAX_WIDTH, DENSE_F64_TILE_ROWS = 16, 128, 4, 64, 16
 
@@ -557,6 +562,8 @@ def lib():
         fn.argtypes = [C.POINTER(AgnosticHeadDesc), C.c_void_p]
     L.cwn_gin_layer_f32.restype = C.c_int
     L.cwn_gin_layer_f32.argtypes = [C.POINTER(GinDesc), C.c_void_p]
+    L.cwn_gine_layer_f32.restype = C.c_int
+    L.cwn_gine_layer_f32.argtypes = [C.POINTER(GineDesc), C.c_void_p]
     L.cwn_target_head_bwd_workspace_bytes.restype = C.c_size_t
     L.cwn_target_head_bwd_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32]
     L.cwn_adam_dev_f32.restype = C.c_int
@@ -842,6 +849,11 @@ def gin_layer(desc: 'GinDesc', device) -> None:
     """One GINConv layer in one launch (csrc/cwn_gin.hip).  The row count is a host count: the descriptor has no m_dev, so
     nothing is looked up in DYN_ROWS (the callers decline under `dynamic_rows`)."""
     check(lib().cwn_gin_layer_f32(C.byref(desc), stream_ptr(device)), 'cwn_gin_layer_f32')
+
+
+def gine_layer(desc: 'GineDesc', device) -> None:
+    """One GINEConv layer in one launch (csrc/cwn_gine.hip).  Host row counts, no m_dev, as `gin_layer`."""
+    check(lib().cwn_gine_layer_f32(C.byref(desc), stream_ptr(device)), 'cwn_gine_layer_f32')
 
 
 def target_head_served(H: int, K: int) -> bool:

@@ -1867,6 +1867,24 @@ FUSED_GIN_DEFAULT = True
 FUSED_GIN = {'0': False, '1': True}.get(os.environ.get('CWN_FUSED_GIN'), FUSED_GIN_DEFAULT)
 
 
+def _gin_fused_stages(nn, eps, x):
+    """([(W, b, scale, shift)] * 2, activation name) of a GINConv's / GINEConv's network when its layer can be ONE launch
+    (the route's own switch aside), else None: autograd off, x float32 on the GPU, no static batch, `nn` a stock Sequential
+    of two (Linear, norm, activation) groups whose norms fold, widths within 128."""
+    if torch.is_grad_enabled() or not isinstance(x, Tensor) or not x.is_cuda or x.dtype != torch.float32 or _ffi_dyn():
+        return None
+    got = _f64_stages(nn, 2)
+    if got is None or not (eps.is_cuda and eps.dtype == torch.float32):
+        return None
+    stages = []
+    for lin, norm in got[0]:
+        fold = _fold_norm(norm, lin.out_features)
+        if fold is None:
+            return None
+        stages.append((lin.weight, lin.bias, fold[0], fold[1]))
+    return (stages, got[1]) if ops.gin_layer_applies(x, stages) else None
+
+
 class GINConv(torch.nn.Module):
     """torch_geometric.nn.GINConv (the layer of mp/graph_models.py and of RingGIN, mp/ring_exp_models.py:76-130) with its
     constructor and state: out_i = nn((1 + eps) * x_i + sum_{j -> i} x_j), `edge_index[0]` the source and `[1]` the target;
@@ -1900,19 +1918,7 @@ class GINConv(torch.nn.Module):
 
     def fused_stages(self, x):
         """([(W, b, scale, shift)] * 2, activation name) when the whole layer is ONE cwn_gin_layer_f32 launch, else None."""
-        if (not FUSED_GIN or torch.is_grad_enabled() or not isinstance(x, Tensor) or not x.is_cuda or x.dtype != torch.float32
-                or _ffi_dyn()):
-            return None
-        got = _f64_stages(self.nn, 2)
-        if got is None or not (self.eps.is_cuda and self.eps.dtype == torch.float32):
-            return None
-        stages = []
-        for lin, norm in got[0]:
-            fold = _fold_norm(norm, lin.out_features)
-            if fold is None:
-                return None
-            stages.append((lin.weight, lin.bias, fold[0], fold[1]))
-        return (stages, got[1]) if ops.gin_layer_applies(x, stages) else None
+        return _gin_fused_stages(self.nn, self.eps, x) if FUSED_GIN else None
 
     def forward(self, x: Tensor, edge_index: Optional[Tensor], out: Optional[Tensor] = None, act_post: str = 'id') -> Tensor:
         n = x.size(0)
@@ -1933,6 +1939,98 @@ class GINConv(torch.nn.Module):
             s = (1 + self.eps.to(x.dtype)) * x
             if edge_index is not None and edge_index.numel():
                 s = torch.zeros_like(x).index_add_(0, edge_index[1], x[edge_index[0]]) + s
+        y = self.nn(s)
+        return y if act_post == 'id' else ACTIVATIONS[act_post][1](y)
+
+    def __repr__(self):
+        return f'{self.__class__.__name__}(nn={self.nn})'
+
+
+# A GINEConv in inference as ONE cwn_gine_layer_f32 launch (csrc/cwn_gine.hip: the GIN kernel with relu(x_j + e_ji) as its
+# message) instead of one aggregation launch (CWN_MSG_RELU_A_PLUS_B) and the torch modules of its network.
+# CWN_FUSED_GINE=1 / =0 turns the route on / off; without it FUSED_GINE_DEFAULT decides, by the project's rule: on only
+# where the route has measured faster than the generic route of the same commit by more than the larger run-to-run spread
+# of the two, both routes alternating in one process (tools/bench_gine.py, profiles/gine_layer.md, 128 ZINC-like molecules
+# per batch, rounds of 400 forwards: one layer at (64, 64) 59.5 against 112.4 us, spread 5.8 us, and at (128, 128) 59.3 against
+# 111.3 us, spread 0.9 us, 1 kernel against 9; EmbedGIN with hidden 128 and 4 layers 326.9 against 547.5 us, spread 20.0 us, 7
+# kernels against 39; rounds of 50 forwards on another machine: 62.0 against 129.0, 62.4 against 128.8, 339.0 against 589.3 us).
+FUSED_GINE_DEFAULT = True
+FUSED_GINE = {'0': False, '1': True}.get(os.environ.get('CWN_FUSED_GINE'), FUSED_GINE_DEFAULT)
+
+
+def _edge_rows(edge_attr) -> Tensor:
+    """One row per entry from an edge attribute that is lazy (IndexedRows) or dense, on either device."""
+    if isinstance(edge_attr, IndexedRows):
+        return edge_attr.tensor() if edge_attr.src.is_cuda else edge_attr.src[edge_attr.index]
+    return edge_attr
+
+
+class GINEConv(torch.nn.Module):
+    """torch_geometric.nn.GINEConv as version 1.6.3 defines it (the layer of EmbedGIN, mp/molec_models.py:506-606) with its
+    constructor and state: out_i = nn((1 + eps) * x_i + sum_{j -> i} relu(x_j + e_ji)), `edge_index[0]` the source and `[1]`
+    the target; `eps` a [1] tensor -- a Parameter with train_eps, a registered buffer otherwise, in the state_dict either way.
+    `edge_attr` is one row per entry of edge_index, or a cell_mp.IndexedRows (the `up_attr` a Complex hands out): then the
+    rows of the edge cochain are read through the adjacency's shared-cell index and [E, w] is never materialised.
+    edge_index None or empty: a graph without edges, edge_attr is not looked at.
+
+    forward has two routes; `last_route` names the one the last call took:
+      'fused'    autograd off, float32 on the GPU, `nn` a stock Sequential of two (Linear, norm, activation) groups whose
+                 norms fold (eval-mode BatchNorm1d or Identity), widths within 128, the edge features float32, on the GPU
+                 and as wide as x, FUSED_GINE on, no static batch: csr.cached_adjacency + ONE ops.gine_layer launch.
+      'generic'  everything else: on the GPU ops.aggregate with the message relu(A + B) and the self term folded in
+                 (differentiable with respect to x, the edge features and eps, float32 and float64), then `self.nn`; on
+                 the CPU, and where the aggregation does not take the operands (edge features of another width, which
+                 broadcast as in torch_geometric), the formula in plain torch, then `self.nn`.
+    `out` and `act_post` as in GINConv."""
+
+    def __init__(self, nn: Callable, eps: float = 0., train_eps: bool = False):
+        super().__init__()
+        self.nn = nn
+        self.initial_eps = eps
+        if train_eps:
+            self.eps = torch.nn.Parameter(torch.Tensor([eps]))
+        else:
+            self.register_buffer('eps', torch.Tensor([eps]))
+        self.last_route = None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        reset(self.nn)
+        self.eps.data.fill_(self.initial_eps)
+
+    def fused_stages(self, x, edge=None):
+        """([(W, b, scale, shift)] * 2, activation name) when the whole layer is ONE cwn_gine_layer_f32 launch, else None.
+        `edge`: the matrix the launch would read (an IndexedRows' src, or the dense rows); None: no edges."""
+        got = _gin_fused_stages(self.nn, self.eps, x) if FUSED_GINE else None
+        return got if got is not None and ops.gine_layer_applies(x, edge, got[0]) else None
+
+    def forward(self, x: Tensor, edge_index: Optional[Tensor], edge_attr=None, out: Optional[Tensor] = None,
+                act_post: str = 'id') -> Tensor:
+        n = x.size(0)
+        has_edges = edge_index is not None and edge_index.numel() > 0
+        edge, mode = _attr_operand(edge_attr) if has_edges else (None, 'aux')
+        if has_edges and edge is None:
+            raise ValueError('GINEConv: edge_index has entries and edge_attr is None')
+        aux = (edge_attr.index, edge.size(0)) if mode == 'aux' and has_edges else (None, 0)
+        fused = self.fused_stages(x, edge)
+        if fused is not None:
+            self.last_route = 'fused'
+            adj = cached_adjacency(edge_index, n, n, *aux) if has_edges else None
+            return ops.gine_layer(x, adj, edge, self.eps, fused[0], fused[1], act_post=act_post, out=out, edge_mode=mode)
+        self.last_route = 'generic'
+        takes = (x.is_cuda and x.dtype in (torch.float32, torch.float64)
+                 and (not has_edges or (isinstance(edge, Tensor) and edge.dim() == 2 and edge.dtype == x.dtype
+                                        and edge.device == x.device and edge.size(1) == x.size(1))))
+        if takes and has_edges:
+            s = ops.aggregate(cached_adjacency(edge_index, n, n, *aux), n, A=x, B=edge, msg_op=ops.MSG_RELU_A_PLUS_B,
+                              ib_mode=mode, self_x=x, eps=self.eps)
+        elif takes:
+            s = ops.aggregate(None, n, A=x, self_x=x, eps=self.eps)
+        else:
+            s = (1 + self.eps.to(x.dtype)) * x
+            if has_edges:
+                msg = torch.relu(x[edge_index[0]] + _edge_rows(edge_attr))
+                s = torch.zeros_like(x).index_add_(0, edge_index[1], msg) + s
         y = self.nn(s)
         return y if act_post == 'id' else ACTIVATIONS[act_post][1](y)
 

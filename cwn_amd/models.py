@@ -990,6 +990,31 @@ def _gin_network(k_in: int, hidden: int, norm, act_module):
     return torch.nn.Sequential(Linear(k_in, hidden), norm(hidden), act_module(), Linear(hidden, hidden), norm(hidden), act_module())
 
 
+def _pool_rows(x, batch, size: int, mean: bool):
+    """global_add_pool / global_mean_pool: the segmented-reduce kernel on the GPU, index_add_ on the CPU."""
+    if x.is_cuda:
+        return global_pool(x, batch, size, mean=mean)
+    p = torch.zeros(size, x.size(-1), dtype=x.dtype).index_add_(0, batch, x)
+    if mean:
+        p = p / torch.bincount(batch, minlength=size).clamp(min=1).to(x.dtype).unsqueeze(1)
+    return p
+
+
+def _pooled_head_fused(model, pooled):
+    """lin2(act(lin1(pooled))) of a model with `lin1`, `lin2`, `nonlinearity` and `dropout_rate` as one ops.agnostic_head
+    launch (one pooled matrix: its sum over the dimensions is that matrix's term), or None where it does not apply: under
+    autograd, with an active dropout, behind a JumpingKnowledge, on the CPU."""
+    if torch.is_grad_enabled() or (model.training and model.dropout_rate > 0) or hasattr(model, 'jump') or not pooled.is_cuda:
+        return None
+    H, O = model.lin1.out_features, model.lin2.out_features
+    ts = [t for t in (model.lin1.weight, model.lin1.bias, model.lin2.weight, model.lin2.bias) if t is not None]
+    if (model.nonlinearity not in ops.ACT_CODES or pooled.dtype not in _ffi.FLOAT_DTYPES or model.lin1.in_features != H
+            or not (1 <= H <= _ffi.AGNOSTIC_MAX_WIDTH and 1 <= O <= _ffi.AGNOSTIC_MAX_WIDTH)
+            or any(t.dtype != pooled.dtype or not t.is_cuda for t in ts)):
+        return None
+    return ops.agnostic_head([pooled], model.lin1.weight, model.lin1.bias, model.lin2.weight, model.lin2.bias, model.nonlinearity)
+
+
 class _GINStack(torch.nn.Module):
     """What GIN0, GIN, GIN0WithJK and GINWithJK (mp/graph_models.py) share: conv1 and convs of layers.GINConv over
     Linear -> BatchNorm -> act -> Linear -> BatchNorm -> act, an optional JumpingKnowledge, the readout per graph,
@@ -1023,13 +1048,7 @@ class _GINStack(torch.nn.Module):
 
     def pooling_fn(self, x, batch, size: int):
         """global_add_pool / global_mean_pool: the segmented-reduce kernel on the GPU, index_add_ on the CPU."""
-        mean = self.readout == 'mean'
-        if x.is_cuda:
-            return global_pool(x, batch, size, mean=mean)
-        p = torch.zeros(size, x.size(-1), dtype=x.dtype).index_add_(0, batch, x)
-        if mean:
-            p = p / torch.bincount(batch, minlength=size).clamp(min=1).to(x.dtype).unsqueeze(1)
-        return p
+        return _pool_rows(x, batch, size, mean=self.readout == 'mean')
 
     def _layers_cat(self, convs, x, edge_index):
         """JumpingKnowledge('cat') through ONE [n, L H] buffer when every layer takes the fused route; torch.cat otherwise."""
@@ -1044,17 +1063,7 @@ class _GINStack(torch.nn.Module):
         return torch.cat(xs, dim=-1)
 
     def _head_fused(self, pooled):
-        """lin2(act(lin1(pooled))) as one ops.agnostic_head launch (one pooled matrix: its sum over the dimensions is that
-        matrix's term), or None where it does not apply."""
-        if torch.is_grad_enabled() or (self.training and self.dropout_rate > 0) or hasattr(self, 'jump') or not pooled.is_cuda:
-            return None
-        H, O = self.lin1.out_features, self.lin2.out_features
-        ts = [t for t in (self.lin1.weight, self.lin1.bias, self.lin2.weight, self.lin2.bias) if t is not None]
-        if (self.nonlinearity not in ops.ACT_CODES or pooled.dtype not in _ffi.FLOAT_DTYPES or self.lin1.in_features != H
-                or not (1 <= H <= _ffi.AGNOSTIC_MAX_WIDTH and 1 <= O <= _ffi.AGNOSTIC_MAX_WIDTH)
-                or any(t.dtype != pooled.dtype or not t.is_cuda for t in ts)):
-            return None
-        return ops.agnostic_head([pooled], self.lin1.weight, self.lin1.bias, self.lin2.weight, self.lin2.bias, self.nonlinearity)
+        return _pooled_head_fused(self, pooled)
 
     @_one_check
     def forward(self, data):
@@ -1157,6 +1166,105 @@ class RingGIN(torch.nn.Module):
         if rows is not None and x.is_cuda:
             return ops.target_head(x, rows, self.lin1.weight, self.lin1.bias)
         return self.lin1(x[mask])                                        # :125-126 literally
+
+    def __repr__(self):
+        return self.__class__.__name__
+
+
+class EmbedGIN(torch.nn.Module):
+    """mp/molec_models.py:506-606, the graph baseline of the molecular experiments (`--model embed_gin`): the embedding front
+    of EmbedSparseCIN over vertices and edges, then GINEConv layers over the vertex graph whose edge features are the edge
+    cochain's rows -- read through the shared-coboundary index (cell_mp.IndexedRows), computed once for all layers -- the
+    readout over the vertices, act(lin1) and lin2.  Same constructor arguments, attributes and state_dict keys as the
+    reference (the embeddings appear as `v_embed_init.*` and as `init_conv.v_embed_init.*`).  In inference on the GPU
+    every layer is one launch where layers.FUSED_GINE is on and the head one ops.agnostic_head launch; on the CPU the
+    front, the layers and the head are plain torch."""
+
+    def __init__(self, atom_types, bond_types, out_size, num_layers, hidden, dropout_rate: float = 0.5, nonlinearity='relu',
+                 readout='sum', train_eps=False, apply_dropout_before='lin2', init_reduce='sum', embed_edge=False,
+                 embed_dim=None):
+        super().__init__()
+        self.max_dim = 1
+        if embed_dim is None:
+            embed_dim = hidden
+        self.v_embed_init = Embedding(atom_types, embed_dim)
+        self.e_embed_init = Embedding(bond_types, embed_dim) if embed_edge else None
+        self.reduce_init = InitReduceConv(reduce=init_reduce)
+        self.init_conv = EmbedVEWithReduce(self.v_embed_init, self.e_embed_init, self.reduce_init)
+        if readout not in ('sum', 'mean'):
+            raise NotImplementedError(f'Readout {readout} is not currently supported.')
+        self.readout = readout
+        self.dropout_rate = dropout_rate
+        self.apply_dropout_before = apply_dropout_before
+        self.nonlinearity = nonlinearity
+        act_module = get_nonlinearity(nonlinearity, return_module=True)
+        self.convs = torch.nn.ModuleList(
+            layers.GINEConv(_gin_network(embed_dim if i == 0 else hidden, hidden, BN, act_module), train_eps=train_eps)
+            for i in range(num_layers))
+        self.lin1 = Linear(hidden, hidden)
+        self.lin2 = Linear(hidden, out_size)
+
+    def reset_parameters(self):
+        for conv in self.convs:
+            conv.reset_parameters()
+        self.init_conv.reset_parameters()
+        self.lin1.reset_parameters()
+        self.lin2.reset_parameters()
+
+    def pooling_fn(self, x, batch, size: int):
+        return _pool_rows(x, batch, size, mean=self.readout == 'mean')
+
+    def _front_cpu(self, params):
+        """init_conv (mp/layers.py:490-570) in plain torch: its launches run on the GPU only."""
+        vx = self.v_embed_init(self.init_conv._prepare_v_inputs(params[0]))
+        if len(params) == 1:
+            return [vx]
+        e = params[1]
+        if e.x is not None:
+            return [vx, self.e_embed_init(self.init_conv._prepare_e_inputs(e))]
+        n_e = getattr(e, 'num_cells', None)
+        n_e = int(e.boundary_index[1].max()) + 1 if n_e is None else int(n_e)
+        rows, cells = vx[e.boundary_index[0]], e.boundary_index[1]
+        reduce = {'sum': 'add'}.get(self.reduce_init.reduce, self.reduce_init.reduce)
+        if reduce in ('add', 'mean'):
+            ex = torch.zeros(n_e, vx.size(1), dtype=vx.dtype).index_add_(0, cells, rows)
+            if reduce == 'mean':
+                ex = ex / torch.bincount(cells, minlength=n_e).clamp(min=1).to(vx.dtype).unsqueeze(1)
+        else:
+            ex = torch.zeros(n_e, vx.size(1), dtype=vx.dtype).scatter_reduce(
+                0, cells.unsqueeze(1).expand_as(rows), rows, {'max': 'amax', 'min': 'amin'}[reduce], include_self=False)
+        return [vx, ex]
+
+    @_one_check
+    def forward(self, data: ComplexBatch):
+        act = get_nonlinearity(self.nonlinearity, return_module=False)
+        assert data.cochains[0].x.size(-1) == 1
+        if 1 in data.cochains and data.cochains[1].x is not None:
+            assert data.cochains[1].x.size(-1) == 1
+        params = data.get_all_cochain_params(max_dim=self.max_dim, include_down_features=False)
+        xs = list(self.init_conv(*params)) if params[0].x.is_cuda else self._front_cpu(params)
+        xs[0] = ops.dropout(xs[0], self.dropout_rate, self.training)
+        data.set_xs(xs)
+        # the vertices' parameters alone (:578-581); the edge features do not change from layer to layer
+        params = data.get_all_cochain_params(max_dim=0, include_down_features=False)[0]
+        x, edge_index = params.x, params.up_index
+        edge_attr = params.kwargs['up_attr'] if edge_index is not None else None      # no edges (:584-586): the self term alone
+        for conv in self.convs:
+            x = conv(x, edge_index, edge_attr)
+        batch = data.nodes.batch
+        size = getattr(data, 'num_complexes', None)
+        if size is None:
+            size = int(batch.max()) + 1
+        x = self.pooling_fn(x, batch, int(size))
+        out = _pooled_head_fused(self, x)
+        if out is not None:
+            return out
+        if self.apply_dropout_before == 'lin1':
+            x = ops.dropout(x, self.dropout_rate, self.training)
+        x = act(self.lin1(x))
+        if self.apply_dropout_before in ('final_readout', 'lin2'):
+            x = ops.dropout(x, self.dropout_rate, self.training)
+        return self.lin2(x)
 
     def __repr__(self):
         return self.__class__.__name__

@@ -2481,51 +2481,129 @@ def gin_layer(x: Tensor, adj: Optional[Adjacency], eps, stages, act, act_post='i
     as the two do not overlap; nothing outside it is written.  Inference only: under a recording autograd (an operand that
     requires a gradient while gradients are enabled) this raises instead of detaching.  float32 on the GPU and widths up to
     128 (`gin_layer_applies`); another dtype or device is a TypeError that names it, never a fallback."""
-    x = _rows_operand(x, 'x', 2, **_GIN_ROWS)
+    x, out, d = _gin_descriptor('gin_layer', 'cwn_gin_layer_f32', _GIN_ROWS, 'layers.GINConv', x, eps, stages, act, act_post, out)
+    if d is None:
+        return out
+    _gin_plan(d, 'gin_layer', adj, int(x.size(0)))
+    _ffi.gin_layer(d, x.device)
+    return out
+
+
+def _gin_descriptor(op: str, entry: str, rows: dict, layer: str, x, eps, stages, act, act_post, out):
+    """The operand checks that gin_layer and gine_layer share, and the cwn_gin_desc without its plan: (x, out, descriptor);
+    the descriptor is None when there is nothing to launch (no rows)."""
+    x = _rows_operand(x, 'x', 2, **rows)
     if len(stages) != 2 or any(len(s) != 4 for s in stages):
-        raise ValueError('gin_layer: stages is [(W1, b1, scale1, shift1), (W2, b2, scale2, shift2)]')
+        raise ValueError(f'{op}: stages is [(W1, b1, scale1, shift1), (W2, b2, scale2, shift2)]')
     named = []
     for k, (W, b, sc, sh) in enumerate(stages, 1):
-        named.append(tuple(_rows_operand(t, f'{name}{k}', dim, **_GIN_ROWS)
+        named.append(tuple(_rows_operand(t, f'{name}{k}', dim, **rows)
                            for t, name, dim in ((W, 'W', 2), (b, 'b', 1), (sc, 'scale', 1), (sh, 'shift', 1))))
     if isinstance(eps, Tensor):
-        eps = _rows_operand(eps.reshape(-1), 'eps', 1, **_GIN_ROWS)
+        eps = _rows_operand(eps.reshape(-1), 'eps', 1, **rows)
         if eps.numel() != 1:
-            raise ValueError(f'gin_layer: eps holds {eps.numel()} elements, not one')
+            raise ValueError(f'{op}: eps holds {eps.numel()} elements, not one')
     elif eps is not None:
         eps = None if float(eps) == 0.0 else torch.full((1,), float(eps), dtype=torch.float32, device=x.device)
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in [x, eps] + [t for s in named for t in s]):
-        raise RuntimeError('gin_layer is inference only (cwn_gin_layer_f32 has no backward) and an operand requires a gradient '
-                           'while autograd is recording: run it under torch.no_grad(), or use layers.GINConv, whose '
+        raise RuntimeError(f'{op} is inference only ({entry} has no backward) and an operand requires a gradient '
+                           f'while autograd is recording: run it under torch.no_grad(), or use {layer}, whose '
                            'generic route is differentiable')
     if _ffi.DYN_ROWS:
-        raise RuntimeError('gin_layer takes host row counts: it does not run under _ffi.dynamic_rows (a static batch)')
+        raise RuntimeError(f'{op} takes host row counts: it does not run under _ffi.dynamic_rows (a static batch)')
     named = [tuple(None if t is None else t.contiguous() for t in s) for s in named]
     if not gin_layer_applies(x, named):
-        raise ValueError(f'gin_layer takes x [n, w], W1 [H, w], W2 [H, H] with 1 <= w, H <= {_ffi.GIN_MAX_WIDTH} and vectors '
+        raise ValueError(f'{op} takes x [n, w], W1 [H, w], W2 [H, H] with 1 <= w, H <= {_ffi.GIN_MAX_WIDTH} and vectors '
                          f'[H]: x {tuple(x.shape)}, W1 {tuple(named[0][0].shape)}, W2 {tuple(named[1][0].shape)}')
     n, w = int(x.size(0)), int(x.size(1))
     H = int(named[0][0].size(0))
     if out is None:
         out = torch.empty(n, H, dtype=torch.float32, device=x.device)
     else:
-        out = _rows_operand(out, 'out', 2, **_GIN_ROWS)
+        out = _rows_operand(out, 'out', 2, **rows)
         if tuple(out.shape) != (n, H) or out.device != x.device:
-            raise ValueError(f'gin_layer: out is {tuple(out.shape)} on {out.device}, the result {(n, H)} on {x.device}')
+            raise ValueError(f'{op}: out is {tuple(out.shape)} on {out.device}, the result {(n, H)} on {x.device}')
     if n == 0:
-        return out
+        return x, out, None
     d = _ffi.GinDesc(x=x.data_ptr(), eps_dev=_ffi.ptr(eps), out=out.data_ptr(), n=n, ldx=_ld(x), ldout=_ld(out), w=w, H=H,
                      act=_act_code(act), act_post=_act_code(act_post))
     (d.W1, d.b1, d.scale1, d.shift1), (d.W2, d.b2, d.scale2, d.shift2) = [[_ffi.ptr(t) for t in s] for s in named]
-    if adj is not None and adj.n_entries:
-        if adj.n_dst != n or adj.n_val != n:
-            raise ValueError(f'gin_layer: adjacency over {adj.n_val} -> {adj.n_dst} rows, x has {n}')
-        if not adj.built:
-            from .csr import build_many
-            build_many([adj])
-        wait_ready([adj])
-        d.rowptr, d.col = adj.rowptr.data_ptr(), adj.col.data_ptr()
-    _ffi.gin_layer(d, x.device)
+    d._keep = (eps, named)             # (what the descriptor points at, alive until the launch is issued)
+    return x, out, d
+
+
+def _gin_plan(d, op: str, adj: Optional[Adjacency], n: int) -> bool:
+    """rowptr / col of a built plan over the n rows of x into the descriptor; False where there are no entries."""
+    if adj is None or not adj.n_entries:
+        return False
+    if adj.n_dst != n or adj.n_val != n:
+        raise ValueError(f'{op}: adjacency over {adj.n_val} -> {adj.n_dst} rows, x has {n}')
+    if not adj.built:
+        from .csr import build_many
+        build_many([adj])
+    wait_ready([adj])
+    d.rowptr, d.col = adj.rowptr.data_ptr(), adj.col.data_ptr()
+    return True
+
+
+# an operand of cwn_gine_layer_f32
+_GINE_ROWS = dict(dtypes=(torch.float32,), what='gine_layer: ', hint='cwn_gine_layer_f32 computes in fp32 only (float64 and '
+                  'training run through ops.aggregate and the torch modules: layers.GINEConv)')
+
+
+def gine_layer_applies(x: Tensor, edge, stages) -> bool:
+    """Does cwn_gine_layer_f32 take these operands?  What `gin_layer_applies` asks of x and the stages, and of `edge` (None: a
+    graph without edges): float32 on the GPU, [rows, w] with contiguous rows, as wide as x."""
+    if not gin_layer_applies(x, stages):
+        return False
+    return edge is None or (isinstance(edge, Tensor) and edge.is_cuda and edge.dtype == torch.float32 and edge.device == x.device
+                            and _rows_contiguous(edge, 2) and edge.size(1) == x.size(1))
+
+
+def gine_layer(x: Tensor, adj: Optional[Adjacency], edge: Optional[Tensor], eps, stages, act, act_post='id',
+               out: Optional[Tensor] = None, edge_mode: str = 'aux') -> Tensor:
+    """A whole GINEConv (torch_geometric 1.6.3's definition, `edge_index[0]` the source) in inference as ONE launch:
+
+        s   = sum_{j -> i} relu(x_j + e_ji) + (1 + eps) * x_i      (`adj`: a destination-sorted plan over the rows of x;
+        h   = act((s W1^T + b1) * scale1 + shift1)                   None or without entries: no edges, `edge` is not read)
+        out = act_post(act((h W2^T + b2) * scale2 + shift2))
+
+    `edge` holds the edge features, as wide as x, in one of two forms.  edge_mode='aux': one row per edge CELL, read through
+    the plan's shared-cell index (`adj.aux`; the src of a cell_mp.IndexedRows -- the [E, w] matrix is never materialised), so
+    the plan must have been built with that index and edge.size(0) == adj.n_aux.  edge_mode='perm': one row per entry of the
+    index the plan was built from, as a torch_geometric caller hands edge_attr: edge.size(0) == adj.n_entries.  Everything
+    else -- `eps`, `stages`, `act`, `act_post`, `out`, inference only, float32 on the GPU, widths up to 128, TypeError and
+    never a fallback for another dtype or device -- is as in `gin_layer`."""
+    if edge_mode not in ('aux', 'perm'):
+        raise ValueError(f"gine_layer: edge_mode {edge_mode!r}: 'aux' or 'perm'")
+    edge = _rows_operand(edge, 'edge', 2, **_GINE_ROWS)
+    x, out, d = _gin_descriptor('gine_layer', 'cwn_gine_layer_f32', _GINE_ROWS, 'layers.GINEConv', x, eps, stages, act, act_post,
+                                out)
+    has_edges = adj is not None and adj.n_entries > 0
+    if has_edges:
+        if edge is None:
+            raise ValueError('gine_layer: the adjacency has entries and edge is None')
+        if torch.is_grad_enabled() and edge.requires_grad:
+            raise RuntimeError('gine_layer is inference only (cwn_gine_layer_f32 has no backward) and edge requires a gradient '
+                               'while autograd is recording: run it under torch.no_grad(), or use layers.GINEConv, whose '
+                               'generic route is differentiable')
+        if edge.size(1) != x.size(1) or edge.device != x.device:
+            raise ValueError(f'gine_layer: edge is {tuple(edge.shape)} on {edge.device}: its width must be that of x '
+                             f'{tuple(x.shape)} on {x.device} (another width runs through layers.GINEConv\'s generic route)')
+        if edge_mode == 'aux':
+            if adj.aux is None:
+                raise ValueError("gine_layer: edge_mode='aux' needs an adjacency built with a shared-cell index (aux_index)")
+            if edge.size(0) != adj.n_aux:
+                raise ValueError(f"gine_layer: edge_mode='aux': edge has {edge.size(0)} rows, the plan's shared cells are {adj.n_aux}")
+        elif edge.size(0) != adj.n_entries:
+            raise ValueError(f"gine_layer: edge_mode='perm': edge has {edge.size(0)} rows, the plan has {adj.n_entries} entries")
+    if d is None:
+        return out
+    D = _ffi.GineDesc(g=d)
+    if _gin_plan(D.g, 'gine_layer', adj, int(x.size(0))):
+        D.e, D.lde, D.n_e = edge.data_ptr(), _ld(edge), int(edge.size(0))
+        D.eidx = (adj.aux if edge_mode == 'aux' else adj.perm).data_ptr()
+    _ffi.gine_layer(D, x.device)
     return out
 
 

@@ -1505,6 +1505,42 @@ typedef struct cwn_gin_desc {
 int cwn_gin_layer_f32(const cwn_gin_desc* desc_host, cwn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * GINEConv as one launch (csrc/cwn_gine.hip), float32, inference.  Additive to ABI 24.
+ *
+ * Replaces the whole forward of a torch_geometric (1.6.3) GINEConv whose `nn` is the two-stage network of EmbedGIN
+ * (mp/molec_models.py:506-606), the graph baseline of the molecular experiments -- the GINConv above with edge features
+ * inside the message:
+ *
+ *     s   = (sum over the entries p of row i, in CSR order, of relu(x[col[p], :] + e[eidx[p], :])) + (1 + eps) * x[i, :]
+ *     h   = act( (s W1^T + b1) * scale1 + shift1 )                                                          [n, H]
+ *     out = act_post( act( (h W2^T + b2) * scale2 + shift2 ) )                                              [n, H]
+ *
+ * `g` is the descriptor of cwn_gin_layer_f32 with the meaning, the limits and the geometry it has there (the kernels share
+ * csrc/cwn_gin_tile.h): only the fold of a row's entries differs.  A row's messages are added one after the other in CSR
+ * order whatever its length, then (1 + eps) * x; a row without entries gets (1 + eps) * x.  The ReLU propagates NaN (a NaN
+ * operand gives NaN, a -Inf message gives 0, +Inf + -Inf is NaN).  No atomics: two launches on the same operands give the
+ * same bits.
+ *
+ *   - e [n_e, w] with row stride lde >= w: the edge features, as wide as x.  eidx [E]: the row of e that CSR position p
+ *     reads, in [0, n_e).  The kernel has one path for its two uses: the plan's `aux` (the shared-cell index of
+ *     cwn_csr_build: e holds one row per edge CELL, and the [E, w] matrix of per-entry attributes is never materialised) and
+ *     the plan's `perm` (e holds one row per ORIGINAL entry, n_e = E, as a torch_geometric caller hands edge_attr).
+ *   - g.rowptr == NULL: a graph without edges; e and eidx may then be NULL and the layer is nn((1 + eps) x).
+ *   - g.n is a HOST count, n_e too: there is NO m_dev and no static batch reaches this launch.
+ * The checks of cwn_gin_layer_f32 on `g` come first, with its codes.  Then, with a rowptr: a NULL e or eidx, lde < w or
+ * n_e < 0 is CWN_ERR_BAD_ARG; e or eidx off 4 bytes is CWN_ERR_ALIGN.  n == 0: CWN_OK, nothing is launched.  All checks
+ * precede the first HIP call; the launcher neither allocates nor synchronises.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct cwn_gine_desc {
+    cwn_gin_desc g;            /* x, the plan, eps, the two stages, out: as in cwn_gin_layer_f32 */
+    const float* e;            /* [n_e, w] row stride lde, or NULL without a rowptr */
+    const int32_t* eidx;       /* [E] row of e per CSR position (the plan's aux or perm), or NULL without a rowptr */
+    int64_t lde;
+    int64_t n_e;               /* host count of the rows of e */
+} cwn_gine_desc;
+int cwn_gine_layer_f32(const cwn_gine_desc* desc_host, cwn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Device-side batching (collate): build the arrays of a ComplexBatch from a dataset that is
  * resident in HBM in packed form, with ONE launch.
  *
