@@ -25,7 +25,7 @@ EXPORTS = ('cwn_abi_version', 'cwn_error_string', 'cwn_target_arch', 'cwn_csr_wo
            'cwn_layernorm_act_f32', 'cwn_layernorm_bwd_workspace_bytes', 'cwn_layernorm_bwd_f32',
            'cwn_oriented_layer_f32', 'cwn_oriented_dz_f32',
            'cwn_target_head_f32', 'cwn_target_head_bwd_f32', 'cwn_target_head_bwd_workspace_bytes',
-           'cwn_linear_many_f64', 'cwn_update_chain_f64',
+           'cwn_linear_many_f64', 'cwn_update_chain_f64', 'cwn_update_chain_f32',
            'cwn_aggregate_act_f32', 'cwn_aggregate_act_f64',
            'cwn_embed_pool_f32', 'cwn_embed_pool_f64', 'cwn_agnostic_head_f32', 'cwn_agnostic_head_f64',
            'cwn_gin_layer_f32', 'cwn_gine_layer_f32',
@@ -377,6 +377,15 @@ class ChainDescF64(C.Structure):
                 ('act', C.c_int32), ('reserved', C.c_int32)]
 
 
+# the float32 update chain (csrc/cwn_chain_f32.hip) = CWN_CHAIN_F32_MAX_DIMS / _MAX_WIDTH / _TM
+CHAIN_F32_MAX_DIMS, CHAIN_F32_MAX_WIDTH, CHAIN_F32_TM = 4, 128, 32
+
+
+class ChainDescF32(C.Structure):
+    """cwn_chain_desc_f32: the update / combine networks of one dimension of a cwn_update_chain_f32 launch."""
+    _fields_ = ChainDescF64._fields_ + [('m_dev', C.c_void_p)]
+
+
 class GemmTnDesc(C.Structure):
     _fields_ = [('dZ', C.c_void_p), ('X', C.c_void_p), ('X2', C.c_void_p), ('in_scale', C.c_void_p),
                 ('in_shift', C.c_void_p), ('in_scale2', C.c_void_p), ('in_shift2', C.c_void_p),
@@ -550,6 +559,8 @@ def lib():
     L.cwn_linear_many_f64.argtypes = [C.POINTER(LinearDescF64), C.c_int, C.c_void_p]
     L.cwn_update_chain_f64.restype = C.c_int
     L.cwn_update_chain_f64.argtypes = [C.POINTER(ChainDescF64), C.c_int, C.c_void_p]
+    L.cwn_update_chain_f32.restype = C.c_int
+    L.cwn_update_chain_f32.argtypes = [C.POINTER(ChainDescF32), C.c_int, C.c_void_p]
     L.cwn_aggregate_act_f32.restype = C.c_int
     L.cwn_aggregate_act_f32.argtypes = [C.POINTER(AggActDesc), C.c_int, C.c_void_p]
     L.cwn_aggregate_act_f64.restype = C.c_int

@@ -136,6 +136,29 @@ BLOCKED_LAYER = os.environ.get('CWN_BLOCKED_LAYER') != '0'   # False: propagate 
 # lin1s / lin2) as torch modules -- a rocBLAS dgemm, a bias add and an activation launch per Linear -- instead of the
 # csrc/cwn_dense_f64.hip launches
 FUSED_F64_DENSE = os.environ.get('CWN_FUSED_F64_DENSE') != '0'
+# The update / combine networks of a float32 SparseCINConv layer in inference as ONE cwn_update_chain_f32 launch
+# (csrc/cwn_chain_f32.hip: any width up to 128, any of the five activations) where cwn_update_mlp_f32 -- 64 / 128 with ReLU --
+# does not serve them.  A set of regimes:
+#   'relu_width'  ReLU networks at a width other than 64 / 128, instead of a grouped GEMM launch per stage + the combine;
+#   'act'         networks with elu / tanh / sigmoid / id at any width up to 128, instead of the torch modules.
+# CWN_FUSED_CHAIN_F32=1 / =0: both / neither; unset: FUSED_CHAIN_F32_DEFAULT, which holds the regimes in which the route has
+# measured faster than the one it replaces by more than the run-to-run spread of both (tools/bench_chain_f32.py,
+# profiles/chain_f32.md) with the whole suite passing.  True / False are read as both / neither.
+CHAIN_F32_REGIMES = frozenset({'relu_width', 'act'})
+FUSED_CHAIN_F32_DEFAULT = frozenset({'relu_width', 'act'})
+
+
+def _chain_f32_switch(value: Optional[str]):
+    """The regimes CWN_FUSED_CHAIN_F32 = `value` turns on."""
+    return {'0': frozenset(), '1': CHAIN_F32_REGIMES}.get(value, FUSED_CHAIN_F32_DEFAULT)
+
+
+FUSED_CHAIN_F32 = _chain_f32_switch(os.environ.get('CWN_FUSED_CHAIN_F32'))
+
+
+def _chain_f32_on(regime: str) -> bool:
+    on = FUSED_CHAIN_F32
+    return regime in on if isinstance(on, (set, frozenset)) else bool(on)
 CSR_REUSE = True              # blocked layer kernel: sort a batch's adjacencies once, later layers load the result
 # One workgroup per item and one item per CU at a time: the blocked kernel wins while the items fit the chip
 # a few times over (measured on ZINC-like batches, tools/range_of_use.sh, M cells/s blocked vs CSR path: 256
@@ -251,6 +274,7 @@ class ByModule:
 # prepared launches per (layer module, batch): kept OUTSIDE the modules (ctypes records do not deepcopy / pickle)
 _BLOCKED_CACHE = ByModule()
 _MLP_CACHE = ByModule()            # layer module -> (ops.MlpLaunch, (start, dims, outputs), BatchNorm modules)
+_CHAIN_CACHE = ByModule()          # layer module -> {regime: (ops.ChainLaunch or None: declined, (start, dims), BatchNorm modules, STRUCT_EPOCH)}
 FUSED_OGB_FRONT = os.environ.get('CWN_FUSED_OGB_FRONT', '1') != '0'      # (A/B: '0' = the separate launches of the OGB encoders' front)
 _FRONT_CACHE = ByModule()          # embedding front module -> {id(boundary_index_1): (ops.FrontLaunch, (rings?, reduce))}
 
@@ -1219,7 +1243,8 @@ class SparseCINConv(torch.nn.Module):
         """Inference: the update / combine networks of ALL dimensions (mp/layers.py:193-199, :255-260) with eval-mode
         BatchNorm and the ReLU folded into the epilogue -- in ONE launch where `_one_launch` has a kernel for them, else
         as one grouped MFMA launch per update stage over every branch and dimension, then the combine: two branches as a
-        grouped launch with torch.cat folded into the K-concatenation, three or four as torch.cat + combine_nn.  No
+        grouped launch with torch.cat folded into the K-concatenation, three or four as torch.cat + combine_nn.  ReLU networks
+        at a width that kernel does not take go to `_dense_chain_f32` first (regime 'relu_width' of FUSED_CHAIN_F32).  No
         autograd, running statistics; returns None when it does not apply and the caller runs the torch modules instead."""
         from . import _ffi
         if torch.is_grad_enabled() or any(o.dtype != torch.float32 for o in outs):
@@ -1235,6 +1260,10 @@ class SparseCINConv(torch.nn.Module):
                     return res
             else:
                 del _MLP_CACHE[self]
+        if FUSED_UPDATE_MLP and not ops.GEMM_EXACT:      # ReLU at a width the one-launch kernel below does not take
+            res = self._dense_chain_f32(plans, outs, start, regime='relu_width')
+            if res is not None:
+                return res
         got = self._update_chains(plans, outs, start)
         if got is None:
             return None
@@ -1295,23 +1324,104 @@ class SparseCINConv(torch.nn.Module):
         res = launch.run([D.x_up for D in mdims], [D.x_b for D in mdims])
         return res if res is not None else ops.update_mlp(mdims)
 
-    def _f64_chain(self, lvl):
+    def _chain_net(self, lvl, dtype, wmax: int):
         """(weights, biases, folds, activation) of one dimension's three networks in the order of ops.ChainDim, or None when
         they are not the stock Linear-norm-act structure with one of the five activations and Identity / eval-mode
-        BatchNorm norms, or are wider than the launch takes."""
+        BatchNorm norms, hold another dtype, or are wider than `wmax`."""
         if type(lvl) is not SparseCINCochainConv:
             return None
         got = [_f64_stages(lvl.update_up_nn, 2), _f64_stages(lvl.update_boundaries_nn, 2), _f64_stages(lvl.combine_nn, 1)]
         if any(g is None for g in got) or len({g[1] for g in got}) != 1:
             return None
         stages = got[0][0] + got[1][0] + got[2][0]
-        wmax = ops._ffi.CHAIN_F64_MAX_WIDTH
-        if any(lin.weight.dtype != torch.float64 or lin.out_features > wmax for lin, _ in stages) or stages[0][0].in_features > wmax:
+        if any(lin.weight.dtype != dtype or lin.out_features > wmax for lin, _ in stages) or stages[0][0].in_features > wmax:
             return None                  # (hidden 256 of cwn-sr-base.sh: dgemm is the right tool)
         folds = [_fold_norm(norm, lin.out_features) for lin, norm in stages]
         if any(f is None for f in folds):
             return None                  # LayerNorm, a training-mode BatchNorm
         return [lin.weight for lin, _ in stages], [lin.bias for lin, _ in stages], folds, got[0][1]
+
+    def _f64_chain(self, lvl):
+        """`_chain_net` for the float64 launch (widths up to 64)."""
+        return self._chain_net(lvl, torch.float64, ops._ffi.CHAIN_F64_MAX_WIDTH)
+
+    def _dense_chain_f32(self, plans, outs, start: int = 0, cochain_params=None, regime: str = 'act') -> Optional[List[Tensor]]:
+        """The update / combine networks of ALL dimensions of a float32 layer in ONE launch (ops.update_chain_f32,
+        csrc/cwn_chain_f32.hip) in one of the regimes of FUSED_CHAIN_F32: 'relu_width' -- ReLU networks at a width that
+        cwn_update_mlp_f32 does not take (asked by `_dense_eval` in front of its own launches) -- or 'act' -- networks
+        with elu / tanh / sigmoid / id at any width up to 128 (asked by `forward` behind `_dense_eval`, which reads ReLU
+        networks only).  In the 'act' regime a dimension whose message has no fused stream (plans[d] is None) runs its
+        generic propagate first and joins the same launch, as in `_dense_f64`.  Inference only.  The launch is prepared
+        once per layer (ops.ChainLaunch in _CHAIN_CACHE): per call only the rows are looked at.
+        None when it does not apply -- the regime is off, a recording autograd, CIN++, float64 or CPU features, LayerNorm or
+        a training-mode BatchNorm, a passed-in network, a width above 128, more than 4 dimensions, ReLU at 64 / 128 --
+        and the caller goes on as before."""
+        if not _chain_f32_on(regime) or torch.is_grad_enabled() or type(self) is not SparseCINConv:
+            return None
+        active = list(range(start, len(plans)))
+        unfused = [d for d in active if plans[d] is None]
+        if not active or len(outs) != 2 * (len(active) - len(unfused)) or len(active) > ops._ffi.CHAIN_F32_MAX_DIMS:
+            return None
+        if unfused and (regime != 'act' or cochain_params is None or _ffi_dyn()):
+            return None                  # (a static batch: the generic propagate is not part of its captured graph)
+        feats = list(outs) + [cochain_params[d].x for d in unfused]
+        if any(not isinstance(t, Tensor) or t.dtype != torch.float32 or not t.is_cuda for t in feats):
+            return None
+        key = (start, len(plans))
+        ents = _CHAIN_CACHE.get(self)
+        if ents is None:
+            _CHAIN_CACHE[self] = ents = {}
+        ent = ents.get(regime)
+        if ent is not None and (ent[1] != key or ent[3] != ops.STRUCT_EPOCH or (ent[0] is not None and not ent[0].current())):
+            ent = None
+        if ent is None:
+            got = self._chain_f32_launch(active, regime)
+            if got is None and any(isinstance(m, BN) and m.training for d in active for m in self.mp_levels[d].modules()):
+                return None              # (not remembered: eval() is no change of the module tree)
+            ent = ents[regime] = (None, key, [], ops.STRUCT_EPOCH) if got is None else (got[0], key, got[1], ops.STRUCT_EPOCH)
+        if ent[0] is None:
+            return None                  # (these networks have been read and are not this regime's)
+        launch, _, norms, _ = ent
+        if any(m.training for m in norms):
+            return None                  # batch statistics are no fixed affine
+        ins, k = [], 0
+        for d in active:
+            if plans[d] is None:
+                ins.append(self.mp_levels[d].aggregate_unfused(cochain_params[d]))
+            else:
+                ins.append((outs[k], outs[k + 1]))
+                k += 2
+        res = launch.run(ins)
+        if res is None and unfused:      # (an input of another width than its network: let torch say so)
+            return [self.mp_levels[d].finish(u, b) for d, (u, b) in zip(active, ins)]
+        return res
+
+    def _chain_f32_launch(self, active, regime: str):
+        """(ops.ChainLaunch, BatchNorm modules) of the networks of the dimensions `active` when they are `regime`'s, or None:
+        'relu_width' -- all ReLU and not the 64 / 128 shapes of cwn_update_mlp_f32; 'act' -- none of them ReLU."""
+        nets = [self._chain_net(self.mp_levels[d], torch.float32, ops._ffi.CHAIN_F32_MAX_WIDTH) for d in active]
+        if any(net is None for net in nets):
+            return None
+        relu = [net[3] == 'relu' for net in nets]
+        if any(relu) != (regime == 'relu_width') or len(set(relu)) != 1:
+            return None
+        if regime == 'relu_width' and all(net[0][0].size(0) in (64, 128) and net[0][0].size(1) <= net[0][0].size(0) for net in nets):
+            return None                  # ReLU at 64 / 128 is cwn_update_mlp_f32's, whatever makes that launch decline
+        empty = lambda w: w.new_empty(0, w.size(1))
+        dims = [ops.ChainDim(in_up=empty(net[0][0]), in_b=empty(net[0][0]), weights=net[0], biases=net[1], folds=net[2], act=net[3])
+                for net in nets]
+        if not ops.update_chain_f32_applies(dims):
+            return None
+        sources, norms = [], []
+        for d in active:
+            lvl = self.mp_levels[d]
+            for m in list(lvl.update_up_nn) + list(lvl.update_boundaries_nn) + list(lvl.combine_nn):
+                if isinstance(m, Linear):
+                    sources += [m.weight, m.bias]
+                elif isinstance(m, BN):
+                    norms.append(m)
+                    sources += [m.weight, m.bias, m.running_mean, m.running_var, m.num_batches_tracked]
+        return ops.ChainLaunch(dims, sources), norms
 
     def _dense_f64(self, plans, outs, start: int = 0, cochain_params=None) -> Optional[List[Tensor]]:
         """The update / combine networks of ALL dimensions of a float64 layer in ONE launch (ops.update_chain_f64,
@@ -1420,6 +1530,8 @@ class SparseCINConv(torch.nn.Module):
         self.__dict__['_out_drop'], self.__dict__['_out_dropped'] = (float(out_dropout) if self.training else 0.0), False
         plans, outs = self.propagate_all(*cochain_params, start_to_process=start_to_process)
         dense = self._dense_eval(plans, outs, start_to_process)
+        if dense is None:
+            dense = self._dense_chain_f32(plans, outs, start_to_process, cochain_params)
         if dense is None:
             dense = self._dense_f64(plans, outs, start_to_process, cochain_params)
         if dense is None:

@@ -2268,8 +2268,9 @@ class ChainDim:
     out: Optional[Tensor] = None
 
 
-def _chain_shapes(d: ChainDim) -> Optional[Tuple[int, int, int]]:
-    """(n, F, H) when the shapes of `d` are those of a SparseCINConv dimension, else None."""
+def _chain_shapes(d: ChainDim, paired: bool = True) -> Optional[Tuple[int, int, int]]:
+    """(n, F, H) when the shapes of `d` are those of a SparseCINConv dimension, else None.  `paired`: a stage's scale and
+    shift come together or not at all (the float64 launch; the float32 one takes either alone)."""
     ts = [d.in_up, d.in_b] + list(d.weights)
     if len(d.weights) != 5 or len(d.biases) != 5 or len(d.folds) != 5 or not all(isinstance(t, Tensor) and t.dim() == 2 for t in ts):
         return None
@@ -2279,7 +2280,9 @@ def _chain_shapes(d: ChainDim) -> Optional[Tuple[int, int, int]]:
     if tuple(d.in_b.shape) != (n, F) or [tuple(w.shape) for w in d.weights] != want:
         return None
     vecs = list(d.biases) + [t for f in d.folds for t in f]
-    if any(t is not None and tuple(t.shape) != (H,) for t in vecs) or any((s is None) != (t is None) for s, t in d.folds):
+    if any(len(f) != 2 for f in d.folds) or any(t is not None and tuple(t.shape) != (H,) for t in vecs):
+        return None
+    if paired and any((s is None) != (t is None) for s, t in d.folds):
         return None
     if d.out is not None and (d.out.dim() != 2 or d.out.size(0) < n or d.out.size(1) != H):
         return None
@@ -2336,6 +2339,128 @@ def update_chain_f64(dims: Sequence[ChainDim]) -> List[Tensor]:
     _ffi.check(_ffi.lib().cwn_update_chain_f64((_ffi.ChainDescF64 * len(descs))(*descs), len(descs), _ffi.stream_ptr(dev)),
                'cwn_update_chain_f64')
     return outs
+
+
+# ------------------------------------------------------------------------------------------------
+# The float32 update chain (csrc/cwn_chain_f32.hip): the same networks in float32 at any width up to 128, inference only
+# ------------------------------------------------------------------------------------------------
+# an operand of the float32 chain kernel
+_F32_ROWS = dict(dtypes=(torch.float32,), rows_got=True,
+                 hint='this kernel computes in fp32 only (float64 runs through update_chain_f64)')
+
+
+def _chain_f32_tensors(d: ChainDim) -> list:
+    return [d.in_up, d.in_b, d.out] + list(d.weights) + list(d.biases) + [t for f in d.folds for t in f]
+
+
+def update_chain_f32_applies(dims: Sequence[ChainDim]) -> bool:
+    """Does cwn_update_chain_f32 take these dimensions?  1 to 4 of them, every tensor float32 on the GPU with contiguous
+    rows (the weights contiguous), 1 <= F, H <= 128, the five-stage shapes of a SparseCINConv dimension, a known activation."""
+    if not 1 <= len(dims) <= _ffi.CHAIN_F32_MAX_DIMS:
+        return False
+    wmax = _ffi.CHAIN_F32_MAX_WIDTH
+    for d in dims:
+        shp = _chain_shapes(d, paired=False)
+        if shp is None or not (1 <= shp[1] <= wmax and 1 <= shp[2] <= wmax):
+            return False
+        if not all(t is None or (t.dtype == torch.float32 and t.is_cuda and _rows_contiguous(t, t.dim())) for t in _chain_f32_tensors(d)):
+            return False
+        if not all(w.is_contiguous() for w in d.weights):
+            return False
+        if isinstance(d.act, str) and d.act not in ACT_CODES:
+            return False
+    return True
+
+
+def update_chain_f32(dims: Sequence[ChainDim]) -> List[Tensor]:
+    """`update_chain_f64` in float32: act(aff(combine_nn[0](cat(update_up_nn(in_up), update_boundaries_nn(in_b))))) of every
+    dimension of a SparseCINConv layer in ONE launch at any widths 1 <= F, H <= 128 and with any of the five activations
+    (csrc/cwn_chain_f32.hip: exact-fp32 MFMA, everything between the two inputs and the output in LDS).  Takes the same
+    `ChainDim`s -- here a stage's scale and shift may be absent independently -- and returns the outputs [n, H] per
+    dimension (`out`, when given, has its first n rows written).  Inference only: nothing is recorded for autograd.  A row's
+    result depends on that row and the weights alone.  Inside `_ffi.dynamic_rows` a row count that is a capacity is read
+    from the device (include/cwn_hip.h, "Conventions").  ctypes only: the compiled binding does not carry this launch.
+    Anything but float32 GPU tensors is a TypeError, shapes the launch does not take (`update_chain_f32_applies`) a
+    ValueError."""
+    descs, outs, dev = [], [], None
+    for i, d in enumerate(dims):
+        named = [('in_up', d.in_up, 2), ('in_b', d.in_b, 2)] + [(f'weights[{s}]', w, 2) for s, w in enumerate(d.weights)] + \
+                [(f'biases[{s}]', b, 1) for s, b in enumerate(d.biases)] + \
+                [(f'folds[{s}]', t, 1) for s, f in enumerate(d.folds) for t in f] + [('out', d.out, 2)]
+        for name, t, dim in named:
+            _rows_operand(t, f'dims[{i}].{name}', dim, **_F32_ROWS)
+    if not update_chain_f32_applies(dims):
+        raise ValueError('update_chain_f32: 1 to 4 dimensions of the five-stage shapes [H, F], [H, H], [H, F], [H, H], [H, 2H] '
+                         f'with 1 <= F, H <= {_ffi.CHAIN_F32_MAX_WIDTH}, contiguous weights, a known activation')
+    for d in dims:
+        n, F, H = _chain_shapes(d, paired=False)
+        dev = d.in_up.device
+        out = torch.empty(n, H, dtype=torch.float32, device=dev) if d.out is None else d.out[:n]
+        outs.append(out)
+        D = _ffi.ChainDescF32(in_up=d.in_up.data_ptr(), in_b=d.in_b.data_ptr(), out=out.data_ptr(), n=n, ld_up=_ld(d.in_up),
+                              ld_b=_ld(d.in_b), ld_out=int(d.out.stride(0)) if d.out is not None and d.out.size(0) > 1 else H,
+                              F=F, H=H, act=_act_code(d.act))
+        for s in range(5):
+            D.W[s], D.bias[s] = d.weights[s].data_ptr(), _ffi.ptr(d.biases[s])
+            D.scale[s], D.shift[s] = _ffi.ptr(d.folds[s][0]), _ffi.ptr(d.folds[s][1])
+        descs.append(D)
+    _ffi._set_dyn(descs, 'n')
+    _ffi.check(_ffi.lib().cwn_update_chain_f32((_ffi.ChainDescF32 * len(descs))(*descs), len(descs), _ffi.stream_ptr(dev)),
+               'cwn_update_chain_f32')
+    return outs
+
+
+class ChainLaunch:
+    """A prepared cwn_update_chain_f32 call for one layer, as MlpLaunch is for cwn_update_mlp_f32 (an eager forward is bound
+    by its host time, and re-reading fifteen Linear layers and their norms per call costs more than the launch): the weights,
+    biases, folds and activation of `dims` -- which `update_chain_f32` has taken -- filled in once; `run` fills in the rows
+    of this call and launches.  `sources`: every tensor the record was derived from (Linear weights and biases, the
+    BatchNorm tensors behind the folds); `current()` is false as soon as one of them was written in place or moved, the
+    module tree changed (STRUCT_EPOCH), or a raw-pointer writer ran (STATE_EPOCH)."""
+
+    def __init__(self, dims: Sequence[ChainDim], sources: Sequence[Tensor]):
+        self.n = len(dims)
+        self.dev = dims[0].in_up.device
+        self.arr = (_ffi.ChainDescF32 * self.n)()
+        self.widths = []
+        self.keep = [(d.weights, d.biases, d.folds) for d in dims]
+        for D, d in zip(self.arr, dims):
+            _, F, H = _chain_shapes(d, paired=False)
+            self.widths.append((F, H))
+            D.F, D.H, D.ld_out, D.act = F, H, H, _act_code(d.act)
+            for s in range(5):
+                D.W[s], D.bias[s] = d.weights[s].data_ptr(), _ffi.ptr(d.biases[s])
+                D.scale[s], D.shift[s] = _ffi.ptr(d.folds[s][0]), _ffi.ptr(d.folds[s][1])
+        self.marks = _marks(sources)
+        self.epochs = (STATE_EPOCH, STRUCT_EPOCH)
+        self.fn = _ffi.lib().cwn_update_chain_f32
+
+    def current(self) -> bool:
+        return self.epochs == (STATE_EPOCH, STRUCT_EPOCH) and _marks_current(self.marks)
+
+    def run(self, ins: Sequence[Tuple[Tensor, Tensor]]) -> Optional[List[Tensor]]:
+        """None: these inputs are not what the launch takes (another width / dtype / device, rows that are not contiguous)
+        -- the caller then goes the long way, which says what is wrong."""
+        if len(ins) != self.n:
+            return None
+        outs = []
+        for D, (u, b), (F, H) in zip(self.arr, ins, self.widths):
+            for x in (u, b):
+                if (x.dim() != 2 or x.size(1) != F or x.dtype != torch.float32 or x.device != self.dev or (F > 1 and x.stride(1) != 1)
+                        or (x.size(0) > 1 and x.stride(0) < F)):
+                    return None
+            n = u.size(0)
+            if b.size(0) != n:
+                return None
+            out = torch.empty(n, H, dtype=torch.float32, device=self.dev)
+            outs.append(out)
+            D.in_up, D.in_b, D.out, D.n = u.data_ptr(), b.data_ptr(), out.data_ptr(), n
+            D.ld_up, D.ld_b = (u.stride(0), b.stride(0)) if n > 1 else (F, F)
+            D.m_dev = _ffi.dyn(n)
+        rc = self.fn(self.arr, self.n, _ffi.stream_ptr(self.dev))
+        if rc != 0:
+            _ffi.check(rc, 'cwn_update_chain_f32')
+        return outs
 
 
 # ------------------------------------------------------------------------------------------------

@@ -28,7 +28,7 @@
  *     cwn_layer_bwd_items_build_dev produce the per-batch tables on the device.
  *     Who checks "*m_dev <= capacity": cwn_gemm_f32 (both kernels), cwn_gemm_tn_f32, cwn_layernorm_*, cwn_dropout_f32,
  *     cwn_loss_f32 / cwn_loss_cols_f32, cwn_csr_long_rows, cwn_embedding_bwd_f32, cwn_embed_front_f32,
- *     cwn_embed_front_bwd_f32, cwn_oriented_layer_f32 / cwn_oriented_dz_f32 and cwn_target_head_f32 / _bwd_f32 CLAMP the count to the capacity (a larger count behaves as the capacity); cwn_dense_stage_f32 /
+ *     cwn_embed_front_bwd_f32, cwn_oriented_layer_f32 / cwn_oriented_dz_f32, cwn_target_head_f32 / _bwd_f32 and cwn_update_chain_f32 CLAMP the count to the capacity (a larger count behaves as the capacity); cwn_dense_stage_f32 /
  *     _ex / _bwd, cwn_bn_finalize_f32, cwn_norm_*, cwn_update_mlp_f32 / cwn_update_mlp3_f32 and cwn_aggregate_f32 / _f64 take
  *     the count AS IT IS -- there the caller's vouching is what keeps the stores inside the buffers (the collate guard,
  *     cwn_collate_guard, zeroes the counts of a batch beyond its capacities before any of them is read).
@@ -1255,6 +1255,61 @@ typedef struct cwn_chain_desc_f64 {
  * unknown act, scale without shift (or the reverse), a NULL in_up / in_b / out / W[i] with n > 0.  n == 0: the
  * dimension writes nothing. */
 int cwn_update_chain_f64(const cwn_chain_desc_f64* descs_host, int n_dims, cwn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The float32 update chain (csrc/cwn_chain_f32.hip): the same five Linear layers per dimension in float32, inference only,
+ * at ANY width 1 .. 128 and with any of the five activations, all dimensions of a layer in ONE launch.
+ *
+ * cwn_update_mlp_f32 is the fast form of this arithmetic at 64 / 128 with ReLU (a bf16 split on packed weights).  This
+ * launch is the one for everything else -- hidden 48 of the 100k-parameter "small" scripts (exp/scripts/cwn-zinc-small.sh
+ * and its four siblings), the 16 / 32 of the TU tuning grid, a first layer over raw features, a model built with elu /
+ * tanh / sigmoid / id -- where the networks otherwise run as one grouped cwn_gemm_f32 launch per stage with the hidden
+ * activations in memory, or as torch modules.
+ *
+ *     u   = act(aff1(act(aff0(in_up W[0]^T + bias[0])) W[1]^T + bias[1]))        aff_i(z) = z * scale[i] + shift[i]
+ *     b   = act(aff3(act(aff2(in_b  W[2]^T + bias[2])) W[3]^T + bias[3]))
+ *     out = act(aff4(cat(u, b) W[4]^T + bias[4]))
+ *
+ *   - in_up / in_b [n, F] with row strides ld_up / ld_b >= F; W[0], W[2] [H, F], W[1], W[3] [H, H], W[4] [H, 2H], each
+ *     row-major and contiguous as torch.nn.Linear holds them; bias[i] / scale[i] / shift[i] [H], each NULL-able on its own
+ *     (an absent operand is skipped, not multiplied by one); act: one CWN_ACT_* code for all five stages; out [n, H] with
+ *     row stride ld_out >= H.  out must not overlap an input or a weight (the caller vouches: not checked).
+ *   - 1 <= F, H <= CWN_CHAIN_F32_MAX_WIDTH, any value; 1 <= n_dims <= CWN_CHAIN_F32_MAX_DIMS; a dimension with n == 0 is
+ *     skipped and none of its pointers is looked at.
+ *   - a workgroup of 256 threads owns CWN_CHAIN_F32_TM rows of one dimension; the tiles of all dimensions form one grid.
+ *     Everything between the two inputs and out stays in LDS: three panels of 32 x 132 floats.
+ *   - arithmetic: every product runs on v_mfma_f32_16x16x4_f32, exact fp32 -- no bf16 split, so non-finite inputs
+ *     propagate as in torch (NaN-propagating ReLU, the library's own expm1f / tanhf / expf).  An output element is one
+ *     chain of products whose k order depends on (F, H) alone: a row's result is a function of that row and the weights
+ *     only -- the same bits alone or anywhere in any batch, in any dimension slot of the launch.
+ *   - m_dev: see "Conventions" (n is the capacity); the count is CLAMPED to [0, n].  Rows in [*m_dev, n) are never written
+ *     and their rows of in_up / in_b are never read.
+ *   - no allocation, no synchronisation, no atomics.
+ * CWN_ERR_BAD_ARG: descs NULL, n_dims outside the range, n < 0, F or H outside [1, 128], an unknown act, and for n > 0 a
+ * NULL in_up / in_b / out / W[i] or a stride below its width.  CWN_ERR_ALIGN (n > 0): a pointer off 4 bytes (m_dev: 8).
+ * CWN_ERR_TOO_LARGE: INT32_MAX tiles or more.  All checks precede the first HIP call.
+ * Not here: CIN++ (three or four branches: cwn_update_mlp3_f32 or the grouped launches), training, widths above 128, the
+ * compiled torch binding (ctypes only), float64 (cwn_update_chain_f64 above).
+ * ------------------------------------------------------------------------------------------ */
+#define CWN_CHAIN_F32_MAX_DIMS 4        /* dimensions of one cwn_update_chain_f32 launch */
+#define CWN_CHAIN_F32_MAX_WIDTH 128     /* F and H of a dimension */
+#define CWN_CHAIN_F32_TM 32             /* rows a workgroup owns */
+
+typedef struct cwn_chain_desc_f32 {
+    const float* in_up;        /* [n, F] row stride ld_up */
+    const float* in_b;         /* [n, F] row stride ld_b */
+    float* out;                /* [n, H] row stride ld_out */
+    const float* W[5];
+    const float* bias[5];      /* [H] or NULL, each */
+    const float* scale[5];
+    const float* shift[5];
+    int64_t n, ld_up, ld_b, ld_out;
+    int32_t F, H;
+    int32_t act;               /* CWN_ACT_*, the one activation of all five stages */
+    int32_t reserved;
+    const int64_t* m_dev;      /* or NULL: rows that exist (n = capacity) */
+} cwn_chain_desc_f32;
+int cwn_update_chain_f32(const cwn_chain_desc_f32* descs_host, int n, cwn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * The activated two-operand message (csrc/cwn_aggregate_act.hip), float32 and float64, inference:
