@@ -25,7 +25,7 @@ EXPORTS = ('cwn_abi_version', 'cwn_error_string', 'cwn_target_arch', 'cwn_csr_wo
            'cwn_layernorm_act_f32', 'cwn_layernorm_bwd_workspace_bytes', 'cwn_layernorm_bwd_f32',
            'cwn_oriented_layer_f32', 'cwn_oriented_dz_f32',
            'cwn_target_head_f32', 'cwn_target_head_bwd_f32', 'cwn_target_head_bwd_workspace_bytes',
-           'cwn_linear_many_f64', 'cwn_update_chain_f64', 'cwn_update_chain_f32',
+           'cwn_linear_many_f64', 'cwn_update_chain_f64', 'cwn_update_chain_f32', 'cwn_linear_stats_f32',
            'cwn_aggregate_act_f32', 'cwn_aggregate_act_f64',
            'cwn_embed_pool_f32', 'cwn_embed_pool_f64', 'cwn_agnostic_head_f32', 'cwn_agnostic_head_f64',
            'cwn_gin_layer_f32', 'cwn_gine_layer_f32',
@@ -438,6 +438,8 @@ def lib():
     L.cwn_aggregate_f64.argtypes = [C.POINTER(AggDesc), C.c_int, C.c_void_p]
     L.cwn_gemm_f32.restype = C.c_int
     L.cwn_gemm_f32.argtypes = [C.POINTER(GemmDesc), C.c_int, C.c_void_p]
+    L.cwn_linear_stats_f32.restype = C.c_int
+    L.cwn_linear_stats_f32.argtypes = [C.POINTER(GemmDesc), C.c_int, C.c_void_p]
     L.cwn_layer_fused_f32.restype = C.c_int
     L.cwn_layer_fused_f32.argtypes = [C.POINTER(LayerDim), C.c_int, C.c_int32, C.POINTER(LayerPlan), C.c_int32,
                                       C.c_void_p, C.c_void_p]
@@ -758,6 +760,16 @@ def gemm(descs: Sequence[GemmDesc], device) -> None:
         chunk = descs[i:i + MAX_DESCS]
         arr = (GemmDesc * len(chunk))(*chunk)
         check(L.cwn_gemm_f32(arr, len(chunk), s), 'cwn_gemm_f32')
+
+
+def linear_stats(descs: Sequence[GemmDesc], device) -> None:
+    """cwn_linear_stats_f32: one launch for up to MAX_DESCS Linear stages whose band statistics count the rows that exist."""
+    L = lib()
+    s = stream_ptr(device)
+    for i in range(0, len(descs), MAX_DESCS):
+        chunk = descs[i:i + MAX_DESCS]
+        arr = (GemmDesc * len(chunk))(*chunk)
+        check(L.cwn_linear_stats_f32(arr, len(chunk), s), 'cwn_linear_stats_f32')
 
 
 def gemm_would_split(descs: Sequence[GemmDesc]) -> bool:

@@ -14,6 +14,11 @@ Forward, per layer (all dimensions and both branches in each launch):
 `prologue` is the BatchNorm apply + ReLU of the producing stage, done while the tile is staged, so
 no normalised activation between two Linear layers is ever written to memory.
 
+Which launch a stage takes: cwn_dense_stage_f32 at widths 64 / 128 (ops.run_stage); else, inside a static slot -- rows with a
+device-side count, which cwn_gemm_f32 refuses next to the statistics -- cwn_linear_stats_f32 at any width up to 128
+(ops.run_linear_stats); else cwn_gemm_f32.  In the backward the lazy form below keeps the count on cwn_dense_stage_bwd_f32
+only: under a count every other stage takes reduce + apply and a plain transposed-weight GEMM.
+
 Backward, per stage from the last to the first:
 
     cwn_norm_bwd_reduce   s1 = sum dyh, s2 = sum dyh * xhat          (= d beta, d gamma)
@@ -252,7 +257,10 @@ class _DenseTrain(torch.autograd.Function):
             if res is None:
                 if live:
                     raise RuntimeError('dense_train: a stage left cwn_dense_stage_f32 in live-BatchNorm mode (set CWN_LIVE_BN=0)')
-                res = ops.run_gemm(gemms, dev)
+                # (a static slot at a width the stage kernel does not hold: the band statistics over the rows that exist)
+                res = ops.run_linear_stats(gemms, dev)
+                if res is None:
+                    res = ops.run_gemm(gemms, dev)
             return res
 
         Z = [[[None] * depth for _ in range(nb)] for _ in range(nd)]   # Z[dim][branch][stage]
@@ -425,14 +433,21 @@ class _DenseTrain(torch.autograd.Function):
             return (FUSED_NORM_APPLY and not fused_norm and z.size(1) in (64, 128) and z.numel() > 0
                     and all(t.data_ptr() % 16 == 0 and t.stride(0) % 4 == 0 and t.stride(1) == 1 for t in (dy, z)))
 
-        def norm_backward(items, lazy=False):
+        def counted(z):
+            return z.numel() > 0 and _ffi.dyn(z.size(0)) is not None
+
+        def norm_backward(items, lazy=False, stage_ok=False):
             """items: (stage, dy, z) -> dz list; BatchNorm stages reduce first.  The sums are handed on to gamma.grad /
             beta.grad by the apply launch itself where those buffers exist (`norm_targets`).  `lazy`: only the reduce is
             launched and every entry comes back as (dz, bnb) -- dz still EMPTY, bnb the cwn_gemm_bnb extension with which
-            the consuming transposed-weight GEMM forms (and writes) it in its prologue; bnb None = dz is complete."""
+            the consuming transposed-weight GEMM forms (and writes) it in its prologue; bnb None = dz is complete.
+            `stage_ok`: ops.run_stage_bwd takes every product that consumes these dz.  Under a device-side row count (a static
+            slot) only that launch has the lazy form -- cwn_gemm_f32 refuses a count next to its bnb prologue -- so without it
+            the stage takes reduce + apply and a plain transposed-weight GEMM, which all carry the count."""
             red, app, outs = [], [], []
             direct, scratch = [], []
             lazy = lazy and all(bnb_ok(dy, z) for _, dy, z in items if z.numel())
+            lazy = lazy and (stage_ok or not any(counted(z) for _, _, z in items))
             for st, dy, z in items:
                 dz = torch.empty(z.shape, dtype=torch.float32, device=dev)
                 if not z.numel():
@@ -535,7 +550,11 @@ class _DenseTrain(torch.autograd.Function):
                         filled.add(id(plan.cb[i]))
                         ops.BN_BWD_FUSED[0] += 1
                         ctx.bn_ext[i] = None            # (one shot: a second backward over this forward reduces by itself)
-            pend3 = norm_backward([(plan.cb[i], dH_in[i], Z3[i]) for i in range(nd)], lazy=True)
+            n_pairs = (nb + 1) // 2
+            stage3 = nd * n_pairs <= _ffi.MAX_DESCS and all(
+                ops.stage_bwd_takes(P[id(plan.cb[i])][0], int(Z3[i].size(1)), nb)
+                and all(ch[-1].lin.out_features == Z3[i].size(1) for ch in plan.chains[i]) for i in range(nd))
+            pend3 = norm_backward([(plan.cb[i], dH_in[i], Z3[i]) for i in range(nd)], lazy=True, stage_ok=stage3)
             lazy3 = bool(pend3) and isinstance(pend3[0], tuple)
             dZ3 = [p[0] for p in pend3] if lazy3 else pend3
             tn, nn = [], []
@@ -624,7 +643,8 @@ class _DenseTrain(torch.autograd.Function):
             #  over 1-wide features -- REDDIT-BINARY's constant vertex feature, mp/models.py:112-260 -- takes the apply launch)
             wide = all(P[id(chain[s])][0].size(1) % 4 == 0 and P[id(chain[s])][0].stride(0) % 4 == 0
                        for i in range(nd) for chain in plan.chains[i])
-            pend = norm_backward(items, lazy=wide)
+            stage_s = nd * nb <= _ffi.MAX_DESCS and all(ops.stage_bwd_takes(P[id(st_)][0], int(z_.size(1))) for st_, _, z_ in items)
+            pend = norm_backward(items, lazy=wide, stage_ok=stage_s)
             lazy_s = bool(pend) and isinstance(pend[0], tuple)
             dZ = [p[0] for p in pend] if lazy_s else pend
             tn, nn, k = [], [], 0

@@ -3666,6 +3666,74 @@ def run_stage(gemms: Sequence['Gemm'], device) -> Optional[List[Tensor]]:
     return outs
 
 
+LINEAR_STATS_MAX_N, LINEAR_STATS_MAX_K = 128, 256      # cwn_linear_stats_f32: N, K + K2
+
+
+def run_linear_stats(gemms: Sequence['Gemm'], device) -> Optional[List[Tensor]]:
+    """The grouped launch `gemms` on cwn_linear_stats_f32 (a Linear stage whose band statistics count the rows that EXIST, at
+    any width up to 128), or None when it does not apply and the caller runs cwn_gemm_f32: it takes a launch in which at
+    least one product carries a device-side row count together with `col_stats` -- what cwn_gemm_f32 refuses -- and nothing
+    needs what this entry point refuses (w_trans, bnb, an output affine or ReLU, add_out, a live BatchNorm record, a third
+    K-block, widths beyond its limits).  Outside a static slot no row has a device-side count: None, always."""
+    if not gemms or not _ffi.DYN_ROWS or len(gemms) > _ffi.MAX_DESCS:
+        return None
+    if not any(g.col_stats is not None and _ffi.dyn(g.X.size(0)) is not None for g in gemms):
+        return None
+    for g in gemms:
+        if (g.relu or g.out_scale is not None or g.out_shift is not None or g.w_trans or g.bnb is not None or g.add_out
+                or g.stat_slots is not None or g.in_bn is not None or g.in_bn2 is not None or g.more or g.debug
+                or g.w_packed is not None):
+            return None
+        K = int(g.X.size(1)) + (int(g.X2.size(1)) if g.X2 is not None else 0)
+        if g.W.dim() != 2 or not (1 <= g.W.size(0) <= LINEAR_STATS_MAX_N) or not (1 <= int(g.X.size(1)) and K <= LINEAR_STATS_MAX_K):
+            return None
+        cs = g.col_stats
+        if cs is not None and (cs.dtype != torch.float64 or tuple(cs.shape) != (2, stat_rows(g.X.size(0)), g.W.size(0))
+                               or not cs.is_contiguous()):
+            return None
+    outs, descs, keep = [], [], []
+    for g in gemms:
+        g.X, g.W = _rowmajor(g.X, 'X'), _rowmajor(g.W, 'W')
+        if g.X2 is not None:
+            g.X2 = _rowmajor(g.X2, 'X2')
+        cons = {k: (None if getattr(g, k) is None else _f32c(getattr(g, k), k)) for k in ('bias', 'in_scale', 'in_shift', 'in_scale2', 'in_shift2')}
+        keep.append(cons)
+        X, X2, W = g.X, g.X2, g.W
+        M, N, K1 = int(X.size(0)), int(W.size(0)), int(X.size(1))
+        K2 = int(X2.size(1)) if X2 is not None else 0
+        if g.w_col0 is not None:
+            if W.size(1) < g.w_col0 + K1 + K2:
+                raise ValueError('w_col0 selects columns of an untransposed weight')
+        elif W.size(1) != K1 + K2:
+            raise ValueError(f'weight has {W.size(1)} input columns, operands have {K1 + K2}')
+        if X2 is not None and X2.size(0) != M:
+            raise ValueError('X and X2 must have the same number of rows')
+        Y = g.out if g.out is not None else torch.empty(M, N, dtype=torch.float32, device=device)
+        outs.append(Y)
+        if not Y.numel():
+            continue
+        cs = g.col_stats
+        ld = lambda t, w: int(t.stride(0)) if t.size(0) > 1 else max(w, 1)
+        descs.append(_ffi.GemmDesc(
+            X=X.data_ptr(), X2=_ffi.ptr(X2), W=W.data_ptr() + 4 * (g.w_col0 or 0), bias=_ffi.ptr(cons['bias']),
+            in_scale=_ffi.ptr(cons['in_scale']), in_shift=_ffi.ptr(cons['in_shift']),
+            in_scale2=_ffi.ptr(cons['in_scale2']), in_shift2=_ffi.ptr(cons['in_shift2']),
+            col_sum=None if cs is None else cs[0].data_ptr(), col_sumsq=None if cs is None else cs[1].data_ptr(),
+            Y=Y.data_ptr(), M=M, ldx=ld(X, K1), ldx2=ld(X2, K2) if X2 is not None else 0, ldw=ld(W, int(W.size(1))), ldy=ld(Y, N),
+            N=N, K=K1, K2=K2, relu=0, in_relu=int(g.in_relu) & (3 if X2 is not None else 1), w_trans=0, bnb=None,
+            m_dev=_ffi.dyn(M), flags=_ffi.GEMM_EXACT))
+    if descs:
+        _ffi.linear_stats(descs, device)
+    return outs
+
+
+def stage_bwd_takes(W: Tensor, F: int, blocks: int = 1) -> bool:
+    """Would run_stage_bwd take the input-gradient product of a stage of width F whose weight is `blocks` [F, F] blocks side
+    by side?  (The lazy BatchNorm-backward form -- cwn_gemm_bnb -- has the device-side row count on that launch only.)"""
+    return bool(STAGE_KERNEL and F in (64, 128) and W.dim() == 2 and tuple(W.shape) == (F, blocks * F)
+                and all(packed_stage_block(W, c * F, transposed=True) is not None for c in range(blocks)))
+
+
 def layer_fused(dims: Sequence[LayerDim], table, csr_mode: int = 0) -> List[Tensor]:
     """[out_up_0, out_b_0, out_up_1, out_b_1, ...] ([out_up_d, out_down_d, out_b_d] for a dimension with `want_down`); no
     autograd (inference path).  `table` is one of the

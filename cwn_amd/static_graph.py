@@ -180,6 +180,26 @@ def refuse_unsupported_layers(model: torch.nn.Module, who: str, static: Optional
     if bad:
         raise NotImplementedError(f'{who}: {", ".join(bad)} layers are not served by this static batch ({why}); or use collated '
                                   'batches with model(batch) / TrainStep')
+    from .layers import SparseCINConv
+    if static is not None and static.mode == 'blocked':
+        # the blocked layer kernels exist at feature widths 64 and 128: at any other width a layer would leave them for its
+        # CSR path, which a 'blocked' static batch does not carry
+        widths = sorted({int(lvl.up_msg_size) for m in model.modules() if isinstance(m, SparseCINConv) for lvl in m.mp_levels}
+                        - {64, 128})
+        if widths:
+            raise NotImplementedError(f"{who}: a static batch in mode 'blocked' serves layers of feature width 64 or 128, this model "
+                                      f"has {widths}: build the StaticBatch with mode='csr' (any width up to 128)")
+    if static is not None and static.mode == 'csr' and training:
+        # A CIN++ layer at a width other than 64 / 128 has no combine stage on the kernels (dense_train: its plan comes without
+        # one): combine_nn runs as torch modules, and a torch BatchNorm1d in training mode would take its statistics over the
+        # capacity rows of a slot -- stale rows of an earlier batch.
+        bad = sorted({f'CINppConv(width {int(lvl.up_msg_size)})' for m in model.modules() if isinstance(m, CINppConv)
+                      for lvl in m.mp_levels if int(lvl.up_msg_size) not in (64, 128)
+                      and any(isinstance(x, torch.nn.modules.batchnorm._BatchNorm) for x in lvl.combine_nn.modules())})
+        if bad:
+            raise NotImplementedError(f'{who}: {", ".join(bad)} is not served in training by a static batch: at a width other than '
+                                      '64 / 128 its combine network runs as torch modules, whose BatchNorm(train) statistics would '
+                                      'be taken over the capacity rows of a slot; use collated batches with TrainStep')
 
 
 class StaticForward:

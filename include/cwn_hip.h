@@ -28,7 +28,7 @@
  *     cwn_layer_bwd_items_build_dev produce the per-batch tables on the device.
  *     Who checks "*m_dev <= capacity": cwn_gemm_f32 (both kernels), cwn_gemm_tn_f32, cwn_layernorm_*, cwn_dropout_f32,
  *     cwn_loss_f32 / cwn_loss_cols_f32, cwn_csr_long_rows, cwn_embedding_bwd_f32, cwn_embed_front_f32,
- *     cwn_embed_front_bwd_f32, cwn_oriented_layer_f32 / cwn_oriented_dz_f32, cwn_target_head_f32 / _bwd_f32 and cwn_update_chain_f32 CLAMP the count to the capacity (a larger count behaves as the capacity); cwn_dense_stage_f32 /
+ *     cwn_embed_front_bwd_f32, cwn_oriented_layer_f32 / cwn_oriented_dz_f32, cwn_target_head_f32 / _bwd_f32, cwn_update_chain_f32 and cwn_linear_stats_f32 CLAMP the count to the capacity (a larger count behaves as the capacity); cwn_dense_stage_f32 /
  *     _ex / _bwd, cwn_bn_finalize_f32, cwn_norm_*, cwn_update_mlp_f32 / cwn_update_mlp3_f32 and cwn_aggregate_f32 / _f64 take
  *     the count AS IT IS -- there the caller's vouching is what keeps the stores inside the buffers (the collate guard,
  *     cwn_collate_guard, zeroes the counts of a batch beyond its capacities before any of them is read).
@@ -925,6 +925,36 @@ int cwn_gemm_f32(const cwn_gemm_desc* descs_host, int n, cwn_stream_t stream);
  * give NaN.  1 when cwn_gemm_f32 would run these descriptors on that path, else 0 (a pure function
  * of its arguments). */
 int cwn_gemm_would_split(const cwn_gemm_desc* descs_host, int n);
+
+/* ------------------------------------------------------------------------------------------
+ * A Linear stage with band statistics under a row count (csrc/cwn_linear_stats.hip):
+ *
+ *     Y = prologue([X | X2]) . W^T + bias          up to CWN_MAX_DESCS products per launch
+ *
+ * The forward of a Linear (K -> N) or of combine_nn's Linear (K + K2 -> N) in TRAINING mode at any width
+ * 1 <= N <= 128, K >= 1, K + K2 <= 256, any row stride and alignment (16-byte accesses where pointer, stride
+ * and widths allow, element by element otherwise; K need not be a multiple of 4 next to X2) -- what
+ * cwn_gemm_f32 refuses (m_dev next to col_sum / col_sumsq) and cwn_dense_stage_f32 serves at 64 / 128 only.
+ * It reads cwn_gemm_desc unchanged:
+ *   prologue:  cwn_gemm_f32's (in_scale / in_shift for X, in_scale2 / in_shift2 for X2, in_relu bits 0 / 1);
+ *   rows:      live = clamp(*m_dev, 0, M), or M when m_dev is NULL.  Rows at or beyond `live` are neither
+ *              stored nor counted (they may be LOADED -- they lie inside the buffers -- and may hold NaN:
+ *              nothing of them reaches a live row or a statistic); live == 0 writes nothing;
+ *   col_sum / col_sumsq [CWN_STAT_ROWS(M), N] fp64, both or neither (NULL: a stage with an identity norm):
+ *              band b = the column sums of y, y^2 over the rows [32b, 32b + 32) below `live`; plain stores, no
+ *              atomics, nothing to zero; bands at or beyond CWN_STAT_ROWS(live) are not written -- what
+ *              cwn_bn_finalize_f32 reads under the same count.
+ * Exact fp32 on v_mfma_f32_16x16x4_f32 in cwn_gemm_f32's k order (slabs of 16 ascending, one accumulator chain
+ * per element): with m_dev NULL, Y and every band equal bit for bit what cwn_gemm_f32 writes for the same
+ * descriptor (which takes its exact kernel whenever statistics are asked for), and a live row's bits depend on
+ * neither the count nor the rows behind it.
+ * CWN_ERR_BAD_ARG, before any device call: n < 0, n > CWN_MAX_DESCS, descs NULL with n > 0; w_trans, bnb,
+ * out_scale / out_shift, relu, a flag other than CWN_GEMM_EXACT; one of col_sum / col_sumsq (or of a
+ * scale / shift pair) without the other; N, K, K2 outside the limits; X2 without K2 or K2 without X2; M < 0,
+ * a row stride below its width, a NULL operand with M > 0.  CWN_ERR_ALIGN: a pointer not aligned to its
+ * element.  n == 0 and launches whose every M is 0 return CWN_OK without a device.
+ * ------------------------------------------------------------------------------------------ */
+int cwn_linear_stats_f32(const cwn_gemm_desc* descs_host, int n, cwn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Training-mode pieces of the dense networks (torch.nn.BatchNorm1d in train mode + ReLU between
