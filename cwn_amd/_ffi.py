@@ -26,6 +26,7 @@ EXPORTS = ('cwn_abi_version', 'cwn_error_string', 'cwn_target_arch', 'cwn_csr_wo
            'cwn_oriented_layer_f32', 'cwn_oriented_dz_f32',
            'cwn_target_head_f32', 'cwn_target_head_bwd_f32', 'cwn_target_head_bwd_workspace_bytes',
            'cwn_linear_many_f64', 'cwn_update_chain_f64', 'cwn_update_chain_f32', 'cwn_linear_stats_f32',
+           'cwn_linear_wide_f32',
            'cwn_aggregate_act_f32', 'cwn_aggregate_act_f64',
            'cwn_embed_pool_f32', 'cwn_embed_pool_f64', 'cwn_agnostic_head_f32', 'cwn_agnostic_head_f64',
            'cwn_gin_layer_f32', 'cwn_gine_layer_f32',
@@ -128,6 +129,16 @@ class GemmDesc(C.Structure):
                 ('w_trans', C.c_int32), ('flags', C.c_int32), ('pad_', C.c_int32), ('bnb', C.POINTER(GemmBnb)),
                 ('m_dev', C.c_void_p)]
 
+
+class LinearWideDesc(C.Structure):
+    """cwn_linear_wide_desc (include/cwn_hip.h)."""
+    _fields_ = [('X', C.c_void_p), ('X2', C.c_void_p), ('W', C.c_void_p), ('bias', C.c_void_p), ('Y', C.c_void_p),
+                ('m_dev', C.c_void_p), ('M', C.c_int64), ('ldx', C.c_int64), ('ldx2', C.c_int64), ('ldw', C.c_int64),
+                ('ldy', C.c_int64), ('N', C.c_int32), ('K', C.c_int32), ('K2', C.c_int32), ('w_trans', C.c_int32)]
+
+
+LINEAR_WIDE_MAX_N = 256        # = CWN_LINEAR_WIDE_MAX_N
+LINEAR_WIDE_MAX_K = 512        # = CWN_LINEAR_WIDE_MAX_K (K + K2)
 
 GEMM_EXACT = 1
 GEMM_W_PACKED = 2         # = CWN_GEMM_W_PACKED
@@ -440,6 +451,8 @@ def lib():
     L.cwn_gemm_f32.argtypes = [C.POINTER(GemmDesc), C.c_int, C.c_void_p]
     L.cwn_linear_stats_f32.restype = C.c_int
     L.cwn_linear_stats_f32.argtypes = [C.POINTER(GemmDesc), C.c_int, C.c_void_p]
+    L.cwn_linear_wide_f32.restype = C.c_int
+    L.cwn_linear_wide_f32.argtypes = [C.POINTER(LinearWideDesc), C.c_int, C.c_void_p]
     L.cwn_layer_fused_f32.restype = C.c_int
     L.cwn_layer_fused_f32.argtypes = [C.POINTER(LayerDim), C.c_int, C.c_int32, C.POINTER(LayerPlan), C.c_int32,
                                       C.c_void_p, C.c_void_p]
@@ -770,6 +783,18 @@ def linear_stats(descs: Sequence[GemmDesc], device) -> None:
         chunk = descs[i:i + MAX_DESCS]
         arr = (GemmDesc * len(chunk))(*chunk)
         check(L.cwn_linear_stats_f32(arr, len(chunk), s), 'cwn_linear_stats_f32')
+
+
+def linear_wide(descs: Sequence['LinearWideDesc'], device) -> None:
+    """cwn_linear_wide_f32: one launch for up to MAX_DESCS products of one weight layout, K streamed (K + K2 <= 512,
+    N <= 256); a descriptor whose row count is the capacity of a static batch gets the device-side count."""
+    L = lib()
+    s = stream_ptr(device)
+    _set_dyn(descs)
+    for i in range(0, len(descs), MAX_DESCS):
+        chunk = descs[i:i + MAX_DESCS]
+        arr = (LinearWideDesc * len(chunk))(*chunk)
+        check(L.cwn_linear_wide_f32(arr, len(chunk), s), 'cwn_linear_wide_f32')
 
 
 def gemm_would_split(descs: Sequence[GemmDesc]) -> bool:

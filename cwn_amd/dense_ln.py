@@ -47,6 +47,22 @@ def supported(chains, combine) -> bool:
     return all(lin.in_features <= ops.GEMM_MAX_K for st in flat for lin, _ in st)
 
 
+def counted(chains, combine) -> bool:
+    """Does every launch `run` makes for these networks carry the device-side row count of a static batch -- in the
+    backward too?  True when `supported` accepts them and the combine product is a grouped GEMM or ops.linear_wide.  The
+    torch branch (three / four branches: CIN++; a combine beyond cwn_linear_wide_f32) sums its weight gradient over the
+    CAPACITY rows of a slot, and so do the torch modules a layer runs when `supported` declines or FUSED_LN is off."""
+    if not FUSED_LN or not supported(chains, combine) or len(chains[0]) != 2:
+        return False
+    for branches, cb in zip(chains, combine):
+        lin = cb[0][0]
+        k1, k2 = (st[-1][0].out_features for st in branches)
+        if k1 + k2 != lin.in_features or not ((lin.in_features <= ops.GEMM_MAX_K and k1 % 4 == 0)
+                                              or ops.linear_wide_applies(k1, k2, lin.out_features)):
+            return False
+    return True
+
+
 def run(chains, combine, outs: Sequence[Tensor]) -> List[Tensor]:
     """The networks `supported` accepted on `outs` ([dim][branch] flattened: the aggregated streams of every dimension);
     returns one matrix per dimension."""
@@ -57,11 +73,16 @@ def run(chains, combine, outs: Sequence[Tensor]) -> List[Tensor]:
         ys = ops.gemm_many([ops.Gemm(X=h, W=st[s][0].weight, bias=st[s][0].bias) for h, st in zip(hs, flat)])
         hs = ops.layer_norm_act_many(ys, [st[s][1] for st in flat], relu=True)
     lins = [cb[0][0] for cb in combine]
-    if nb == 2 and all(lin.in_features <= ops.GEMM_MAX_K for lin in lins):
-        # torch.cat folded into the K-concatenation of the GEMM
+    if nb == 2 and all(lin.in_features <= ops.GEMM_MAX_K and hs[2 * i].size(1) % 4 == 0 for i, lin in enumerate(lins)):
+        # torch.cat folded into the K-concatenation of the GEMM (cwn_gemm_f32 wants K % 4 == 0 next to X2)
         ys = ops.gemm_many([ops.Gemm(X=hs[2 * i], X2=hs[2 * i + 1], W=lin.weight, bias=lin.bias) for i, lin in enumerate(lins)])
+    elif nb == 2 and all(ops.linear_wide_applies(hs[2 * i].size(1), hs[2 * i + 1].size(1), lin.out_features)
+                         for i, lin in enumerate(lins)):
+        # wider than the GEMM's K (width 160: 320) or a width that is no multiple of 4: K streamed (csrc/cwn_linear_wide.hip),
+        # under the row count of a static batch
+        ys = [ops.linear_wide(hs[2 * i], hs[2 * i + 1], lin.weight, lin.bias) for i, lin in enumerate(lins)]
     else:
-        # wider than the GEMM's K (width 160: 320) or three / four branches (CIN++)
+        # three / four branches (CIN++), or beyond cwn_linear_wide_f32 (N > 256, K + K2 > 512): the torch modules
         ys = [torch.nn.functional.linear(torch.cat(hs[nb * i: nb * (i + 1)], dim=-1), lin.weight, lin.bias)
               for i, lin in enumerate(lins)]
     return ops.layer_norm_act_many(ys, [cb[0][1] for cb in combine], relu=True)

@@ -1822,6 +1822,128 @@ def gemm_many(gemms: Sequence[Gemm]) -> List[Tensor]:
 
 
 # ------------------------------------------------------------------------------------------------
+# a Linear product beyond GEMM_MAX_K, K streamed, under a device-side row count (csrc/cwn_linear_wide.hip)
+# ------------------------------------------------------------------------------------------------
+_WIDE_ROWS = dict(dtypes=(torch.float32,), what='linear_wide: ',
+                  hint='cwn_linear_wide_f32 computes in fp32 only (float64 products run on torch.nn.functional.linear)')
+
+
+def linear_wide_applies(K: int, K2: int, N: int) -> bool:
+    """The shapes cwn_linear_wide_f32 takes: 1 <= N <= 256, K >= 1, K2 >= 0, K + K2 <= 512."""
+    return 1 <= N <= _ffi.LINEAR_WIDE_MAX_N and K >= 1 and K2 >= 0 and K + K2 <= _ffi.LINEAR_WIDE_MAX_K
+
+
+def _wide_desc(X: Tensor, X2: Optional[Tensor], W: Tensor, bias: Optional[Tensor], Y: Tensor, w_trans: bool) -> '_ffi.LinearWideDesc':
+    return _ffi.LinearWideDesc(X=X.data_ptr(), X2=_ffi.ptr(X2), W=W.data_ptr(), bias=_ffi.ptr(bias), Y=Y.data_ptr(),
+                               M=X.size(0), ldx=_ld(X), ldx2=0 if X2 is None else _ld(X2), ldw=_ld(W), ldy=_ld(Y),
+                               N=Y.size(1), K=X.size(1), K2=0 if X2 is None else X2.size(1), w_trans=int(w_trans))
+
+
+def _wide_operands(X, X2, weight, bias):
+    for t, name in ((X, 'X'), (X2, 'X2'), (weight, 'weight'), (bias, 'bias')):      # every dtype before the first device
+        if t is not None:
+            _operand_dtype(t, name, _WIDE_ROWS['dtypes'], _WIDE_ROWS['what'], _WIDE_ROWS['hint'])
+    X = _rows_operand(X, 'X', 2, **_WIDE_ROWS)
+    X2 = _rows_operand(X2, 'X2', 2, **_WIDE_ROWS)
+    weight = _rows_operand(weight, 'weight', 2, **_WIDE_ROWS)
+    bias = _rows_operand(bias, 'bias', 1, **_WIDE_ROWS)
+    if X is None or weight is None:
+        raise TypeError('linear_wide: X and weight are required')
+    K, K2, N = X.size(1), 0 if X2 is None else X2.size(1), weight.size(0)
+    if weight.size(1) != K + K2:
+        raise ValueError(f'linear_wide: weight has {weight.size(1)} input columns, the operands have {K + K2}')
+    if X2 is not None and (X2.size(0) != X.size(0) or K2 == 0):
+        raise ValueError('linear_wide: X and X2 must have the same number of rows, and X2 at least one column')
+    if bias is not None and bias.numel() != N:
+        raise ValueError(f'linear_wide: bias has {bias.numel()} entries, weight {N} rows')
+    if not linear_wide_applies(K, K2, N):
+        raise ValueError(f'linear_wide: cwn_linear_wide_f32 takes 1 <= N <= {_ffi.LINEAR_WIDE_MAX_N}, K >= 1 and K + K2 <= '
+                         f'{_ffi.LINEAR_WIDE_MAX_K} (got N = {N}, K = {K}, K2 = {K2})')
+    return X, X2, weight, bias
+
+
+class _LinearWide(torch.autograd.Function):
+    """Forward: one cwn_linear_wide_f32 launch.  Backward: dX / dX2 = g W[:, :K] / g W[:, K:] as one launch of the transposed
+    form (the layer's own weight, no copy), dW / db one cwn_gemm_tn_f32 launch; all under the row count of _ffi.dyn."""
+
+    @staticmethod
+    def forward(ctx, X, X2, weight, bias):
+        Y = torch.empty(X.size(0), weight.size(0), dtype=torch.float32, device=X.device)
+        if Y.numel():
+            _ffi.linear_wide([_wide_desc(X, X2, weight, bias, Y, False)], X.device)
+        ctx.has_bias = bias is not None
+        ctx.params = (weight, bias)                 # (the Parameters: their .grad is the target inside accumulate_into_grad())
+        ctx.save_for_backward(X, X2, weight)
+        return Y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        X, X2, W = ctx.saved_tensors
+        weight_p, bias_p = ctx.params
+        nX, nX2, nW, nb = ctx.needs_input_grad
+        dev, K, N = X.device, X.size(1), W.size(0)
+        K2 = 0 if X2 is None else X2.size(1)
+        g = _rowmajor(g, 'grad')
+        dX = dX2 = dW = db = None
+        descs = []
+        CN = _ffi.LINEAR_WIDE_MAX_N                 # (the transposed form's N is an input width: column blocks of at most 256)
+        if nX:
+            dX = torch.empty(X.size(0), K, dtype=torch.float32, device=dev)
+            descs += [_wide_desc(g, None, W[:, c:min(c + CN, K)], None, dX[:, c:min(c + CN, K)], True) for c in range(0, K, CN)]
+        if nX2 and X2 is not None:
+            dX2 = torch.empty(X.size(0), K2, dtype=torch.float32, device=dev)
+            descs += [_wide_desc(g, None, W[:, K + c:K + min(c + CN, K2)], None, dX2[:, c:min(c + CN, K2)], True)
+                      for c in range(0, K2, CN)]
+        if descs and g.size(0):
+            _ffi.linear_wide(descs, dev)
+        want_b = nb and ctx.has_bias
+        if nW or want_b:
+            tw = _grad_target(weight_p) if nW else None
+            tb = _grad_target(bias_p) if want_b else None
+            in_place = (tw is not None or not nW) and (tb is not None or not want_b)
+            # (a throw-away dW when only the bias gradient is wanted: cwn_gemm_tn_f32 always accumulates one)
+            tgt_w = tw if tw is not None else torch.zeros(N, K + K2, dtype=torch.float32, device=dev)
+            tgt_b = None
+            if want_b:
+                tgt_b = tb if tb is not None else torch.zeros(N, dtype=torch.float32, device=dev)
+            if nW and tw is None:
+                dW = tgt_w
+            if want_b and tb is None:
+                db = tgt_b
+            if g.size(0):
+                tn = dict(dZ=g.data_ptr(), in_scale=None, in_shift=None, in_scale2=None, in_shift2=None, M=g.size(0), lddz=_ld(g),
+                          lddw=tgt_w.stride(0), N=N, in_relu=0)
+                if X2 is None or K % 4 == 0:
+                    tns = [_ffi.GemmTnDesc(X=X.data_ptr(), X2=_ffi.ptr(X2), dW=tgt_w.data_ptr(), db=_ffi.ptr(tgt_b), ldx=_ld(X),
+                                           ldx2=0 if X2 is None else _ld(X2), K=K, K2=K2, **tn)]
+                else:
+                    # (cwn_gemm_tn_f32 wants K % 4 == 0 next to X2: two descriptors into the column halves of dW)
+                    tns = [_ffi.GemmTnDesc(X=X.data_ptr(), X2=None, dW=tgt_w.data_ptr(), db=_ffi.ptr(tgt_b), ldx=_ld(X), ldx2=0,
+                                           K=K, K2=0, **tn),
+                           _ffi.GemmTnDesc(X=X2.data_ptr(), X2=None, dW=tgt_w.data_ptr() + 4 * K, db=None, ldx=_ld(X2), ldx2=0,
+                                           K=K2, K2=0, **tn)]
+                # in-place targets only (nothing handed back to autograd): the launch may wait for the end of the backward
+                _ffi.gemm_tn(tns, dev, keep=[g, X, X2, tgt_w, tgt_b], deferrable=ACCUMULATE_INTO_GRAD and in_place)
+        return dX, dX2, dW, db
+
+
+def linear_wide(X: Tensor, X2: Optional[Tensor], weight: Tensor, bias: Optional[Tensor] = None) -> Tensor:
+    """[X | X2] @ weight.T + bias in float32 from ONE cwn_linear_wide_f32 launch: weight [N, K + K2] with N <= 256 and
+    K + K2 <= 512 -- beyond GEMM_MAX_K (the combine network of a 160-wide layer: Linear(320 -> 160)).  X2 and bias may be
+    None; rows may be strided views.  Differentiable w.r.t. all four; inside a static batch (_ffi.dynamic_rows) the forward
+    and every part of the backward take the rows that exist from the device-side count, so rows behind the count are neither
+    written nor summed into dW / db.  Inside accumulate_into_grad() dW / db are added into the parameters' .grad."""
+    X, X2, weight, bias = _wide_operands(X, X2, weight, bias)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (X, X2, weight, bias)):
+        return _LinearWide.apply(X, X2, weight, bias)
+    Y = torch.empty(X.size(0), weight.size(0), dtype=torch.float32, device=X.device)
+    if Y.numel():
+        _ffi.linear_wide([_wide_desc(X, X2, weight.detach(), None if bias is None else bias.detach(), Y, False)], X.device)
+    return Y
+
+
+# ------------------------------------------------------------------------------------------------
 # LayerNorm (+ ReLU) over the rows of several matrices: graph_norm='ln' (csrc/cwn_layernorm.hip)
 # ------------------------------------------------------------------------------------------------
 def _ln_descs(zs, gammas, betas, outs, epss, relu: bool, stats=None) -> List['_ffi.LnDesc']:

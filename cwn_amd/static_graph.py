@@ -188,7 +188,7 @@ def refuse_unsupported_layers(model: torch.nn.Module, who: str, static: Optional
                         - {64, 128})
         if widths:
             raise NotImplementedError(f"{who}: a static batch in mode 'blocked' serves layers of feature width 64 or 128, this model "
-                                      f"has {widths}: build the StaticBatch with mode='csr' (any width up to 128)")
+                                      f"has {widths}: build the StaticBatch with mode='csr' (any width)")
     if static is not None and static.mode == 'csr' and training:
         # A CIN++ layer at a width other than 64 / 128 has no combine stage on the kernels (dense_train: its plan comes without
         # one): combine_nn runs as torch modules, and a torch BatchNorm1d in training mode would take its statistics over the
@@ -200,6 +200,41 @@ def refuse_unsupported_layers(model: torch.nn.Module, who: str, static: Optional
             raise NotImplementedError(f'{who}: {", ".join(bad)} is not served in training by a static batch: at a width other than '
                                       '64 / 128 its combine network runs as torch modules, whose BatchNorm(train) statistics would '
                                       'be taken over the capacity rows of a slot; use collated batches with TrainStep')
+    if static is not None and training:
+        # graph_norm='ln': the grouped GEMM, the LayerNorm launches and the wide combine product (cwn_amd/dense_ln.py) carry the
+        # row count, forward and backward, in both modes of a static batch.  What leaves them -- CIN++'s three / four-branch
+        # combine (torch.cat + linear), a layer beyond cwn_linear_wide_f32 (N > 256, K + K2 > 512), networks dense_ln does not
+        # take, CWN_FUSED_LN=0 -- runs torch modules whose weight gradients sum the capacity rows of a slot.
+        from . import dense_ln
+        bad, odd = [], []
+        for m in model.modules():
+            if not isinstance(m, SparseCINConv):
+                continue
+            nb, L = 2, len(m.mp_levels)
+            if isinstance(m, CINppConv):
+                nb = 4 if m.mp_levels[0].update_coboundaries_nn is not None else 3
+            nets = [net for lvl in m.mp_levels for net in m._update_nets(lvl, nb) + [lvl.combine_nn] if net is not None]
+            if not any(isinstance(x, torch.nn.LayerNorm) for net in nets for x in net.modules()):
+                continue
+            got = m._ln_chains([[None] * nb] * L, [None] * (nb * L), 0)
+            width = max(int(lvl.combine_nn[0].out_features) if isinstance(lvl.combine_nn[0], torch.nn.Linear) else
+                        int(lvl.up_msg_size) for lvl in m.mp_levels)
+            if got is None or not dense_ln.counted(*got):
+                bad.append(f'{type(m).__name__}(width {width})')
+            elif width % 4 != 0:
+                odd.append(f'{type(m).__name__}(width {width})')
+        if bad:
+            raise NotImplementedError(f'{who}: {", ".join(sorted(set(bad)))} with LayerNorm is not served in training by a static '
+                                      'batch: its update / combine networks leave the counted launches of cwn_amd/dense_ln.py (three or '
+                                      'four branches, N > 256 or K + K2 > 512, an activation other than ReLU, CWN_FUSED_LN=0) and '
+                                      'run as torch modules, whose weight gradients would be summed over the capacity rows of a '
+                                      'slot; use collated batches with TrainStep')
+        if odd:
+            # (seen on the device: at hidden 6 the embedding front leaves its fused launch for ops.embedding_sum, which builds a
+            #  host tensor per call -- not capturable; the fused head wants K % 4 == 0 as well)
+            raise NotImplementedError(f'{who}: {", ".join(sorted(set(odd)))} with LayerNorm is not served in training by a static '
+                                      'batch: at a width that is no multiple of 4 the embedding front and the head leave their '
+                                      'fused, count-aware launches; use collated batches with TrainStep')
 
 
 class StaticForward:

@@ -28,7 +28,7 @@
  *     cwn_layer_bwd_items_build_dev produce the per-batch tables on the device.
  *     Who checks "*m_dev <= capacity": cwn_gemm_f32 (both kernels), cwn_gemm_tn_f32, cwn_layernorm_*, cwn_dropout_f32,
  *     cwn_loss_f32 / cwn_loss_cols_f32, cwn_csr_long_rows, cwn_embedding_bwd_f32, cwn_embed_front_f32,
- *     cwn_embed_front_bwd_f32, cwn_oriented_layer_f32 / cwn_oriented_dz_f32, cwn_target_head_f32 / _bwd_f32, cwn_update_chain_f32 and cwn_linear_stats_f32 CLAMP the count to the capacity (a larger count behaves as the capacity); cwn_dense_stage_f32 /
+ *     cwn_embed_front_bwd_f32, cwn_oriented_layer_f32 / cwn_oriented_dz_f32, cwn_target_head_f32 / _bwd_f32, cwn_update_chain_f32, cwn_linear_stats_f32 and cwn_linear_wide_f32 CLAMP the count to the capacity (a larger count behaves as the capacity); cwn_dense_stage_f32 /
  *     _ex / _bwd, cwn_bn_finalize_f32, cwn_norm_*, cwn_update_mlp_f32 / cwn_update_mlp3_f32 and cwn_aggregate_f32 / _f64 take
  *     the count AS IT IS -- there the caller's vouching is what keeps the stores inside the buffers (the collate guard,
  *     cwn_collate_guard, zeroes the counts of a batch beyond its capacities before any of them is read).
@@ -955,6 +955,45 @@ int cwn_gemm_would_split(const cwn_gemm_desc* descs_host, int n);
  * element.  n == 0 and launches whose every M is 0 return CWN_OK without a device.
  * ------------------------------------------------------------------------------------------ */
 int cwn_linear_stats_f32(const cwn_gemm_desc* descs_host, int n, cwn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * A wide Linear product under a row count (csrc/cwn_linear_wide.hip):
+ *
+ *     Y = [X | X2] . W^T + bias        W [N, K + K2], torch Linear layout        up to CWN_MAX_DESCS products per launch
+ *     Y = [X | X2] . W   + bias        w_trans != 0: W [K + K2, N] -- dX = dY . W from the layer's own weight
+ *
+ * 1 <= N <= CWN_LINEAR_WIDE_MAX_N (256), K >= 1, K2 >= 0, K + K2 <= CWN_LINEAR_WIDE_MAX_K (512): what lies beyond
+ * cwn_gemm_f32's whole-K weight residency (K + K2 <= 256) -- the combine network Linear(320 -> 160) of a 160-wide layer.
+ * X2, bias and m_dev are optional; every operand has its own row stride; any alignment of 4 bytes (16-byte accesses
+ * where pointer, stride and widths allow, element by element otherwise; K need not be a multiple of 4 next to X2).
+ *   rows:  live = clamp(*m_dev, 0, M), or M when m_dev is NULL.  The workgroups walk the row tiles below `live` only and
+ *          the tile the count ends in stores its rows below the count only (cwn_gemm_desc.m_dev's contract).  Rows in
+ *          [live, M) may be LOADED -- they lie inside the buffers -- and may hold NaN: nothing of them reaches a live row.
+ * Exact fp32 on v_mfma_f32_16x16x4_f32 in cwn_gemm_f32's k order (slabs of 16 ascending, one accumulator chain per
+ * element, the bias added last); the weight is streamed through LDS in K-chunks of 64.  A row's bits depend on its own
+ * operands alone: not on M, the count or its position in the batch; at K + K2 <= 256 they are the bits of cwn_gemm_f32's
+ * exact kernel.  All descriptors of a launch share one weight layout.
+ * CWN_ERR_BAD_ARG, before any device call: n < 0, n > CWN_MAX_DESCS, descs NULL with n > 0; N, K, K2 outside the
+ * limits; X2 without K2 or K2 without X2; M < 0; a row stride below its width; a NULL X / W / Y with M > 0; descriptors
+ * that differ in w_trans.  CWN_ERR_ALIGN: a float pointer off 4 bytes, m_dev off 8.  CWN_ERR_TOO_LARGE: INT32_MAX tiles or
+ * more.  n == 0 and launches whose every M is 0 return CWN_OK without a device.
+ * ------------------------------------------------------------------------------------------ */
+#define CWN_LINEAR_WIDE_MAX_N 256
+#define CWN_LINEAR_WIDE_MAX_K 512
+#define CWN_LINEAR_WIDE_LDS_BYTES 41984   /* static LDS of a workgroup, at most (the transposed form) */
+typedef struct cwn_linear_wide_desc {
+    const float* X;         /* [M, K] row stride ldx */
+    const float* X2;        /* [M, K2] row stride ldx2, or NULL (K2 == 0) */
+    const float* W;         /* [N, K + K2], or [K + K2, N] with w_trans; row stride ldw */
+    const float* bias;      /* [N] or NULL */
+    float* Y;               /* [M, N] row stride ldy */
+    const int64_t* m_dev;   /* or NULL: the rows that exist (M = capacity, see "Conventions") */
+    int64_t M;
+    int64_t ldx, ldx2, ldw, ldy;
+    int32_t N, K, K2;
+    int32_t w_trans;
+} cwn_linear_wide_desc;
+int cwn_linear_wide_f32(const cwn_linear_wide_desc* descs_host, int n, cwn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Training-mode pieces of the dense networks (torch.nn.BatchNorm1d in train mode + ReLU between
