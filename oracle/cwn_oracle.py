@@ -300,19 +300,24 @@ def _lin(h: Tensor, p: Dict, prefix: str) -> Tensor:
     return h @ p[prefix + '.weight'].t() + p[prefix + '.bias']
 
 
-def _mlp2(h: Tensor, p: Dict, prefix: str, training: bool, norm: str) -> Tensor:
-    """mp/layers.py:303-321: Linear -> norm -> ReLU -> Linear -> norm -> ReLU (Sequential ids
+# mp/nn.py:7-27 get_nonlinearity, in plain torch: wherever the reference builds `act_module()` or calls `act`
+ACTS = {'relu': torch.relu, 'elu': torch.nn.functional.elu, 'tanh': torch.tanh, 'sigmoid': torch.sigmoid,
+        'id': lambda z: z}
+
+
+def _mlp2(h: Tensor, p: Dict, prefix: str, training: bool, norm: str, act: str = 'relu') -> Tensor:
+    """mp/layers.py:303-321: Linear -> norm -> act -> Linear -> norm -> act (Sequential ids
     0..5)."""
     h = _lin(h, p, prefix + '.0')
     h = _norm(h, p, prefix + '.1', training, norm)
-    h = torch.relu(h)
+    h = ACTS[act](h)
     h = _lin(h, p, prefix + '.3')
     h = _norm(h, p, prefix + '.4', training, norm)
-    return torch.relu(h)
+    return ACTS[act](h)
 
 
 def sparse_cin_cochain_conv(p: Dict, prm: Dict, use_coboundaries: bool, training: bool = False,
-                            norm: str = 'bn') -> Tensor:
+                            norm: str = 'bn', act: str = 'relu') -> Tensor:
     """SparseCINCochainConv.forward, mp/layers.py:184-214 + the default sub-networks of
     SparseCINConv (:286-325).  `p` is that level's state_dict (keys such as
     'msg_up_nn.1.weight', 'update_up_nn.0.weight', 'combine_nn.0.weight', 'eps1').
@@ -323,8 +328,8 @@ def sparse_cin_cochain_conv(p: Dict, prm: Dict, use_coboundaries: bool, training
     def msg_up(x_j, attr):
         if not use_coboundaries:
             return x_j                                    # lambda xs: xs[0]   (:295)
-        # Catter -> Linear(2F, F) -> ReLU                 (:290-293)
-        return torch.relu(_lin(torch.cat([x_j, attr], dim=-1), p, 'msg_up_nn.1'))
+        # Catter -> Linear(2F, F) -> act_module()         (:290-293)
+        return ACTS[act](_lin(torch.cat([x_j, attr], dim=-1), p, 'msg_up_nn.1'))
 
     out_up, _, out_b = propagate(
         x, prm['up_index'], prm['down_index'], prm['boundary_index'],
@@ -333,15 +338,15 @@ def sparse_cin_cochain_conv(p: Dict, prm: Dict, use_coboundaries: bool, training
         up_msg_size=width, down_msg_size=width, boundary_msg_size=width)
     out_up = out_up + (1 + p['eps1']) * x
     out_b = out_b + (1 + p['eps2']) * x
-    out_up = _mlp2(out_up, p, 'update_up_nn', training, norm)
-    out_b = _mlp2(out_b, p, 'update_boundaries_nn', training, norm)
+    out_up = _mlp2(out_up, p, 'update_up_nn', training, norm, act)
+    out_b = _mlp2(out_b, p, 'update_boundaries_nn', training, norm, act)
     h = _lin(torch.cat([out_up, out_b], dim=-1), p, 'combine_nn.0')
     h = _norm(h, p, 'combine_nn.1', training, norm)
-    return torch.relu(h)
+    return ACTS[act](h)
 
 
 def cinpp_cochain_conv(p: Dict, prm: Dict, use_coboundaries: bool, training: bool = False,
-                       norm: str = 'bn') -> Tensor:
+                       norm: str = 'bn', act: str = 'relu') -> Tensor:
     """CINppCochainConv.forward, mp/layers.py:243-260, with the default sub-networks of CINppConv (:366-416).  The
     class inherits use_down_msg=False (:167-168) and its forward passes no down_attr (:244-247): the lower stream is
     zeros, so out_down is the self term (1 + eps2) x alone; the boundary stream takes eps3."""
@@ -351,7 +356,7 @@ def cinpp_cochain_conv(p: Dict, prm: Dict, use_coboundaries: bool, training: boo
     def msg_up(x_j, attr):
         if not use_coboundaries:
             return x_j
-        return torch.relu(_lin(torch.cat([x_j, attr], dim=-1), p, 'msg_up_nn.1'))
+        return ACTS[act](_lin(torch.cat([x_j, attr], dim=-1), p, 'msg_up_nn.1'))
 
     out_up, out_down, out_b = propagate(
         x, prm['up_index'], prm['down_index'], prm['boundary_index'],
@@ -361,13 +366,13 @@ def cinpp_cochain_conv(p: Dict, prm: Dict, use_coboundaries: bool, training: boo
     out_up = out_up + (1 + p['eps1']) * x
     out_down = out_down + (1 + p['eps2']) * x
     out_b = out_b + (1 + p['eps3']) * x
-    out_up = _mlp2(out_up, p, 'update_up_nn', training, norm)
-    out_down = _mlp2(out_down, p, 'update_down_nn', training, norm)
-    out_b = _mlp2(out_b, p, 'update_boundaries_nn', training, norm)
+    out_up = _mlp2(out_up, p, 'update_up_nn', training, norm, act)
+    out_down = _mlp2(out_down, p, 'update_down_nn', training, norm, act)
+    out_b = _mlp2(out_b, p, 'update_boundaries_nn', training, norm, act)
     h = _lin(torch.cat([out_up, out_down, out_b], dim=-1), p, 'combine_nn.0')
     if norm == 'bn':
         h = _bn(h, p, 'combine_nn.1', training)
-    return torch.relu(h)
+    return ACTS[act](h)
 
 
 def _level_state(state: Dict, level: int) -> Dict:
@@ -376,7 +381,8 @@ def _level_state(state: Dict, level: int) -> Dict:
 
 
 def sparse_cin_conv(state: Dict, params: List[Dict], use_coboundaries: bool,
-                    training: bool = False, norm: str = 'bn', start_to_process: int = 0, conv: str = 'sparse_cin'):
+                    training: bool = False, norm: str = 'bn', start_to_process: int = 0, conv: str = 'sparse_cin',
+                    act: str = 'relu'):
     """SparseCINConv.forward, mp/layers.py:333-342 (`conv='cinpp'`: CINppConv.forward, :418-427)."""
     level = cinpp_cochain_conv if conv == 'cinpp' else sparse_cin_cochain_conv
     outs = []
@@ -384,7 +390,7 @@ def sparse_cin_conv(state: Dict, params: List[Dict], use_coboundaries: bool,
         if d < start_to_process:
             outs.append(prm['x'])
         else:
-            outs.append(level(_level_state(state, d), prm, use_coboundaries, training, norm))
+            outs.append(level(_level_state(state, d), prm, use_coboundaries, training, norm, act))
     return outs
 
 
@@ -481,10 +487,12 @@ def sparse_cin_model_forward(state: Dict, cx: Dict, num_layers: int, max_dim: in
                              final_readout: str = 'sum', training: bool = False, norm: str = 'bn',
                              jump_mode: Optional[str] = None, embed: Optional[str] = 'zinc',
                              init_reduce_mode: str = 'add', readout_dims=(0, 1, 2), conv: str = 'sparse_cin',
-                             drop_edge_up: bool = False, dropout: Optional[Dict] = None, drop_position: str = 'lin2'):
+                             drop_edge_up: bool = False, dropout: Optional[Dict] = None, drop_position: str = 'lin2',
+                             act: str = 'relu'):
     """SparseCIN.forward (mp/models.py:195-260), EmbedSparseCIN.forward (mp/molec_models.py:90-160)
     and OGBEmbedSparseCIN.forward (mp/molec_models.py:281-350) with dropout off and jump_mode in
-    {None, 'cat', 'max'}.  `embed`: None (features used as they are), 'zinc' (one Embedding per dimension
+    {None, 'cat', 'max'}.  `act`: the model's `nonlinearity` (ACTS), applied wherever the reference applies `act_module()`
+    or `act`: the message network, both stages of every update network, the combine stage, act(lin1s[d](x)).  `embed`: None (features used as they are), 'zinc' (one Embedding per dimension
     0/1) or 'ogb' (sum of per-column embeddings).  `conv='cinpp'`: EmbedCINpp / OGBEmbedCINpp (mp/molec_models.py:167-199,
     355-384: the same forward over CINppConv layers).  `drop_edge_up` (with max_dim 1): EmbedSparseCINNoRings
     (mp/molec_models.py:386-503: the edges' upper adjacency is removed from every layer's parameters, :456-457, 471-472).
@@ -528,7 +536,7 @@ def sparse_cin_model_forward(state: Dict, cx: Dict, num_layers: int, max_dim: in
         params = layer_params()
         pre = f'convs.{l}.'
         lstate = {k[len(pre):]: v for k, v in state.items() if k.startswith(pre)}
-        xs = sparse_cin_conv(lstate, params, use_coboundaries, training, norm, conv=conv)
+        xs = sparse_cin_conv(lstate, params, use_coboundaries, training, norm, conv=conv, act=act)
         xs = [x * dropout[('conv', l, d)] if ('conv', l, d) in dropout else x for d, x in enumerate(xs)]
         for d, x in enumerate(xs):
             cx['cochains'][d]['x'] = x
@@ -541,7 +549,8 @@ def sparse_cin_model_forward(state: Dict, cx: Dict, num_layers: int, max_dim: in
         xs = [torch.cat(j, dim=-1) for j in jump]
     elif jump_mode == 'max':
         # torch_geometric.nn.JumpingKnowledge('max') (torch_geometric is not in /root/reference nor in this
-        # image: its published forward is `torch.stack(xs, dim=-1).max(dim=-1)[0]`; parity unpinned for this mode)
+        # image: its published forward is `torch.stack(xs, dim=-1).max(dim=-1)[0]`); the reference's EmbedSparseCIN with
+        # jump_mode='max' is pinned by the case `jk_max` of tests/golden/cell_options.npz
         xs = [torch.stack(j, dim=-1).max(dim=-1)[0] for j in jump]
     elif jump_mode is not None:
         raise NotImplementedError(jump_mode)
@@ -558,7 +567,7 @@ def sparse_cin_model_forward(state: Dict, cx: Dict, num_layers: int, max_dim: in
         h = pin @ state[f'lin1s.{d}.weight'].t()
         if f'lin1s.{d}.bias' in state:
             h = h + state[f'lin1s.{d}.bias']
-        h = torch.relu(h)
+        h = ACTS[act](h)
         if drop_position == 'final_readout' and ('head', k) in dropout:
             h = h * dropout[('head', k)]
         hs.append(h)
@@ -573,11 +582,11 @@ def embed_sparse_cin_forward(state: Dict, cx: Dict, num_layers: int, max_dim: in
                              use_coboundaries: bool = True, readout: str = 'sum',
                              final_readout: str = 'sum', training: bool = False,
                              norm: str = 'bn', init_reduce_mode: str = 'add',
-                             embed_edge: bool = True, readout_dims=(0, 1, 2)):
+                             embed_edge: bool = True, readout_dims=(0, 1, 2), act: str = 'relu'):
     """EmbedSparseCIN.forward, mp/molec_models.py:90-160 (see sparse_cin_model_forward)."""
     return sparse_cin_model_forward(state, cx, num_layers, max_dim, use_coboundaries, readout,
                                     final_readout, training, norm, None, 'zinc', init_reduce_mode,
-                                    readout_dims)
+                                    readout_dims, act=act)
 
 
 # --------------------------------------------------------------------------------------------

@@ -7,9 +7,10 @@
     (JumpingKnowledge: 'cat' side by side, 'max' element-wise), the readout per graph, act(lin1), lin2 (eval: no dropout);
   * the `forward` of RingGIN, mp/ring_exp_models.py:117-127: init_linear, act(conv1), the convs, lin1 on the marked rows.
 
-torch_geometric is not a dependency and the reference's GINConv cannot run here, so there is no golden from the reference for
-this family: these functions are the yardstick, evaluated from a model's state_dict in float64.  Nothing here calls the code
-under test."""
+These functions are the yardstick of the graph baselines' kernel tests, evaluated from a model's state_dict in float64.  They
+are tied to the reference by tests/golden/gin_family.npz (tools/gen_golden_options.py: the reference's own GIN0, GIN,
+GIN0WithJK, GINWithJK and RingGIN behind a stand-in GINConv): tests/test_options_golden_host.py evaluates them from the stored
+states and holds them to the reference's float64 outputs, layer by layer, at 1e-11.  Nothing here calls the code under test."""
 import torch
 
 ACT64 = {'id': lambda z: z, 'relu': torch.relu, 'elu': torch.nn.functional.elu, 'tanh': torch.tanh, 'sigmoid': torch.sigmoid}

@@ -8,9 +8,10 @@
     where they have none), the GINEConv layers over the vertex graph with the edge cochain's rows as edge features (the row
     `shared_coboundaries[p]` for entry p of `upper_index`), the readout over the vertices, act(lin1), lin2.
 
-torch_geometric is not a dependency and the reference's GINEConv cannot run here, so there is no golden from the reference
-for this model: these functions are the yardstick, evaluated from a model's state_dict in float64.  Nothing here calls the
-code under test."""
+These functions are the yardstick of the GINE kernel's tests, evaluated from a model's state_dict in float64.  They are tied to
+the reference by tests/golden/gin_family.npz (tools/gen_golden_options.py: the reference's own EmbedGIN behind a stand-in
+GINEConv, five configurations): tests/test_options_golden_host.py evaluates them from the stored states and holds them to the
+reference's float64 outputs at 1e-11.  Nothing here calls the code under test."""
 import torch
 
 from tests._gin import ACT64, _norm64

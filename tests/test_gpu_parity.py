@@ -1100,8 +1100,8 @@ def test_molhiv_like_full_size_vs_oracle():
 
 def test_jumping_knowledge_max_vs_oracle():
     """mp/models.py:51, 92-99 with jump_mode='max' (torch_geometric's JumpingKnowledge('max'): elementwise
-    maximum over the layers' outputs, per dimension).  The oracle restates the published one-liner; no
-    reference-generated fixture exists for it (torch_geometric is absent): parity unpinned, stated."""
+    maximum over the layers' outputs, per dimension).  The oracle restates the published one-liner; the reference's own
+    EmbedSparseCIN with jump_mode='max' is the case 'jk_max' of tests/golden/cell_options.npz (tests/test_gpu_options_golden.py)."""
     from cwn_amd.models import SparseCIN
     torch.manual_seed(3)
     model = SparseCIN(1, 2, 3, 16, dropout_rate=0.0, max_dim=2, jump_mode='max', readout='sum',
