@@ -25,6 +25,7 @@ EXPORTS = ('cwn_abi_version', 'cwn_error_string', 'cwn_target_arch', 'cwn_csr_wo
            'cwn_layernorm_act_f32', 'cwn_layernorm_bwd_workspace_bytes', 'cwn_layernorm_bwd_f32',
            'cwn_oriented_layer_f32', 'cwn_oriented_dz_f32',
            'cwn_target_head_f32', 'cwn_target_head_bwd_f32', 'cwn_target_head_bwd_workspace_bytes',
+           'cwn_flow_head_f32', 'cwn_flow_head_bwd_f32', 'cwn_flow_head_workspace_floats',
            'cwn_linear_many_f64', 'cwn_update_chain_f64', 'cwn_update_chain_f32', 'cwn_linear_stats_f32',
            'cwn_linear_wide_f32',
            'cwn_aggregate_act_f32', 'cwn_aggregate_act_f64',
@@ -641,6 +642,16 @@ def lib():
     L.cwn_head_bwd_f32.restype = C.c_int
     L.cwn_head_bwd_f32.argtypes = [C.POINTER(HeadBwdDim), C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                    C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(Dropout), C.c_int32, C.c_int32, C.c_void_p]
+    L.cwn_flow_head_workspace_floats.restype = C.c_size_t
+    L.cwn_flow_head_workspace_floats.argtypes = [C.c_int64, C.c_int64, C.c_int32]
+    L.cwn_flow_head_f32.restype = C.c_int
+    L.cwn_flow_head_f32.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                    C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.cwn_flow_head_bwd_f32.restype = C.c_int
+    L.cwn_flow_head_bwd_f32.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                        C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]
     L.cwn_lift_create.restype = C.c_void_p
     L.cwn_lift_create.argtypes = [C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int]
     L.cwn_lift_size.restype = C.c_int64
@@ -936,6 +947,48 @@ def target_head_bwd(g: torch.Tensor, x: torch.Tensor, target_rows: torch.Tensor,
                                         weight.data_ptr(), ptr(dx), H, ptr(dW), ptr(db), H, K, ptr(ws), nbytes, dyn(Cn),
                                         stream_ptr(dev)), 'cwn_target_head_bwd_f32')
     return dx, (dW if need_dw else None), db
+
+
+FLOW_HEAD_MAX_WIDTH = 128      # = CWN_FLOW_HEAD_MAX_WIDTH
+FLOW_HEAD_MAX_OUT = 64         # = CWN_FLOW_HEAD_MAX_OUT
+FLOW_HEAD_CHUNK = 128          # = CWN_FLOW_HEAD_CHUNK
+
+
+def _flow_workspace(N: int, Cn: int, K: int, device) -> torch.Tensor:
+    floats = int(lib().cwn_flow_head_workspace_floats(N, Cn, K))
+    return torch.empty(max(floats, 4), dtype=torch.float32, device=device)
+
+
+def flow_head(x: torch.Tensor, ptr_dev: torch.Tensor, w1, b1, w2, b2, take_abs: bool, mean: bool, keep: bool):
+    """(out [C, O], pooled [C, K], h [C, H]) of cwn_flow_head_f32 -- two launches; pooled and h (lin1's pre-activation) only with
+    `keep`, else None.  x [N, K] with contiguous rows, the weights contiguous.  Host row counts: nothing is looked up in DYN_ROWS."""
+    N, K = x.shape
+    Cn, H, O = ptr_dev.numel() - 1, w1.size(0), w2.size(0)
+    dev = x.device
+    out = torch.empty(Cn, O, dtype=torch.float32, device=dev)
+    pooled = torch.empty(Cn, K, dtype=torch.float32, device=dev) if keep else None
+    h = torch.empty(Cn, H, dtype=torch.float32, device=dev) if keep else None
+    ws = _flow_workspace(N, Cn, K, dev)
+    check(lib().cwn_flow_head_f32(x.data_ptr() if N else None, N, x.stride(0) if N > 1 else K, ptr_dev.data_ptr(), Cn, w1.data_ptr(),
+                                  ptr(b1), w2.data_ptr(), ptr(b2), out.data_ptr(), O, ptr(pooled), ptr(h), K, H, O, int(take_abs),
+                                  int(mean), ws.data_ptr(), ws.numel(), stream_ptr(dev)), 'cwn_flow_head_f32')
+    return out, pooled, h
+
+
+def flow_head_bwd(g: torch.Tensor, h: torch.Tensor, x: torch.Tensor, ptr_dev: torch.Tensor, w1, w2, take_abs: bool, mean: bool,
+                  need_dx: bool):
+    """(dx [N, K] every row written or None, dh [C, H]) of cwn_flow_head_bwd_f32: two launches, one without dx."""
+    N, K = x.shape
+    Cn, H, O = ptr_dev.numel() - 1, w1.size(0), w2.size(0)
+    dev = x.device
+    dx = torch.empty(N, K, dtype=torch.float32, device=dev) if need_dx else None
+    dh = torch.empty(Cn, H, dtype=torch.float32, device=dev)
+    ws = _flow_workspace(N, Cn, K, dev)
+    check(lib().cwn_flow_head_bwd_f32(g.data_ptr(), g.stride(0) if Cn > 1 else O, h.data_ptr(), x.data_ptr() if N else None, N,
+                                      x.stride(0) if N > 1 else K, ptr_dev.data_ptr(), Cn, w1.data_ptr(), w2.data_ptr(), ptr(dx), K,
+                                      dh.data_ptr(), K, H, O, int(take_abs), int(mean), ws.data_ptr(), ws.numel(), stream_ptr(dev)),
+          'cwn_flow_head_bwd_f32')
+    return dx, dh
 
 
 # False: the row bands of a weight gradient are added with fp32 atomics (fastest: 1.48 ms ZINC training

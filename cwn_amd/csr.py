@@ -302,6 +302,14 @@ def ensure_built(adj: Optional['Adjacency']) -> Optional['Adjacency']:
     return adj
 
 
+def register_adjacency(index: torch.Tensor, adj: Adjacency) -> Adjacency:
+    """Enter a plan somebody else built for `index` (packed.PackedCochains.collate: the concatenation of the per-cochain
+    CSRs kept with the dataset) where `cached_adjacency(index, adj.n_dst, adj.n_val)` finds it: no build for that tensor."""
+    key = id(index)
+    _cache[key] = ((_ffi.tver(index), adj.n_dst, adj.n_val), weakref.ref(index, lambda _r, k=key: _cache.pop(k, None)), adj)
+    return adj
+
+
 def cached_adjacency(index: torch.Tensor, n_dst: int, n_src: int,
                      aux_index: Optional[torch.Tensor] = None, n_aux: int = 0,
                      build: bool = True) -> Adjacency:

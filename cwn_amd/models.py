@@ -761,6 +761,42 @@ class MessagePassingAgnostic(torch.nn.Module):
         return self.__class__.__name__
 
 
+# The head of EdgeOrient / EdgeMPNN -- |.|, the readout over every cochain's rows, lin1, ReLU, lin2 -- as ops.flow_head
+# (csrc/cwn_flow_head.hip: two launches forward, two backward and the weight-gradient GEMMs, no CSR over the batch vector, no
+# second [N, hidden] matrix).  CWN_FUSED_FLOW_HEAD=1 turns the route on; it is OFF by default: the launches of the default
+# forward are pinned (tests/test_gpu_oriented.py::test_dispatch_proof), whatever the route measures -- the figures are in
+# profiles/flow_packed.md (tools/bench_flow.py).
+FUSED_FLOW_HEAD = os.environ.get('CWN_FUSED_FLOW_HEAD') == '1'
+
+
+def _edge_readout(model, data, x: torch.Tensor, include_partial: bool):
+    """The end of EdgeOrient.forward / EdgeMPNN.forward behind the layers; `model.last_head_route` names the route taken:
+      'fused'    FUSED_FLOW_HEAD on, x float32 on the GPU within ops.flow_head's limits, a batch that carries `ptr_dev`
+                 (packed.PackedCochains.collate), no active dropout, no `include_partial`: ops.flow_head.
+      'generic'  everything else: torch.abs, global_pool, the Linear modules -- unchanged."""
+    n = getattr(data, 'num_cochains', None)
+    ptr_dev = getattr(data, 'ptr_dev', None)
+    lin1, lin2 = model.lin1, model.lin2
+    if (FUSED_FLOW_HEAD and not include_partial and ptr_dev is not None and n is not None
+            and not (model.training and model.dropout_rate > 0)
+            and ops.flow_head_applies(x, ptr_dev, lin1.weight, lin1.bias, lin2.weight, lin2.bias)
+            and ptr_dev.numel() == int(n) + 1):
+        model.last_head_route = 'fused'
+        return ops.flow_head(x, ptr_dev, lin1.weight, lin1.bias, lin2.weight, lin2.bias, abs=not model.fully_invar,
+                             mean=model.readout == 'mean', n_cochains=int(n))
+    model.last_head_route = 'generic'
+    cell_pred = x
+    if not model.fully_invar:
+        x = torch.abs(x)
+    if n is None:
+        n = int(data.batch.max()) + 1
+    x = global_pool(x, data.batch, int(n), mean=model.readout == 'mean')
+    x = torch.relu(lin1(x))
+    x = ops.dropout(x, model.dropout_rate, model.training)
+    x = lin2(x)
+    return (x, cell_pred) if include_partial else x
+
+
 class EdgeOrient(torch.nn.Module):
     """mp/models.py:476-546: edge signals under a choice of edge orientations -- L x OrientedConv (bias-free update maps: the
     layers stay equivariant), |.| for invariance, readout over the edges of each complex, lin1 -> ReLU -> dropout -> lin2.
@@ -783,6 +819,7 @@ class EdgeOrient(torch.nn.Module):
                 act_fn=get_nonlinearity(nonlinearity, return_module=False), orient=not fully_invar))
         self.lin1 = Linear(hidden, hidden)
         self.lin2 = Linear(hidden, num_classes)
+        self.last_head_route = None          # 'fused' / 'generic': the route of the last forward's head (_edge_readout)
 
     def reset_parameters(self):
         for conv in self.convs:
@@ -798,17 +835,7 @@ class EdgeOrient(torch.nn.Module):
         for conv in self.convs:
             x = conv(data)
             data.x = x
-        cell_pred = x
-        if not self.fully_invar:
-            x = torch.abs(x)
-        n = getattr(data, 'num_cochains', None)
-        if n is None:
-            n = int(data.batch.max()) + 1
-        x = global_pool(x, data.batch, int(n), mean=self.readout == 'mean')
-        x = torch.relu(self.lin1(x))
-        x = ops.dropout(x, self.dropout_rate, self.training)
-        x = self.lin2(x)
-        return (x, cell_pred) if include_partial else x
+        return _edge_readout(self, data, x, include_partial)
 
     def __repr__(self):
         return self.__class__.__name__
@@ -838,6 +865,7 @@ class EdgeMPNN(torch.nn.Module):
                 act_fn=get_nonlinearity(nonlinearity, return_module=False), orient=not fully_invar))
         self.lin1 = Linear(hidden, hidden)
         self.lin2 = Linear(hidden, num_classes)
+        self.last_head_route = None          # 'fused' / 'generic': the route of the last forward's head (_edge_readout)
 
     def reset_parameters(self):
         for conv in self.convs:
@@ -853,17 +881,7 @@ class EdgeMPNN(torch.nn.Module):
         for conv in self.convs:
             x = conv(data)
             data.x = x
-        cell_pred = x
-        if not self.fully_invar:
-            x = torch.abs(x)
-        n = getattr(data, 'num_cochains', None)
-        if n is None:
-            n = int(data.batch.max()) + 1
-        x = global_pool(x, data.batch, int(n), mean=self.readout == 'mean')
-        x = torch.relu(self.lin1(x))
-        x = ops.dropout(x, self.dropout_rate, self.training)
-        x = self.lin2(x)
-        return (x, cell_pred) if include_partial else x
+        return _edge_readout(self, data, x, include_partial)
 
     def __repr__(self):
         return self.__class__.__name__

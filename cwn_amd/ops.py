@@ -2285,6 +2285,121 @@ def target_head(x: Tensor, target_rows: Tensor, weight: Tensor, bias: Optional[T
 
 
 # ------------------------------------------------------------------------------------------------
+# The edge-flow readout head (csrc/cwn_flow_head.hip): |x| -> readout per cochain -> lin1 -> ReLU -> lin2 of EdgeOrient /
+# EdgeMPNN, two launches forward, two backward (+ the weight gradients through cwn_gemm_tn_f32)
+# ------------------------------------------------------------------------------------------------
+# an operand of cwn_flow_head_f32 / _bwd_f32
+_FLOW_ROWS = dict(dtypes=(torch.float32,), what='flow_head: ', hint='cwn_flow_head_f32 computes in fp32 only (float64 runs through '
+                  'ops.aggregate and the torch modules: the generic route of models.EdgeOrient / EdgeMPNN)')
+
+
+def _flow_shapes_ok(x: Tensor, ptr_dev: Tensor, w1: Tensor, b1, w2: Tensor, b2) -> bool:
+    if x.dim() != 2 or w1.dim() != 2 or w2.dim() != 2 or ptr_dev.dim() != 1 or ptr_dev.numel() < 1:
+        return False
+    (H, K), O = w1.shape, int(w2.size(0))
+    return (1 <= K <= _ffi.FLOW_HEAD_MAX_WIDTH and 1 <= H <= _ffi.FLOW_HEAD_MAX_WIDTH and 1 <= O <= _ffi.FLOW_HEAD_MAX_OUT
+            and x.size(1) == K and w2.size(1) == H and (b1 is None or tuple(b1.shape) == (H,))
+            and (b2 is None or tuple(b2.shape) == (O,)))
+
+
+def flow_head_applies(x, ptr_dev, lin1_w, lin1_b, lin2_w, lin2_b) -> bool:
+    """Do cwn_flow_head_f32 / _bwd_f32 take these operands?  float32 on the GPU, x [N, K] with contiguous rows (a row stride
+    is allowed), lin1_w [H, K] and lin2_w [O, H] contiguous, the biases [H] / [O] or None, 1 <= K, H <= 128, 1 <= O <= 64,
+    ptr_dev a contiguous int64 vector on the GPU, and no `_ffi.dynamic_rows` in force (the launches take host row counts)."""
+    ts = [x, lin1_w, lin2_w] + [b for b in (lin1_b, lin2_b) if b is not None]
+    if _ffi.DYN_ROWS or not all(isinstance(t, Tensor) and t.is_cuda and t.dtype == torch.float32 for t in ts):
+        return False
+    if not (isinstance(ptr_dev, Tensor) and ptr_dev.is_cuda and ptr_dev.dtype == torch.long and ptr_dev.is_contiguous()):
+        return False
+    if not (_rows_contiguous(x, 2) and lin1_w.is_contiguous() and lin2_w.is_contiguous()
+            and all(b is None or b.is_contiguous() for b in (lin1_b, lin2_b))):
+        return False
+    return _flow_shapes_ok(x, ptr_dev, lin1_w, lin1_b, lin2_w, lin2_b)
+
+
+class _FlowHead(torch.autograd.Function):
+    """cwn_flow_head_f32 forward (keeping the pooled rows and lin1's pre-activation), cwn_flow_head_bwd_f32 backward: dx
+    with every row written, dh; the weight gradients are sums over the cochains, one cwn_gemm_tn_f32 call each way of
+    loading (dW1 = dh^T pooled with db1, dW2 = g^T relu(h) with db2)."""
+
+    @staticmethod
+    def forward(ctx, x, ptr_dev, w1, b1, w2, b2, take_abs, mean):
+        out, pooled, h = _ffi.flow_head(x, ptr_dev, w1, b1, w2, b2, take_abs, mean, keep=True)
+        ctx.save_for_backward(x, ptr_dev, w1, w2, pooled, h)
+        ctx.flags = (take_abs, mean, b1 is not None, b2 is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, ptr_dev, w1, w2, pooled, h = ctx.saved_tensors
+        take_abs, mean, has_b1, has_b2 = ctx.flags
+        need = ctx.needs_input_grad
+        g = _f32c(g, 'grad')
+        dev = x.device
+        Cn, (H, K), O = int(g.size(0)), w1.shape, int(w2.size(0))
+        dx, dh = _ffi.flow_head_bwd(g, h, x, ptr_dev, w1, w2, take_abs, mean, need[0])
+        grads = {}
+        descs = []
+        for name, wanted, b_wanted, dZ, X, N_, K_, relu in (('1', need[2], has_b1 and need[3], dh, pooled, H, K, 0),
+                                                           ('2', need[4], has_b2 and need[5], g, h, O, H, 1)):
+            if not (wanted or b_wanted):
+                continue
+            dW = torch.zeros(N_, K_, dtype=torch.float32, device=dev)
+            db = torch.zeros(N_, dtype=torch.float32, device=dev) if b_wanted else None
+            grads['w' + name], grads['b' + name] = (dW if wanted else None), db
+            if Cn:
+                descs.append(_ffi.GemmTnDesc(dZ=dZ.data_ptr(), X=X.data_ptr(), X2=None, in_scale=None, in_shift=None, in_scale2=None,
+                                             in_shift2=None, dW=dW.data_ptr(), db=_ffi.ptr(db), M=Cn, lddz=N_, ldx=K_, ldx2=0,
+                                             lddw=K_, N=N_, K=K_, K2=0, in_relu=relu))
+        if descs:
+            _ffi._flush_descs(descs, dev)
+        return (dx, None, grads.get('w1'), grads.get('b1'), grads.get('w2'), grads.get('b2'), None, None)
+
+
+def flow_head(x: Tensor, ptr_dev: Tensor, lin1_w: Tensor, lin1_b: Optional[Tensor], lin2_w: Tensor, lin2_b: Optional[Tensor], *,
+              abs: bool = True, mean: bool = False, n_cochains: Optional[int] = None) -> Tensor:
+    """The head of EdgeOrient / EdgeMPNN (mp/models.py:531-545) on the device, float32:
+
+        pooled[c, :] = sum over the rows ptr[c] .. ptr[c + 1] - 1 of f(x[r, :])      f = |.| (`abs`) or identity;
+                                                                                     / max(rows, 1) with `mean`
+        out[c, :]    = lin2_w relu(lin1_w pooled[c, :] + lin1_b) + lin2_b            [C, O]
+
+    `ptr_dev`: the collate's `ptr` as an int64 vector of C + 1 entries ON THE DEVICE (packed.PackedCochains.collate's
+    `ptr_dev`): ascending from 0 to the rows of x -- nothing is read back to check it; the kernels clamp what lies outside.
+    `n_cochains`, when given, is checked against its length.  Two launches forward, two backward, no atomics: a cochain's
+    prediction has the same bits alone, anywhere in any batch and on every run.  Differentiable w.r.t. x and the four
+    parameters (d|x|/dx = sgn(x), 0 at 0, as torch).  float32 on the GPU with 1 <= K, H <= 128, 1 <= O <= 64
+    (`flow_head_applies`): another dtype or device is a TypeError that names it, another shape a ValueError -- never a
+    fallback."""
+    x = _rows_operand(x, 'x', 2, **_FLOW_ROWS)
+    w1, w2 = _rows_operand(lin1_w, 'lin1_w', 2, **_FLOW_ROWS), _rows_operand(lin2_w, 'lin2_w', 2, **_FLOW_ROWS)
+    b1, b2 = _rows_operand(lin1_b, 'lin1_b', 1, **_FLOW_ROWS), _rows_operand(lin2_b, 'lin2_b', 1, **_FLOW_ROWS)
+    if x is None or w1 is None or w2 is None:
+        raise TypeError('flow_head: x, lin1_w and lin2_w are required')
+    for name, W in (('lin1_w', w1), ('lin2_w', w2)):
+        if not W.is_contiguous():             # (a row-strided view: the launches take the weights as torch.nn.Linear holds them)
+            raise TypeError(f'flow_head: {name} must be a contiguous 2-D float32 tensor (shape {tuple(W.shape)}, strides '
+                            f'{tuple(W.stride())})')
+    if not isinstance(ptr_dev, Tensor) or ptr_dev.dtype != torch.long or not ptr_dev.is_cuda:
+        got = f'{ptr_dev.dtype} on {ptr_dev.device}' if isinstance(ptr_dev, Tensor) else type(ptr_dev).__name__
+        raise TypeError(f'flow_head: ptr_dev must be an int64 tensor on the GPU (got {got})')
+    if ptr_dev.dim() != 1 or ptr_dev.numel() < 1 or (n_cochains is not None and ptr_dev.numel() != int(n_cochains) + 1):
+        want = 'C + 1 >= 1' if n_cochains is None else f'{int(n_cochains) + 1}'
+        raise ValueError(f'flow_head: ptr_dev holds C + 1 row offsets ({want} entries), got shape {tuple(ptr_dev.shape)}')
+    if _ffi.DYN_ROWS:
+        raise RuntimeError('flow_head takes host row counts: it does not run under _ffi.dynamic_rows (a static batch)')
+    ptr_dev = ptr_dev.contiguous()
+    if not _flow_shapes_ok(x, ptr_dev, w1, b1, w2, b2):
+        raise ValueError(f'flow_head takes x [N, K], lin1_w [H, K], lin2_w [O, H] with 1 <= K, H <= {_ffi.FLOW_HEAD_MAX_WIDTH}, '
+                         f'1 <= O <= {_ffi.FLOW_HEAD_MAX_OUT} and biases [H] / [O]: x {tuple(x.shape)}, lin1_w {tuple(w1.shape)}, '
+                         f'lin2_w {tuple(w2.shape)}, lin1_b {None if b1 is None else tuple(b1.shape)}, '
+                         f'lin2_b {None if b2 is None else tuple(b2.shape)}')
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, w1, b1, w2, b2)):
+        return _FlowHead.apply(x, ptr_dev, w1, b1, w2, b2, bool(abs), bool(mean))
+    return _ffi.flow_head(x, ptr_dev, w1, b1, w2, b2, bool(abs), bool(mean), keep=False)[0]
+
+
+# ------------------------------------------------------------------------------------------------
 # The float64 dense path (csrc/cwn_dense_f64.hip): the Linear layers of a double model, inference only
 # ------------------------------------------------------------------------------------------------
 ACT_CODES = ACTS = {'id': _ffi.ACT_ID, 'relu': _ffi.ACT_RELU, 'elu': _ffi.ACT_ELU, 'tanh': _ffi.ACT_TANH, 'sigmoid': _ffi.ACT_SIGMOID}

@@ -430,3 +430,339 @@ class PackedLoader:
         for idx in self.batches():
             yield self.packed.collate(idx)
         self.epoch += 1
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# Cochains (the edge-flow experiments: a dataset of `Cochain`s of ONE dimension, batched by CochainBatch.from_cochain_list)
+# ------------------------------------------------------------------------------------------------------------------------------
+_COCHAIN_KEYS = ('x', 'y', 'upper_index', 'lower_index', 'upper_orient', 'lower_orient')
+# Their offsets need the cell counts of OTHER dimensions (complex.py from_cochain_list: below / above), which a list of
+# cochains of one dimension does not carry; `mask` needs the target machinery of PackedComplexes.  Out of scope here.
+_COCHAIN_REFUSED = ('shared_boundaries', 'shared_coboundaries', 'boundary_index', 'mask')
+_ORIENT_OF = {'upper_orient': 'upper_index', 'lower_orient': 'lower_index'}
+_SLICE_KEYS = ('upper_index', 'lower_index', 'shared_boundaries', 'shared_coboundaries', 'boundary_index')   # complex.INDEX_KEYS
+
+
+def cochain_meta(cochains) -> dict:
+    """The numpy metadata of a list of cochains, after every check PackedCochains makes (no tensor leaves the host):
+    `dim`; per cochain `n_cells` (0 without cells), `has_cells`, `n_up`, `n_down`; `keys` (those of _COCHAIN_KEYS some cochain
+    carries) and per key `length` / `start` / `has` [len(keys), C] -- lengths and starts in elements of the packed array
+    (x: rows * width, y: rows * its width, an index: columns, an orient: entries) -- and `width` of x and y."""
+    if len(cochains) == 0:
+        raise ValueError('PackedCochains needs at least one cochain')
+    dim = cochains[0].dim
+    C = len(cochains)
+    width = {}
+    for ci, c in enumerate(cochains):
+        if c.dim != dim:
+            raise ValueError(f'cochain {ci} has dim {c.dim}, cochain 0 has dim {dim}: a packed dataset holds cochains of one dimension')
+        for key in _COCHAIN_REFUSED:
+            if getattr(c, key, None) is not None:
+                raise ValueError(f'cochain {ci} carries {key}: PackedCochains does not batch it (its offsets need the cells of '
+                                 'another dimension, or the target rows of PackedComplexes); pack the complexes instead')
+        x = c.x
+        if x is not None:
+            if x.dtype != torch.float32:
+                raise TypeError(f'cochain {ci}: x is {x.dtype}, PackedCochains packs float32 features (the float64 path batches '
+                                'on the host: CochainBatch.from_cochain_list)')
+            if x.dim() != 2 or width.setdefault('x', int(x.size(1))) != int(x.size(1)):
+                raise ValueError(f'cochain {ci}: x is {tuple(x.shape)}, a packed dataset holds [n, {width.get("x", "w")}] features')
+        y = c.y
+        if y is not None:
+            if y.dtype not in (torch.float32, torch.int32, torch.int64):
+                raise TypeError(f'cochain {ci}: y is {y.dtype} (float32 / int32 / int64 only)')
+            tail = tuple(y.shape[1:])
+            if width.setdefault('y_tail', tail) != tail or width.setdefault('y_dtype', y.dtype) != y.dtype:
+                raise ValueError(f'cochain {ci}: y is {y.dtype} {tuple(y.shape)}, the others are {width["y_dtype"]} [.., '
+                                 f'{width["y_tail"]}]')
+        for key in ('upper_index', 'lower_index'):
+            t = c[key]
+            if t is not None and (t.dtype != torch.long or t.dim() != 2 or t.size(0) != 2):
+                raise ValueError(f'cochain {ci}: {key} must be an int64 [2, e] tensor (got {t.dtype} {tuple(t.shape)})')
+        for key, of in _ORIENT_OF.items():
+            t, index = c[key], c[of]
+            if t is None:
+                continue
+            if t.dtype != torch.float32 or t.dim() != 1:
+                raise ValueError(f'cochain {ci}: {key} must be a float32 [e] vector (got {t.dtype} {tuple(t.shape)})')
+            cols = 0 if index is None else int(index.size(1))
+            if int(t.numel()) != cols:
+                raise ValueError(f'cochain {ci}: {key} has {int(t.numel())} entries, {of} has {cols} columns: one orientation per '
+                                 'adjacency entry')
+    width['y'] = int(np.prod(width.pop('y_tail', ()), dtype=np.int64))
+    width.pop('y_dtype', None)
+    n_here = [c.num_cells for c in cochains]
+    meta = dict(dim=dim, width=width,
+                n_cells=np.array([n or 0 for n in n_here], dtype=np.int64), has_cells=np.array([n is not None for n in n_here], dtype=bool),
+                # (the increments from_cochain_list takes without the shared keys: the counts a cochain was GIVEN)
+                n_up=np.array([c.__num_cells_up__ or 0 for c in cochains], dtype=np.int64),
+                n_down=np.array([(c.__num_cells_down__ or 0) if dim > 0 else 0 for c in cochains], dtype=np.int64))
+    keys = tuple(k for k in _COCHAIN_KEYS if any(c[k] is not None for c in cochains))
+    length = np.zeros((len(keys), C), dtype=np.int64)
+    for ki, key in enumerate(keys):
+        for ci, c in enumerate(cochains):
+            t = c[key]
+            if t is None:
+                continue
+            if key == 'x':
+                length[ki, ci] = int(t.size(0)) * width['x']
+            elif key == 'y':
+                length[ki, ci] = (1 if t.dim() == 0 else int(t.size(0))) * width['y']
+            else:
+                length[ki, ci] = int(t.size(-1))
+    meta.update(keys=keys, length=length, start=np.cumsum(length, axis=1) - length,
+                has=np.array([[c[k] is not None for c in cochains] for k in keys], dtype=bool).reshape(len(keys), C))
+    return meta
+
+
+def cochain_tables(meta: dict, idx) -> dict:
+    """The segment tables of the batch of cochains `idx` (in that order) -- numpy in, numpy out, nothing touches a device:
+      cells [B], cell_off [B] (the running cell offset the index values shift by), seg [B + 1] (cell_off and the total: the
+      segments of the batch vector; a cochain without cells is an empty one), ptr ([0] + the running cell count over the
+      cochains that HAVE cells, or None when none has), num_cells / num_cells_up / num_cells_down, num_cells_list (None for
+      a cochain without cells), dst[key] [B + 1] / src[key] [B] / present[key] for every packed key (element offsets in the
+      batched and in the packed array) and slices[key] for the five index keys of the reference's `__slices__`."""
+    idx = np.asarray(idx, dtype=np.int64).reshape(-1)
+    B = int(idx.size)
+    if B == 0:
+        raise ValueError('collate of an empty index list')
+    C = int(meta['n_cells'].size)
+    if idx.min() < 0 or idx.max() >= C:
+        raise IndexError(f'cochain numbers outside 0 .. {C - 1}')
+    cells, has_cells = meta['n_cells'][idx], meta['has_cells'][idx]
+    seg = np.zeros(B + 1, dtype=np.int64)
+    np.cumsum(cells, out=seg[1:])
+    out = dict(B=B, cells=cells, cell_off=seg[:-1], seg=seg, num_cells=int(seg[-1]), num_cells_up=int(meta['n_up'][idx].sum()),
+               num_cells_down=int(meta['n_down'][idx].sum()) if meta['dim'] > 0 else None,
+               num_cells_list=[int(n) if h else None for n, h in zip(cells.tolist(), has_cells.tolist())],
+               ptr=np.concatenate([[0], np.cumsum(cells[has_cells])]).astype(np.int64) if has_cells.any() else None,
+               dst={}, src={}, present={}, slices={k: [0] * (B + 1) for k in _SLICE_KEYS})
+    for ki, key in enumerate(meta['keys']):
+        dst = np.zeros(B + 1, dtype=np.int64)
+        np.cumsum(meta['length'][ki, idx], out=dst[1:])
+        out['dst'][key], out['src'][key] = dst, meta['start'][ki, idx]
+        out['present'][key] = bool(meta['has'][ki, idx].any())
+        if key in out['slices']:
+            out['slices'][key] = dst.tolist()
+    return out
+
+
+class PackedCochains:
+    """A dataset of `Cochain`s (CPU tensors, one `dim`) packed on `device`; `collate(idx)` is the CochainBatch
+    `CochainBatch.from_cochain_list([cochains[i] for i in idx]).to(device)` would be, field for field, from ONE small H2D
+    copy of the segment tables (`cochain_tables`) and ONE cwn_collate launch.  The batch also carries `ptr_dev`: int64
+    [B + 1] on the device, the first row of every cochain by its place in the batch and the row total -- `ptr` itself when
+    every cochain has cells -- which ops.flow_head reads.
+
+    `with_csr`: the destination-sorted CSR of every cochain's upper and lower adjacency and of their source-keyed
+    transposes is built ONCE here (cwn_csr_build over the block-diagonal index of the whole dataset, cut at the cochains,
+    local numbers).  A batch is block-diagonal and per-cochain contiguous, so its plans are the concatenations: `col` and
+    `perm` collate as ADD32 with the cell and the entry offset, `rowptr` without its leading zero plus the running entry
+    count (the scheme of PackedComplexes' boundary CSRs), all in the same launch.  The batch's index tensors are then
+    registered with their built `csr.Adjacency` (and `_t_src`) where OrientedConv looks plans up: no cwn_csr_build per
+    batch, forward or backward.  Long-row lists: none when no row of the dataset exceeds csr.LONG_ROW, else filled by
+    cwn_csr_long_rows over the collated row pointers (one more launch)."""
+
+    def __init__(self, cochains, device, with_csr: bool = True):
+        self.meta = cochain_meta(cochains)
+        self.device = torch.device(device)
+        self.with_csr = bool(with_csr)
+        self.num = len(cochains)
+        self.dim = self.meta['dim']
+        self.epoch = 0
+        m = self.meta
+        self._packs = {}
+        for ki, key in enumerate(m['keys']):
+            present = [c[key] for c in cochains if c[key] is not None]
+            if key in ('x', 'y'):
+                data = torch.cat([t.reshape(-1) for t in present])
+            else:
+                data = torch.cat(present, dim=-1)
+            rows = 2 if key in ('upper_index', 'lower_index') else 1
+            op = _ffi.COLLATE_ADD64 if rows == 2 else (_ffi.COLLATE_COPY64 if data.dtype == torch.int64 else _ffi.COLLATE_COPY32)
+            self._packs[key] = _Packed(data.contiguous().to(self.device), m['start'][ki], m['length'][ki], m['has'][ki], rows,
+                                       m['width'].get(key, 1), op)
+        self._y_tail = tuple(next(c.y for c in cochains if c.y is not None).shape[1:]) if 'y' in self._packs else ()
+        self._row0 = np.cumsum(m['n_cells']) - m['n_cells']           # first cell of every cochain in packed order
+        self._csr = {}               # 'upper_index' / 'lower_index' -> ((rowptr, col, perm), the same of the transpose), local
+        self.has_long_rows = False
+        if self.with_csr:
+            self._build_csr()
+
+    def _build_csr(self) -> None:
+        from .csr import LONG_ROW, Adjacency
+        dev, C = self.device, self.num
+        n = torch.from_numpy(self.meta['n_cells']).to(dev)
+        row0 = torch.from_numpy(self._row0).to(dev)
+        total = int(self.meta['n_cells'].sum())
+        self._zero = torch.zeros(1, dtype=torch.int32, device=dev)     # a plan's rowptr[0]
+        for key in ('upper_index', 'lower_index'):
+            pk = self._packs.get(key)
+            if pk is None:
+                continue
+            E = int(pk.data.size(1))
+            if E >= 2 ** 31 - 1 or total >= 2 ** 31 - 1:
+                raise ValueError(f'{key}: {E} entries over {total} cells do not fit the int32 plans; pack the dataset in parts')
+            cid = torch.repeat_interleave(torch.arange(C, device=dev), torch.from_numpy(np.asarray(pk.length)).to(dev), output_size=E)
+            ent0 = torch.from_numpy(np.asarray(pk.start)).to(dev)
+            if E and bool(((pk.data < 0) | (pk.data >= n[cid])).any()):
+                raise IndexError(f'{key}: a local index outside its cochain')
+            adj = Adjacency.from_index((pk.data + row0[cid]).contiguous(), total, total)
+            local = []
+            for a in (adj, adj.t_src):
+                rp = a.rowptr.long()
+                self.has_long_rows = self.has_long_rows or bool(((rp[1:] - rp[:-1]) > LONG_ROW).any())
+                local.append(((rp[1:] - torch.repeat_interleave(ent0, n, output_size=total)).to(torch.int32),
+                              (a.col.long() - row0[cid]).to(torch.int32), (a.perm.long() - ent0[cid]).to(torch.int32)))
+            self._csr[key] = tuple(local)
+
+    # --------------------------------------------------------------------------------------------
+    def collate(self, idx: Sequence[int]) -> CochainBatch:
+        """The CochainBatch of the cochains `idx` (in that order), on the device."""
+        from . import csr
+        t = cochain_tables(self.meta, idx)
+        idx = np.asarray(idx, dtype=np.int64).reshape(-1)
+        B, dev, n = t['B'], self.device, t['num_cells']
+        keys = self.meta['keys']
+        # ONE int64 array: per key dst [B + 1] and src [B]; the cell offsets twice (both rows of an index); the batch
+        # vector's segments; every cochain's first cell in packed order; the tables of the plans' leading zero
+        parts, off, run = [], {}, 0
+
+        def put(name, a):
+            nonlocal run
+            off[name] = run
+            parts.append(np.asarray(a, dtype=np.int64).reshape(-1))
+            run += parts[-1].size
+        for key in keys:
+            put('dst_' + key, t['dst'][key])
+            put('src_' + key, t['src'][key])
+        put('cell_off', np.concatenate([t['cell_off'], t['cell_off']]))
+        put('seg', t['seg'])
+        if self._csr:
+            put('row0', self._row0[idx])
+            put('one_dst', np.concatenate([[0], np.ones(B, dtype=np.int64)]))
+            put('zero_src', np.zeros(B, dtype=np.int64))
+        tab = torch.from_numpy(np.concatenate(parts)).to(dev, non_blocking=True)
+        base = tab.data_ptr()
+        at = lambda name: base + 8 * off[name]
+        out = CochainBatch(self.dim)
+        descs = []
+        for key in keys:
+            pk, total = self._packs[key], int(t['dst'][key][-1])
+            if not t['present'][key]:
+                continue                      # (no cochain of the batch has it: the attribute stays None, as on the host)
+            if key == 'x':
+                val = torch.empty(total // pk.width, pk.width, dtype=pk.data.dtype, device=dev)
+            elif key == 'y':
+                val = torch.empty((total // max(pk.width, 1),) + self._y_tail, dtype=pk.data.dtype, device=dev)
+            elif pk.rows == 2:
+                val = torch.empty(2, total, dtype=pk.data.dtype, device=dev)
+            else:
+                val = torch.empty(total, dtype=pk.data.dtype, device=dev)
+            if key == 'x':
+                out._x = val
+            else:
+                setattr(out, key, val)
+            if total:
+                descs.append(_ffi.CollateDesc(src=pk.data.data_ptr(), dst=val.data_ptr(), dst_start=at('dst_' + key), src_start=at('src_' + key),
+                                              add=at('cell_off') if pk.rows == 2 else None,
+                                              src_row_stride=pk.data.size(-1) if pk.rows == 2 else 0,
+                                              dst_row_stride=total if pk.rows == 2 else 0, n_rows=pk.rows, op=pk.op))
+        if t['ptr'] is not None:
+            out.batch = torch.empty(n, dtype=torch.int64, device=dev)
+            out.ptr = t['ptr'].tolist()
+            if n:
+                descs.append(_ffi.CollateDesc(src=None, dst=out.batch.data_ptr(), dst_start=at('seg'), src_start=None, add=None,
+                                              src_row_stride=0, dst_row_stride=0, n_rows=1, op=_ffi.COLLATE_SEGID64))
+        plans = []
+        for key, local in self._csr.items():
+            index = getattr(out, key, None)
+            if index is None:
+                continue
+            adj = csr.Adjacency(index[1], index[0], n, n)
+            adj.transposes()
+            E = adj.n_entries
+            for a, (rp, col, perm) in zip((adj, adj._t_src), local):
+                if not self.has_long_rows:
+                    a.long_rows = a.n_long = None              # (known at construction: nothing to list, nothing to zero)
+                one = lambda src, dst, dst_start, src_start, add: _ffi.CollateDesc(
+                    src=src.data_ptr(), dst=dst, dst_start=at(dst_start), src_start=at(src_start), add=None if add is None else at(add),
+                    src_row_stride=0, dst_row_stride=0, n_rows=1, op=_ffi.COLLATE_COPY32 if add is None else _ffi.COLLATE_ADD32)
+                descs.append(one(self._zero, a.rowptr.data_ptr(), 'one_dst', 'zero_src', None))
+                if n:                         # rowptr[1:]: a cochain's inclusive local pointers + the entries in front of it
+                    descs.append(one(rp, a.rowptr.data_ptr() + 4, 'seg', 'row0', 'dst_' + key))
+                if E:
+                    descs.append(one(col, a.col.data_ptr(), 'dst_' + key, 'src_' + key, 'cell_off'))
+                    descs.append(one(perm, a.perm.data_ptr(), 'dst_' + key, 'src_' + key, 'dst_' + key))
+                a.built = True
+                plans.append(a)
+            csr.register_adjacency(index, adj)             # (held by the plan cache for as long as the index tensor lives)
+        L = _ffi.lib()
+        s = _ffi.stream_ptr(dev)
+        for i in range(0, len(descs), _ffi.MAX_COLLATE_DESCS):        # (23 descriptors at most: one launch)
+            chunk = descs[i:i + _ffi.MAX_COLLATE_DESCS]
+            _ffi.check(L.cwn_collate((_ffi.CollateDesc * len(chunk))(*chunk), len(chunk), B, s), 'cwn_collate')
+        if self.has_long_rows:
+            todo = [a for a in plans if a.long_rows is not None]
+            if todo:
+                arr = (_ffi.LongRowsDesc * len(todo))(*[
+                    _ffi.LongRowsDesc(rowptr=a.rowptr.data_ptr(), n_rows=a.n_dst, m_dev=None, long_rows=a.long_rows.data_ptr(),
+                                      n_long=a.n_long.data_ptr(), long_cap=a.long_cap) for a in todo])
+                _ffi.check(L.cwn_csr_long_rows(arr, len(todo), s), 'cwn_csr_long_rows')
+        tab.record_stream(torch.cuda.current_stream(dev))
+        out.ptr_dev = tab[off['seg']:off['seg'] + B + 1]
+        out._collate_tables = tab           # keep the tables alive until the launch has consumed them
+        out.__num_cochains__ = B
+        out.__num_cells__ = n
+        out.__num_cells_up__ = t['num_cells_up']
+        if self.dim > 0:
+            out.__num_cells_down__ = t['num_cells_down']
+        out.__num_cells_list__ = t['num_cells_list']
+        out.__slices__ = t['slices']
+        return out
+
+    def labels(self, idx: Sequence[int]) -> torch.Tensor:
+        """The labels of the cochains `idx`, in that order: equal to `collate(idx).y`, as one gather from the packed `y`
+        (source positions from the host's metadata: one small upload, no collate launch, no synchronisation)."""
+        pk = self._packs.get('y')
+        if pk is None:
+            raise ValueError('the packed cochains carry no labels')
+        idx = np.asarray(idx, dtype=np.int64).reshape(-1)
+        if idx.size and (idx.min() < 0 or idx.max() >= self.num):
+            raise IndexError(f'cochain numbers outside 0 .. {self.num - 1}')
+        ln, st = np.asarray(pk.length, dtype=np.int64)[idx], np.asarray(pk.start, dtype=np.int64)[idx]
+        src = np.repeat(st, ln) + (np.arange(int(ln.sum()), dtype=np.int64) - np.repeat(np.cumsum(ln) - ln, ln))
+        src_dev = torch.from_numpy(np.ascontiguousarray(src)).to(self.device, non_blocking=True)
+        return pk.data.index_select(0, src_dev).reshape((-1,) + self._y_tail)
+
+    # --------------------------------------------------------------------------------------------
+    def batch_indices(self, batch_size: int, shuffle: bool = False, seed: int = 0, drop_last: bool = False,
+                      epoch: int = 0) -> List[np.ndarray]:
+        """The index lists of one epoch: the cochains in order, or (`shuffle`) in the permutation drawn from `seed + epoch`."""
+        if batch_size < 1:
+            raise ValueError('batch_size >= 1')
+        order = np.arange(self.num, dtype=np.int64)
+        if shuffle:
+            order = np.random.default_rng(int(seed) + int(epoch)).permutation(self.num).astype(np.int64)
+        out = [order[lo:lo + batch_size] for lo in range(0, self.num, batch_size)]
+        return out[:-1] if drop_last and out and out[-1].size < batch_size else out
+
+    def batches(self, batch_size: int, shuffle: bool = False, seed: int = 0, drop_last: bool = False):
+        """One epoch of collated batches (the reference's `for batch in loader`): every batch one `collate` on the device, a
+        freshly drawn permutation per epoch -- `self.epoch` counts the epochs begun and moves with every call."""
+        epoch, self.epoch = self.epoch, self.epoch + 1
+        for idx in self.batch_indices(batch_size, shuffle, seed, drop_last, epoch):
+            yield self.collate(idx)
+
+
+class CochainForward:
+    """A model over a packed cochain dataset in the form evaluate.evaluate / evaluate.infer take as `forward`: `batches` are
+    the index arrays of the pass (PackedCochains.batch_indices), every batch is one `collate` and one eager forward, and the
+    labels come from `labels(idx)` -- one gather, no collate."""
+
+    def __init__(self, model, packed_cochains: PackedCochains):
+        self.model, self.packed = model, packed_cochains
+        self.sb = self                       # (evaluate reads the dataset as forward.sb.packed)
+
+    def run_epoch(self, batches) -> List[torch.Tensor]:
+        return [self.model(self.packed.collate(idx)) for idx in batches]

@@ -7,7 +7,11 @@ Every layer is ONE launch (ops.oriented_layer, csrc/cwn_oriented.hip) forward an
 backward.  The loop is plain autograd with torch.optim.Adam over CochainBatch inputs (train.TrainStep and the static
 batches take ComplexBatch).
 
-    python examples/train_flow.py [--model edge_orient|edge_mpnn] [--nonlinearity id|tanh|relu] [--epochs 40]   (needs an MI355X)
+--packed keeps the cochains in HBM (packed.PackedCochains): every batch is one collate launch that also brings the layers'
+CSR plans (no host collate, no per-batch sort), the head runs as ops.flow_head (models.FUSED_FLOW_HEAD is turned on), and the
+test pass goes through evaluate.evaluate with the labels gathered by `labels(idx)`.
+
+    python examples/train_flow.py [--packed] [--model edge_orient|edge_mpnn] [--nonlinearity id|tanh|relu] [--epochs 40]   (needs an MI355X)
 """
 import argparse
 import math
@@ -18,10 +22,11 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from cwn_amd import csr                                                  # noqa: E402
+from cwn_amd import csr, evaluate, models                                # noqa: E402
 from cwn_amd.complex import CochainBatch                                 # noqa: E402
 from cwn_amd.evaluate import Evaluator                                   # noqa: E402
 from cwn_amd.models import EdgeMPNN, EdgeOrient                          # noqa: E402
+from cwn_amd.packed import CochainForward, PackedCochains                # noqa: E402
 from cwn_amd.synthetic import edge_flows                                 # noqa: E402
 
 
@@ -42,6 +47,7 @@ def main():
     ap.add_argument('--layers', type=int, default=4)
     ap.add_argument('--hidden', type=int, default=64)
     ap.add_argument('--lr', type=float, default=1e-3)
+    ap.add_argument('--packed', action='store_true', help='device-resident dataset, one-launch collate with plans, fused head')
     args = ap.parse_args()
     dev = torch.device('cuda', 0)
     train, test = edge_flows(args.train, args.side, seed=0), edge_flows(args.test, args.side, seed=1)
@@ -54,6 +60,8 @@ def main():
     opt = torch.optim.Adam(model.parameters(), lr=args.lr)
     sched = torch.optim.lr_scheduler.StepLR(opt, step_size=20, gamma=0.5)
     evaluator = Evaluator('accuracy')
+    if args.packed:
+        return train_packed(args, model, opt, sched, evaluator, train, test, dev)
     test_batches = batches_of(test, args.batch, dev)
     test_x = [b.x.clone() for b in test_batches]                 # (the models write every layer's features into their batch)
     gen = torch.Generator().manual_seed(0)
@@ -82,6 +90,32 @@ def main():
         acc = evaluator.eval({'y_pred': torch.cat(preds), 'y_true': torch.cat(ys)})
         print(f'epoch {epoch}: lr {opt.param_groups[0]["lr"]:.3e}, train loss {sum(losses) / len(losses):.4f}, test accuracy {acc:.3f} '
               f'({len(losses)} steps in {dt * 1e3:.1f} ms)')
+    csr.check_errors(dev)
+
+
+def train_packed(args, model, opt, sched, evaluator, train, test, dev):
+    """The same experiment over packed.PackedCochains: shuffled batches by one collate launch each, the fused head."""
+    models.FUSED_FLOW_HEAD = True
+    packed_train, packed_test = PackedCochains(train, dev), PackedCochains(test, dev)
+    test_forward, test_idx = CochainForward(model, packed_test), packed_test.batch_indices(args.batch)
+    for epoch in range(args.epochs):
+        model.train()
+        t0 = time.perf_counter()
+        losses = []
+        for b in packed_train.batches(args.batch, shuffle=True, seed=0):       # a new permutation every epoch
+            opt.zero_grad(set_to_none=True)
+            loss = torch.nn.functional.cross_entropy(model(b), b.y.view(-1))
+            loss.backward()
+            opt.step()
+            losses.append(loss.detach())
+        losses = [float(l) for l in losses]
+        dt = time.perf_counter() - t0
+        if not all(math.isfinite(l) for l in losses):
+            raise SystemExit(f'epoch {epoch}: a non-finite loss')
+        sched.step()
+        acc, test_loss = evaluate.evaluate(test_forward, test_idx, evaluator, 'classification')
+        print(f'epoch {epoch}: lr {opt.param_groups[0]["lr"]:.3e}, train loss {sum(losses) / len(losses):.4f}, test accuracy {acc:.3f}, '
+              f'test loss {test_loss:.4f} ({len(losses)} steps in {dt * 1e3:.1f} ms, head route {model.last_head_route})')
     csr.check_errors(dev)
 
 

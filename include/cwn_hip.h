@@ -1255,6 +1255,61 @@ int cwn_target_head_bwd_f32(const float* dlogits, int64_t lddl, const float* x, 
                             cwn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The edge-flow readout head (csrc/cwn_flow_head.hip): the end of EdgeOrient / EdgeMPNN, forward and backward, float32.
+ *
+ * Replaces `torch.abs` -> global pooling over the batch vector -> lin1 -> ReLU -> lin2 (mp/models.py:531-545, :600-614):
+ *
+ *     pooled[c, :] = sum over the rows r of cochain c of f(x[r, :])     f = |.| (take_abs) or identity
+ *                                                                       [ / max(rows, 1) when mean ]
+ *     out[c, :]    = W2 relu(W1 pooled[c, :] + b1) + b2
+ *
+ *   - x [N, K] row stride ldx; ptr: DEVICE int64 [C + 1], the collate's `ptr` (the rows of cochain c are ptr[c] ..
+ *     ptr[c + 1] - 1; ascending, ptr[0] = 0, ptr[C] = N; values outside [0, N] are clamped, so nothing outside x is read
+ *     or written whatever it holds); W1 [H, K] and W2 [O, H] contiguous, b1 [H] / b2 [O] or NULL; out [C, O] row stride
+ *     ldout; pooled_out [C, K] and h_out [C, H] (the PRE-activation) contiguous or NULL: what the backward needs.
+ *     1 <= K, H <= CWN_FLOW_HEAD_MAX_WIDTH, 1 <= O <= CWN_FLOW_HEAD_MAX_OUT.
+ *   - N and C are HOST counts: there is NO m_dev and no static batch reaches these launches.
+ *   - A cochain's rows are cut into chunks of CWN_FLOW_HEAD_CHUNK consecutive rows counted from ITS first row (a chunk never
+ *     spans two cochains); launch 1 stores every chunk's sum to `workspace`, launch 2 (one workgroup per cochain) adds them
+ *     in chunk order and runs lin1 / ReLU / lin2.  At most two launches, no atomics.  Inside a chunk a column's rows are
+ *     added in an order fixed by K and the chunk's row count; 16-byte loads when K % 4 == 0, x is 16-byte aligned and
+ *     ldx % 4 == 0, element loads otherwise, in the SAME order.  lin1 / lin2: one fmaf chain over k ascending from 0 per
+ *     output, then the bias add.  So out[c, :] has the same bits for the cochain alone, at any place of any batch, on every run.
+ *   - A cochain without rows pools to zeros.  ReLU hands a NaN on (torch.relu); a NaN or Inf among a cochain's rows reaches
+ *     that cochain's row of out alone.
+ *   - workspace: caller-owned, 16-byte aligned, at least the number of floats the workspace query returns for (N, C, K); its
+ *     contents afterwards are unspecified.
+ *
+ * The backward, given g_out [C, O] (row stride ldg), h (the forward's h_out) and x:
+ *     ds = W2^T g      dh = ds where h > 0, else 0 (a NaN h hands ds on: torch's threshold_backward)
+ *     dpooled = W1^T dh [ / max(rows, 1) when mean ]
+ *     dx[r, :] = sgn(x[r, :]) * dpooled[c(r), :]   with sgn(0) = 0 (torch's gradient of abs);  dpooled[c(r), :] for identity
+ *   - dx [N, K] row stride lddx or NULL (the data gradient is skipped); every row of every cochain is written exactly
+ *     once, a cochain's rows by several workgroups (one per chunk); dx must not be x.  dh_out [C, H] contiguous or NULL.
+ *   - The weight gradients are sums over C rows and go through cwn_gemm_tn_f32: dW1 = dh^T pooled, db1 = sum_c dh,
+ *     dW2 = g^T relu(h), db2 = sum_c g.
+ *   - Two launches (one when dx is NULL), no atomics; the same workspace rule.
+ *
+ * Both launchers validate on the host before the first HIP call, neither allocates nor synchronises.  CWN_ERR_BAD_ARG: a
+ * width outside its range, take_abs / mean other than 0 / 1, N < 0, C < 0, a row stride below its width, x NULL with
+ * N > 0, ptr / W1 / W2 / out / g_out / h / workspace NULL with C > 0.  CWN_ERR_TOO_LARGE: N, C or the grid beyond int32.
+ * CWN_ERR_ALIGN: a float pointer off 4 bytes, ptr off 8, workspace off 16.  CWN_ERR_WORKSPACE: a workspace smaller than
+ * asked for.  C == 0: CWN_OK, nothing is launched.
+ * ------------------------------------------------------------------------------------------ */
+#define CWN_FLOW_HEAD_MAX_WIDTH 128 /* widest K / H: the oriented layer's own range */
+#define CWN_FLOW_HEAD_MAX_OUT 64    /* widest O */
+#define CWN_FLOW_HEAD_CHUNK 128     /* rows of a cochain per chunk */
+size_t cwn_flow_head_workspace_floats(int64_t N, int64_t C, int32_t K);
+int cwn_flow_head_f32(const float* x, int64_t N, int64_t ldx, const int64_t* ptr, int64_t C, const float* W1, const float* b1,
+                      const float* W2, const float* b2, float* out, int64_t ldout, float* pooled_out, float* h_out, int32_t K,
+                      int32_t H, int32_t O, int32_t take_abs, int32_t mean, float* workspace, size_t workspace_floats,
+                      cwn_stream_t stream);
+int cwn_flow_head_bwd_f32(const float* g_out, int64_t ldg, const float* h, const float* x, int64_t N, int64_t ldx,
+                          const int64_t* ptr, int64_t C, const float* W1, const float* W2, float* dx, int64_t lddx, float* dh_out,
+                          int32_t K, int32_t H, int32_t O, int32_t take_abs, int32_t mean, float* workspace,
+                          size_t workspace_floats, cwn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * The float64 dense path (csrc/cwn_dense_f64.hip): the Linear layers of a double model, inference only.
  *
  * The strongly-regular-graph experiments (exp/test_sr.py: SparseCIN in double, hidden 16, batches of 8 graphs) put
