@@ -26,6 +26,7 @@ EXPORTS = ('cwn_abi_version', 'cwn_error_string', 'cwn_target_arch', 'cwn_csr_wo
            'cwn_oriented_layer_f32', 'cwn_oriented_dz_f32',
            'cwn_target_head_f32', 'cwn_target_head_bwd_f32', 'cwn_target_head_bwd_workspace_bytes',
            'cwn_flow_head_f32', 'cwn_flow_head_bwd_f32', 'cwn_flow_head_workspace_floats',
+           'cwn_flow_head_dev_f32', 'cwn_flow_head_bwd_dev_f32', 'cwn_table_advance',
            'cwn_linear_many_f64', 'cwn_update_chain_f64', 'cwn_update_chain_f32', 'cwn_linear_stats_f32',
            'cwn_linear_wide_f32',
            'cwn_aggregate_act_f32', 'cwn_aggregate_act_f64',
@@ -652,6 +653,14 @@ def lib():
     L.cwn_flow_head_bwd_f32.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                         C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]
+    # (the counted forms: n_dev and c_dev in front of the workspace)
+    L.cwn_flow_head_dev_f32.restype = C.c_int
+    L.cwn_flow_head_dev_f32.argtypes = L.cwn_flow_head_f32.argtypes[:18] + [C.c_void_p, C.c_void_p] + L.cwn_flow_head_f32.argtypes[18:]
+    L.cwn_flow_head_bwd_dev_f32.restype = C.c_int
+    L.cwn_flow_head_bwd_dev_f32.argtypes = (L.cwn_flow_head_bwd_f32.argtypes[:18] + [C.c_void_p, C.c_void_p]
+                                            + L.cwn_flow_head_bwd_f32.argtypes[18:])
+    L.cwn_table_advance.restype = C.c_int
+    L.cwn_table_advance.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.cwn_lift_create.restype = C.c_void_p
     L.cwn_lift_create.argtypes = [C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int]
     L.cwn_lift_size.restype = C.c_int64
@@ -989,6 +998,41 @@ def flow_head_bwd(g: torch.Tensor, h: torch.Tensor, x: torch.Tensor, ptr_dev: to
                                       dh.data_ptr(), K, H, O, int(take_abs), int(mean), ws.data_ptr(), ws.numel(), stream_ptr(dev)),
           'cwn_flow_head_bwd_f32')
     return dx, dh
+
+
+def flow_head_counted(x: torch.Tensor, ptr_dev: torch.Tensor, n_dev: Optional[torch.Tensor], c_dev: torch.Tensor, w1, b1, w2, b2,
+                      take_abs: bool, mean: bool, keep: bool):
+    """`flow_head` under a capacity (cwn_flow_head_dev_f32): x [N, K] and ptr_dev [C + 1] are capacity-sized, `c_dev` / `n_dev` device
+    int64 words with the live cochains / rows (n_dev None: ptr_dev[*c_dev]).  Rows of out / pooled / h of absent cochains are zeros."""
+    N, K = x.shape
+    Cn, H, O = ptr_dev.numel() - 1, w1.size(0), w2.size(0)
+    dev = x.device
+    out = torch.empty(Cn, O, dtype=torch.float32, device=dev)
+    pooled = torch.empty(Cn, K, dtype=torch.float32, device=dev) if keep else None
+    h = torch.empty(Cn, H, dtype=torch.float32, device=dev) if keep else None
+    ws = _flow_workspace(N, Cn, K, dev)
+    check(lib().cwn_flow_head_dev_f32(x.data_ptr() if N else None, N, x.stride(0) if N > 1 else K, ptr_dev.data_ptr(), Cn, w1.data_ptr(),
+                                      ptr(b1), w2.data_ptr(), ptr(b2), out.data_ptr(), O, ptr(pooled), ptr(h), K, H, O, int(take_abs),
+                                      int(mean), ptr(n_dev), c_dev.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr(dev)),
+          'cwn_flow_head_dev_f32')
+    return out, pooled, h
+
+
+def flow_head_counted_bwd(g: torch.Tensor, h: torch.Tensor, x: torch.Tensor, ptr_dev: torch.Tensor, n_dev: Optional[torch.Tensor],
+                          c_dev: torch.Tensor, w1, w2, take_abs: bool, mean: bool, dx: Optional[torch.Tensor]):
+    """dh [C, H] (zeros for absent cochains) of cwn_flow_head_bwd_dev_f32; `dx` [N, K] (or None: skipped) is the caller's: its rows at
+    or beyond the live count are not written."""
+    N, K = x.shape
+    Cn, H, O = ptr_dev.numel() - 1, w1.size(0), w2.size(0)
+    dev = x.device
+    dh = torch.empty(Cn, H, dtype=torch.float32, device=dev)
+    ws = _flow_workspace(N, Cn, K, dev)
+    check(lib().cwn_flow_head_bwd_dev_f32(g.data_ptr(), g.stride(0) if Cn > 1 else O, h.data_ptr(), x.data_ptr() if N else None, N,
+                                          x.stride(0) if N > 1 else K, ptr_dev.data_ptr(), Cn, w1.data_ptr(), w2.data_ptr(), ptr(dx),
+                                          dx.stride(0) if dx is not None and N > 1 else K, dh.data_ptr(), K, H, O, int(take_abs),
+                                          int(mean), ptr(n_dev), c_dev.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr(dev)),
+          'cwn_flow_head_bwd_dev_f32')
+    return dh
 
 
 # False: the row bands of a weight gradient are added with fp32 atomics (fastest: 1.48 ms ZINC training

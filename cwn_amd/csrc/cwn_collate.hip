@@ -217,7 +217,29 @@ __global__ __launch_bounds__(256) void collate_guard_kernel(int64_t* __restrict_
     if (threadIdx.x == 0) atomicOr(err, CWN_ERR_BIT_CAPACITY);
 }
 
+// ---- the next batch of an epoch whose tables the host cut in advance (include/cwn_hip.h: cwn_table_advance) ------------------------
+// One workgroup: row *cursor of `epoch` into `table` (zeros past the last row: the tables of a batch without cochains), then
+// the cursor moves on by one.  Every thread reads the cursor before the barrier, one writes it behind it.
+__global__ __launch_bounds__(kTabThreads) void table_advance_kernel(const int64_t* __restrict__ epoch, int64_t n_rows, int64_t row_len,
+                                                                    int64_t* __restrict__ cursor, int64_t* __restrict__ table) {
+    const int64_t cur = *cursor;
+    const bool past = cur < 0 || cur >= n_rows;
+    const int64_t* const src = epoch + (past ? 0 : cur) * row_len;
+    for (int64_t q = threadIdx.x; q < row_len; q += kTabThreads) table[q] = past ? 0 : src[q];
+    __syncthreads();
+    if (threadIdx.x == 0 && !past) *cursor = cur + 1;
+}
+
 }  // namespace
+
+extern "C" int cwn_table_advance(const int64_t* epoch, int64_t n_rows, int64_t row_len, int64_t* cursor, int64_t* table,
+                                 cwn_stream_t stream_) {
+    if (epoch == nullptr || cursor == nullptr || table == nullptr || n_rows < 1 || row_len < 1) return CWN_ERR_BAD_ARG;
+    if (((uintptr_t)epoch | (uintptr_t)cursor | (uintptr_t)table) % 8 != 0) return CWN_ERR_ALIGN;
+    if (row_len >= INT32_MAX) return CWN_ERR_TOO_LARGE;
+    table_advance_kernel<<<dim3(1), dim3(kTabThreads), 0, (hipStream_t)stream_>>>(epoch, n_rows, row_len, cursor, table);
+    return hipGetLastError() == hipSuccess ? CWN_OK : CWN_ERR_LAUNCH;
+}
 
 extern "C" int cwn_collate_guard(int64_t* tables, int32_t D, int32_t K, int64_t B, int32_t n_slots, int64_t slot_stride,
                                  const int64_t* caps, int32_t* err_flag, cwn_stream_t stream_) {

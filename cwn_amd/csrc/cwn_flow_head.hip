@@ -30,6 +30,13 @@
 // workspace; launch 2 (one workgroup per slot) dx[r, :] = sgn(x[r, :]) dpooled[c, :] over the chunk's rows, every row of
 // every cochain written exactly once.
 //
+// The counted form (cwn_flow_head_dev_f32 / cwn_flow_head_bwd_dev_f32: a capacity-sized batch inside a captured graph) runs the
+// SAME kernels: N and C of the launch are capacities, every workgroup reads the live cochain count (*c_dev) and the live row
+// total (*n_dev, or ptr[live cochains]) first and works as if the launch had been given those -- slots, chunks, clamps and sums
+// are the ones of the host-count launch over the trimmed tensors, so the bits are.  A workgroup whose slot lies behind the last
+// live one leaves at once; a workgroup of an absent cochain (c >= the live count) writes zeros to its rows of out / pooled / h
+// (forward) and dh / dpooled (backward) and reads nothing else.
+//
 // LDS (static): pool 4 KiB; head 128 x 33 + 256 + 128 floats = 18432 B; bwd 128 + 64 floats.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -57,6 +64,15 @@ __device__ __forceinline__ void cochain_rows(const int64_t* __restrict__ ptr, in
     start = clamp_row(ptr[c], N);
     end = clamp_row(ptr[c + 1], N);
     if (end < start) end = start;
+}
+
+// The counted form: N and C arrive as capacities and become the live counts, clamped to them (c_dev NULL: host counts, as given).
+__device__ __forceinline__ void live_counts(const int64_t* __restrict__ ptr, const int64_t* __restrict__ n_dev,
+                                            const int64_t* __restrict__ c_dev, int64_t& N, int64_t& C) {
+    if (c_dev == nullptr) return;
+    const int64_t c = *c_dev;
+    C = c < 0 ? 0 : (c > C ? C : c);
+    N = clamp_row(n_dev != nullptr ? *n_dev : ptr[C], N);
 }
 
 // The cochain that owns slot b: the largest c < C with first(c) <= b, by a 64-ary search (every lane of the wave takes part).
@@ -119,10 +135,13 @@ __device__ __forceinline__ float4 abs4(float4 a) { return make_float4(fabsf(a.x)
 template <bool VEC>
 __global__ __launch_bounds__(kThreads) void flow_pool_kernel(const float* __restrict__ x, int64_t N, int64_t ldx,
                                                              const int64_t* __restrict__ ptr, int64_t C, int K, int take_abs,
-                                                             float* __restrict__ ws) {
+                                                             float* __restrict__ ws, const int64_t* __restrict__ n_dev,
+                                                             const int64_t* __restrict__ c_dev) {
     __shared__ float4 part[kThreads];
     const int tid = threadIdx.x;
     const int64_t b = blockIdx.x;
+    live_counts(ptr, n_dev, c_dev, N, C);
+    if (b >= N / kChunk + C) return;                          // (behind the last live slot: nothing is touched)
     int64_t c, r0, r1;
     if (!slot_chunk(ptr, C, N, b, tid & 63, c, r0, r1)) return;
     const int cols = (K + 3) >> 2;
@@ -182,12 +201,20 @@ __global__ __launch_bounds__(kThreads) void flow_head_kernel(const float* __rest
                                                              const float* __restrict__ W1, const float* __restrict__ b1,
                                                              const float* __restrict__ W2, const float* __restrict__ b2,
                                                              float* __restrict__ out, int64_t ldout, float* __restrict__ pooled_out,
-                                                             float* __restrict__ h_out, int K, int H, int O, int mean) {
+                                                             float* __restrict__ h_out, int K, int H, int O, int mean, int64_t C,
+                                                             const int64_t* __restrict__ n_dev, const int64_t* __restrict__ c_dev) {
     __shared__ float wt[kMaxW * kWld];
     __shared__ float pl[kThreads];
     __shared__ float sh[kMaxW];
     const int tid = threadIdx.x;
     const int64_t c = blockIdx.x;
+    live_counts(ptr, n_dev, c_dev, N, C);
+    if (c >= C) {                                             // an absent cochain of a capacity-sized batch: zeros, nothing read
+        if (tid < O) out[c * ldout + tid] = 0.f;
+        if (pooled_out != nullptr && tid < K) pooled_out[c * K + tid] = 0.f;
+        if (h_out != nullptr && tid < H) h_out[c * H + tid] = 0.f;
+        return;
+    }
     int64_t start, end;
     cochain_rows(ptr, c, N, start, end);
     const int64_t rows = end - start;
@@ -223,11 +250,18 @@ __global__ __launch_bounds__(kThreads) void flow_head_bwd_small_kernel(const flo
                                                                        const int64_t* __restrict__ ptr, int64_t N,
                                                                        const float* __restrict__ W1, const float* __restrict__ W2,
                                                                        float* __restrict__ dh_out, float* __restrict__ dpooled, int K, int H,
-                                                                       int O, int mean) {
+                                                                       int O, int mean, int64_t C, const int64_t* __restrict__ n_dev,
+                                                                       const int64_t* __restrict__ c_dev) {
     __shared__ float gs[kMaxO];
     __shared__ float dhs[kMaxW];
     const int tid = threadIdx.x;
     const int64_t c = blockIdx.x;
+    live_counts(ptr, n_dev, c_dev, N, C);
+    if (c >= C) {                                             // an absent cochain: its row of g / h is never read
+        if (dh_out != nullptr && tid < H) dh_out[c * H + tid] = 0.f;
+        if (tid < K) dpooled[c * K + tid] = 0.f;
+        return;
+    }
     if (tid < O) gs[tid] = g[c * ldg + tid];
     __syncthreads();
     if (tid < H) {
@@ -256,8 +290,11 @@ __device__ __forceinline__ float sgn_times(float x, float d) { return x > 0.f ? 
 template <bool VEC>
 __global__ __launch_bounds__(kThreads) void flow_head_dx_kernel(const float* __restrict__ x, int64_t N, int64_t ldx,
                                                                 const int64_t* __restrict__ ptr, int64_t C, int K, int take_abs,
-                                                                const float* __restrict__ dpooled, float* __restrict__ dx, int64_t lddx) {
+                                                                const float* __restrict__ dpooled, float* __restrict__ dx, int64_t lddx,
+                                                                const int64_t* __restrict__ n_dev, const int64_t* __restrict__ c_dev) {
     const int tid = threadIdx.x;
+    live_counts(ptr, n_dev, c_dev, N, C);
+    if ((int64_t)blockIdx.x >= N / kChunk + C) return;        // (behind the last live slot: rows at or beyond the count stay as they are)
     int64_t c, r0, r1;
     if (!slot_chunk(ptr, C, N, (int64_t)blockIdx.x, tid & 63, c, r0, r1)) return;
     const int cols = (K + 3) >> 2;
@@ -300,61 +337,97 @@ extern "C" size_t cwn_flow_head_workspace_floats(int64_t N, int64_t C, int32_t K
     return (size_t)((N / kChunk + C) * (int64_t)K);
 }
 
-extern "C" int cwn_flow_head_f32(const float* x, int64_t N, int64_t ldx, const int64_t* ptr, int64_t C, const float* W1,
-                                 const float* b1, const float* W2, const float* b2, float* out, int64_t ldout, float* pooled_out,
-                                 float* h_out, int32_t K, int32_t H, int32_t O, int32_t take_abs, int32_t mean, float* workspace,
-                                 size_t workspace_floats, cwn_stream_t stream_) {
+// Both forms of the forward: host counts (n_dev = c_dev = NULL) and the counted one (N, C capacities).
+static int flow_head_fwd(const float* x, int64_t N, int64_t ldx, const int64_t* ptr, int64_t C, const float* W1, const float* b1,
+                         const float* W2, const float* b2, float* out, int64_t ldout, float* pooled_out, float* h_out, int32_t K, int32_t H,
+                         int32_t O, int32_t take_abs, int32_t mean, const int64_t* n_dev, const int64_t* c_dev, bool counted,
+                         float* workspace, size_t workspace_floats, cwn_stream_t stream_) {
     const int bad = check_shapes(N, C, ldx, K, H, O, take_abs, mean);
     if (bad != CWN_OK) return bad;
     if (ldout < O) return CWN_ERR_BAD_ARG;
     if (N > 0 && x == nullptr) return CWN_ERR_BAD_ARG;
     if (C > 0 && (ptr == nullptr || W1 == nullptr || W2 == nullptr || out == nullptr || workspace == nullptr)) return CWN_ERR_BAD_ARG;
+    if (counted && C > 0 && c_dev == nullptr) return CWN_ERR_BAD_ARG;
     for (const void* p : {(const void*)x, (const void*)W1, (const void*)b1, (const void*)W2, (const void*)b2, (const void*)out,
                           (const void*)pooled_out, (const void*)h_out})
         if (!al4(p)) return CWN_ERR_ALIGN;
-    if (!al8(ptr) || !al16(workspace)) return CWN_ERR_ALIGN;
+    if (!al8(ptr) || !al8(n_dev) || !al8(c_dev) || !al16(workspace)) return CWN_ERR_ALIGN;
     if (C == 0) return CWN_OK;
     if (workspace_floats < cwn_flow_head_workspace_floats(N, C, K)) return CWN_ERR_WORKSPACE;
     hipStream_t stream = (hipStream_t)stream_;
     const unsigned slots = (unsigned)(N / kChunk + C);
     if (N > 0) {
         if (K % 4 == 0 && al16(x) && ldx % 4 == 0)
-            flow_pool_kernel<true><<<dim3(slots), dim3(kThreads), 0, stream>>>(x, N, ldx, ptr, C, K, take_abs, workspace);
+            flow_pool_kernel<true><<<dim3(slots), dim3(kThreads), 0, stream>>>(x, N, ldx, ptr, C, K, take_abs, workspace, n_dev, c_dev);
         else
-            flow_pool_kernel<false><<<dim3(slots), dim3(kThreads), 0, stream>>>(x, N, ldx, ptr, C, K, take_abs, workspace);
+            flow_pool_kernel<false><<<dim3(slots), dim3(kThreads), 0, stream>>>(x, N, ldx, ptr, C, K, take_abs, workspace, n_dev, c_dev);
         if (hipGetLastError() != hipSuccess) return CWN_ERR_LAUNCH;
     }
     flow_head_kernel<<<dim3((unsigned)C), dim3(kThreads), 0, stream>>>(workspace, ptr, N, W1, b1, W2, b2, out, ldout, pooled_out, h_out, K, H,
-                                                                       O, mean);
+                                                                       O, mean, C, n_dev, c_dev);
     return hipGetLastError() == hipSuccess ? CWN_OK : CWN_ERR_LAUNCH;
 }
 
-extern "C" int cwn_flow_head_bwd_f32(const float* g_out, int64_t ldg, const float* h, const float* x, int64_t N, int64_t ldx,
-                                     const int64_t* ptr, int64_t C, const float* W1, const float* W2, float* dx, int64_t lddx,
-                                     float* dh_out, int32_t K, int32_t H, int32_t O, int32_t take_abs, int32_t mean, float* workspace,
-                                     size_t workspace_floats, cwn_stream_t stream_) {
+static int flow_head_bwd(const float* g_out, int64_t ldg, const float* h, const float* x, int64_t N, int64_t ldx, const int64_t* ptr,
+                         int64_t C, const float* W1, const float* W2, float* dx, int64_t lddx, float* dh_out, int32_t K, int32_t H, int32_t O,
+                         int32_t take_abs, int32_t mean, const int64_t* n_dev, const int64_t* c_dev, bool counted, float* workspace,
+                         size_t workspace_floats, cwn_stream_t stream_) {
     const int bad = check_shapes(N, C, ldx, K, H, O, take_abs, mean);
     if (bad != CWN_OK) return bad;
     if (ldg < O || (dx != nullptr && lddx < K)) return CWN_ERR_BAD_ARG;
     if (N > 0 && dx != nullptr && take_abs && x == nullptr) return CWN_ERR_BAD_ARG;
     if (C > 0 && (ptr == nullptr || g_out == nullptr || h == nullptr || W1 == nullptr || W2 == nullptr || workspace == nullptr))
         return CWN_ERR_BAD_ARG;
+    if (counted && C > 0 && c_dev == nullptr) return CWN_ERR_BAD_ARG;
     if (dx != nullptr && dx == x) return CWN_ERR_BAD_ARG;
     for (const void* p : {(const void*)g_out, (const void*)h, (const void*)x, (const void*)W1, (const void*)W2, (const void*)dx,
                           (const void*)dh_out})
         if (!al4(p)) return CWN_ERR_ALIGN;
-    if (!al8(ptr) || !al16(workspace)) return CWN_ERR_ALIGN;
+    if (!al8(ptr) || !al8(n_dev) || !al8(c_dev) || !al16(workspace)) return CWN_ERR_ALIGN;
     if (C == 0) return CWN_OK;
     if (workspace_floats < cwn_flow_head_workspace_floats(N, C, K)) return CWN_ERR_WORKSPACE;
     hipStream_t stream = (hipStream_t)stream_;
     flow_head_bwd_small_kernel<<<dim3((unsigned)C), dim3(kThreads), 0, stream>>>(g_out, ldg, h, ptr, N, W1, W2, dh_out, workspace, K, H, O,
-                                                                                 mean);
+                                                                                 mean, C, n_dev, c_dev);
     if (hipGetLastError() != hipSuccess) return CWN_ERR_LAUNCH;
     if (dx == nullptr || N == 0) return CWN_OK;
     const unsigned slots = (unsigned)(N / kChunk + C);
     if (K % 4 == 0 && (!take_abs || (al16(x) && ldx % 4 == 0)) && al16(dx) && lddx % 4 == 0)
-        flow_head_dx_kernel<true><<<dim3(slots), dim3(kThreads), 0, stream>>>(x, N, ldx, ptr, C, K, take_abs, workspace, dx, lddx);
+        flow_head_dx_kernel<true><<<dim3(slots), dim3(kThreads), 0, stream>>>(x, N, ldx, ptr, C, K, take_abs, workspace, dx, lddx, n_dev, c_dev);
     else
-        flow_head_dx_kernel<false><<<dim3(slots), dim3(kThreads), 0, stream>>>(x, N, ldx, ptr, C, K, take_abs, workspace, dx, lddx);
+        flow_head_dx_kernel<false><<<dim3(slots), dim3(kThreads), 0, stream>>>(x, N, ldx, ptr, C, K, take_abs, workspace, dx, lddx, n_dev, c_dev);
     return hipGetLastError() == hipSuccess ? CWN_OK : CWN_ERR_LAUNCH;
+}
+
+extern "C" int cwn_flow_head_f32(const float* x, int64_t N, int64_t ldx, const int64_t* ptr, int64_t C, const float* W1,
+                                 const float* b1, const float* W2, const float* b2, float* out, int64_t ldout, float* pooled_out,
+                                 float* h_out, int32_t K, int32_t H, int32_t O, int32_t take_abs, int32_t mean, float* workspace,
+                                 size_t workspace_floats, cwn_stream_t stream) {
+    return flow_head_fwd(x, N, ldx, ptr, C, W1, b1, W2, b2, out, ldout, pooled_out, h_out, K, H, O, take_abs, mean, nullptr, nullptr, false,
+                         workspace, workspace_floats, stream);
+}
+
+extern "C" int cwn_flow_head_bwd_f32(const float* g_out, int64_t ldg, const float* h, const float* x, int64_t N, int64_t ldx,
+                                     const int64_t* ptr, int64_t C, const float* W1, const float* W2, float* dx, int64_t lddx,
+                                     float* dh_out, int32_t K, int32_t H, int32_t O, int32_t take_abs, int32_t mean, float* workspace,
+                                     size_t workspace_floats, cwn_stream_t stream) {
+    return flow_head_bwd(g_out, ldg, h, x, N, ldx, ptr, C, W1, W2, dx, lddx, dh_out, K, H, O, take_abs, mean, nullptr, nullptr, false,
+                         workspace, workspace_floats, stream);
+}
+
+extern "C" int cwn_flow_head_dev_f32(const float* x, int64_t N, int64_t ldx, const int64_t* ptr, int64_t C, const float* W1,
+                                     const float* b1, const float* W2, const float* b2, float* out, int64_t ldout, float* pooled_out,
+                                     float* h_out, int32_t K, int32_t H, int32_t O, int32_t take_abs, int32_t mean, const int64_t* n_dev,
+                                     const int64_t* c_dev, float* workspace, size_t workspace_floats, cwn_stream_t stream) {
+    return flow_head_fwd(x, N, ldx, ptr, C, W1, b1, W2, b2, out, ldout, pooled_out, h_out, K, H, O, take_abs, mean, n_dev, c_dev, true,
+                         workspace, workspace_floats, stream);
+}
+
+extern "C" int cwn_flow_head_bwd_dev_f32(const float* g_out, int64_t ldg, const float* h, const float* x, int64_t N, int64_t ldx,
+                                         const int64_t* ptr, int64_t C, const float* W1, const float* W2, float* dx, int64_t lddx,
+                                         float* dh_out, int32_t K, int32_t H, int32_t O, int32_t take_abs, int32_t mean,
+                                         const int64_t* n_dev, const int64_t* c_dev, float* workspace, size_t workspace_floats,
+                                         cwn_stream_t stream) {
+    return flow_head_bwd(g_out, ldg, h, x, N, ldx, ptr, C, W1, W2, dx, lddx, dh_out, K, H, O, take_abs, mean, n_dev, c_dev, true,
+                         workspace, workspace_floats, stream);
 }

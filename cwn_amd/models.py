@@ -773,10 +773,20 @@ def _edge_readout(model, data, x: torch.Tensor, include_partial: bool):
     """The end of EdgeOrient.forward / EdgeMPNN.forward behind the layers; `model.last_head_route` names the route taken:
       'fused'    FUSED_FLOW_HEAD on, x float32 on the GPU within ops.flow_head's limits, a batch that carries `ptr_dev`
                  (packed.PackedCochains.collate), no active dropout, no `include_partial`: ops.flow_head.
-      'generic'  everything else: torch.abs, global_pool, the Linear modules -- unchanged."""
+      'generic'  everything else: torch.abs, global_pool, the Linear modules -- unchanged.
+      'counted'  a capacity-sized batch (static_cochains.StaticCochainBatch, which carries `head_counts`: the device words
+                 with its live rows and cochains): ops.flow_head_counted, whatever the switch says -- no other route knows
+                 which rows exist.  static_graph.StaticCochainForward / StaticCochainTrainStep refuse what it does not take."""
     n = getattr(data, 'num_cochains', None)
     ptr_dev = getattr(data, 'ptr_dev', None)
     lin1, lin2 = model.lin1, model.lin2
+    counts = getattr(data, 'head_counts', None)
+    if counts is not None:
+        if include_partial or (model.training and model.dropout_rate > 0):
+            raise NotImplementedError(f'{type(model).__name__}: include_partial / active dropout on a static batch of cochains')
+        model.last_head_route = 'counted'
+        return ops.flow_head_counted(x, ptr_dev, counts[1], lin1.weight, lin1.bias, lin2.weight, lin2.bias, n_dev=counts[0],
+                                     abs=not model.fully_invar, mean=model.readout == 'mean')
     if (FUSED_FLOW_HEAD and not include_partial and ptr_dev is not None and n is not None
             and not (model.training and model.dropout_rate > 0)
             and ops.flow_head_applies(x, ptr_dev, lin1.weight, lin1.bias, lin2.weight, lin2.bias)

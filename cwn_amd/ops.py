@@ -2114,6 +2114,7 @@ class _OrientedLayer(torch.autograd.Function):
         out = _oriented_launch(x, up, dn, w_self, w_up if up is not None else None, w_dn if dn is not None else None, act, H,
                                agg_out=agg)
         ctx.up, ctx.dn, ctx.act = up, dn, act
+        ctx.params = (w_self, w_up, w_dn)             # (the parameters themselves: `_grad_target` asks for their .grad)
         ctx.save_for_backward(x, out, agg, w_self, w_up, w_dn)
         return out
 
@@ -2134,20 +2135,25 @@ class _OrientedLayer(torch.autograd.Function):
             wait_ready([t[0] for t in (t_up, t_dn) if t is not None])
             dx = _oriented_launch(dz, t_up, t_dn, w_self, w_up if up is not None else None, w_dn if dn is not None else None,
                                   _ffi.ACT_ID, w, trans=True)
-        grads, descs = [None, None, None], []
+        grads, descs, in_place, targets = [None, None, None], [], True, []
         for k, (W, X, ldx) in enumerate(((w_self, x, x.stride(0)), (w_up, agg, 2 * w),
                                          (w_dn, None if agg is None else agg[:, w:], 2 * w))):
             if W is None or not need[1 + k]:
                 continue
-            dW = torch.zeros(H, w, dtype=torch.float32, device=dev)
-            grads[k] = dW
+            # inside accumulate_into_grad() (train.TrainStep) the product is added onto the parameter's .grad by the launch
+            # itself: no zero fill, no add kernel of autograd's, and the launch may wait for the end of the backward
+            dW = _grad_target(ctx.params[k])
+            if dW is None:
+                dW = grads[k] = torch.zeros(H, w, dtype=torch.float32, device=dev)
+                in_place = False
+            targets.append(dW)
             if n == 0 or (k == 1 and up is None) or (k == 2 and dn is None):
                 continue                                              # (an absent stream: its aggregate is zero)
             descs.append(_ffi.GemmTnDesc(dZ=dz.data_ptr(), X=X.data_ptr(), X2=None, in_scale=None, in_shift=None, in_scale2=None,
-                                         in_shift2=None, dW=dW.data_ptr(), db=None, M=n, lddz=H, ldx=ldx, ldx2=0, lddw=w,
+                                         in_shift2=None, dW=dW.data_ptr(), db=None, M=n, lddz=H, ldx=ldx, ldx2=0, lddw=dW.stride(0),
                                          N=H, K=w, K2=0, in_relu=0))
         if descs:
-            _ffi.gemm_tn(descs, dev, keep=[dz, x, agg, grads])
+            _ffi.gemm_tn(descs, dev, keep=[dz, x, agg, targets], deferrable=ACCUMULATE_INTO_GRAD and in_place)
         return (dx, grads[0], grads[1], grads[2], None, None, None, None)
 
 
@@ -2397,6 +2403,87 @@ def flow_head(x: Tensor, ptr_dev: Tensor, lin1_w: Tensor, lin1_b: Optional[Tenso
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, w1, b1, w2, b2)):
         return _FlowHead.apply(x, ptr_dev, w1, b1, w2, b2, bool(abs), bool(mean))
     return _ffi.flow_head(x, ptr_dev, w1, b1, w2, b2, bool(abs), bool(mean), keep=False)[0]
+
+
+class _FlowHeadCounted(torch.autograd.Function):
+    """_FlowHead under a capacity: cwn_flow_head_dev_f32 / cwn_flow_head_bwd_dev_f32 with the live counts on the device; dW / db
+    through cwn_gemm_tn_f32 over the capacity rows with m_dev = the live cochains.  Rows of dx beyond the live rows are unwritten."""
+
+    @staticmethod
+    def forward(ctx, x, ptr_dev, n_dev, c_dev, w1, b1, w2, b2, take_abs, mean):
+        out, pooled, h = _ffi.flow_head_counted(x, ptr_dev, n_dev, c_dev, w1, b1, w2, b2, take_abs, mean, keep=True)
+        ctx.save_for_backward(x, ptr_dev, c_dev, w1, w2, pooled, h)
+        ctx.n_dev = n_dev
+        ctx.params = {'w1': w1, 'b1': b1, 'w2': w2, 'b2': b2}
+        ctx.flags = (take_abs, mean, b1 is not None, b2 is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, ptr_dev, c_dev, w1, w2, pooled, h = ctx.saved_tensors
+        take_abs, mean, has_b1, has_b2 = ctx.flags
+        need = ctx.needs_input_grad
+        g = _f32c(g, 'grad')
+        dev = x.device
+        Cn, (H, K), O = int(g.size(0)), w1.shape, int(w2.size(0))
+        dx = torch.empty_like(x, memory_format=torch.contiguous_format) if need[0] else None
+        dh = _ffi.flow_head_counted_bwd(g, h, x, ptr_dev, ctx.n_dev, c_dev, w1, w2, take_abs, mean, dx)
+        grads, descs, in_place, targets = {}, [], True, []
+        for name, wanted, b_wanted, dZ, X, N_, K_, relu in (('1', need[4], has_b1 and need[5], dh, pooled, H, K, 0),
+                                                           ('2', need[6], has_b2 and need[7], g, h, O, H, 1)):
+            if not (wanted or b_wanted):
+                continue
+            # (inside accumulate_into_grad() the launch adds onto the parameters' .grad itself, as _OrientedLayer's does)
+            dW = _grad_target(ctx.params['w' + name]) if wanted else None
+            db = _grad_target(ctx.params['b' + name]) if b_wanted else None
+            if dW is None:
+                dW = torch.zeros(N_, K_, dtype=torch.float32, device=dev)      # (a throw-away one when only db is wanted)
+                grads['w' + name] = dW if wanted else None
+                in_place = in_place and not wanted
+            if b_wanted and db is None:
+                db = grads['b' + name] = torch.zeros(N_, dtype=torch.float32, device=dev)
+                in_place = False
+            targets += [dW, db]
+            descs.append(_ffi.GemmTnDesc(dZ=dZ.data_ptr(), X=X.data_ptr(), X2=None, in_scale=None, in_shift=None, in_scale2=None,
+                                         in_shift2=None, dW=dW.data_ptr(), db=_ffi.ptr(db), M=Cn, lddz=N_, ldx=K_, ldx2=0,
+                                         lddw=dW.stride(0), N=N_, K=K_, K2=0, in_relu=relu))
+        if descs:
+            # M = the capacity of THIS head's cochains, its count c_dev: mapped here for a launch that runs now; a deferred one
+            # (in-place targets only) runs at the end of the backward under the static batch's own mapping of that capacity
+            if ACCUMULATE_INTO_GRAD and in_place and _ffi._tn_queue is not None:
+                _ffi.gemm_tn(descs, dev, keep=[dh, pooled, g, h, targets], deferrable=True)
+            else:
+                with _ffi.dynamic_rows({Cn: c_dev.data_ptr()}):
+                    _ffi._flush_descs(descs, dev)
+        return (dx, None, None, None, grads.get('w1'), grads.get('b1'), grads.get('w2'), grads.get('b2'), None, None)
+
+
+def flow_head_counted(x: Tensor, ptr_dev: Tensor, c_dev: Tensor, lin1_w: Tensor, lin1_b: Optional[Tensor], lin2_w: Tensor,
+                      lin2_b: Optional[Tensor], *, n_dev: Optional[Tensor] = None, abs: bool = True, mean: bool = False) -> Tensor:
+    """`flow_head` for a capacity-sized batch (static_cochains.StaticCochainBatch inside a captured graph): x [N, K] and
+    ptr_dev [C + 1] have the CAPACITY's sizes, `c_dev` is a device int64 word with the cochains of the batch, `n_dev` one with
+    its rows (None: ptr_dev[*c_dev]).  The same arithmetic and the same bits as `flow_head` over the live rows and cochains;
+    out [C, O] with zeros for absent cochains; the backward leaves the rows of dx beyond the live rows unwritten and sums the
+    weight gradients over the live cochains.  Same operands and limits as `flow_head`; no fallback."""
+    x = _rows_operand(x, 'x', 2, **_FLOW_ROWS)
+    w1, w2 = _rows_operand(lin1_w, 'lin1_w', 2, **_FLOW_ROWS), _rows_operand(lin2_w, 'lin2_w', 2, **_FLOW_ROWS)
+    b1, b2 = _rows_operand(lin1_b, 'lin1_b', 1, **_FLOW_ROWS), _rows_operand(lin2_b, 'lin2_b', 1, **_FLOW_ROWS)
+    if x is None or w1 is None or w2 is None:
+        raise TypeError('flow_head_counted: x, lin1_w and lin2_w are required')
+    for name, t, n in (('ptr_dev', ptr_dev, None), ('c_dev', c_dev, 1), ('n_dev', n_dev, 1)):
+        if t is None and name == 'n_dev':
+            continue
+        if not isinstance(t, Tensor) or t.dtype != torch.long or not t.is_cuda or not t.is_contiguous() or t.dim() != 1 \
+                or (n is not None and t.numel() != n) or t.numel() < 1:
+            raise TypeError(f'flow_head_counted: {name} must be a contiguous int64 vector on the GPU'
+                            + (' of one element' if n else ' of C + 1 >= 1 entries'))
+    if not (w1.is_contiguous() and w2.is_contiguous()) or not _flow_shapes_ok(x, ptr_dev, w1, b1, w2, b2):
+        raise ValueError(f'flow_head_counted takes x [N, K], contiguous lin1_w [H, K], lin2_w [O, H] with 1 <= K, H <= '
+                         f'{_ffi.FLOW_HEAD_MAX_WIDTH}, 1 <= O <= {_ffi.FLOW_HEAD_MAX_OUT} and biases [H] / [O]: x {tuple(x.shape)}, '
+                         f'lin1_w {tuple(w1.shape)}, lin2_w {tuple(w2.shape)}')
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, w1, b1, w2, b2)):
+        return _FlowHeadCounted.apply(x, ptr_dev, n_dev, c_dev, w1, b1, w2, b2, bool(abs), bool(mean))
+    return _ffi.flow_head_counted(x, ptr_dev, n_dev, c_dev, w1, b1, w2, b2, bool(abs), bool(mean), keep=False)[0]
 
 
 # ------------------------------------------------------------------------------------------------

@@ -547,6 +547,53 @@ def cochain_tables(meta: dict, idx) -> dict:
     return out
 
 
+EPOCH_COUNTS = ('rows', 'upper_index', 'lower_index', 'cochains')     # the live counts at the end of an epoch-table row
+
+
+def cochain_epoch_layout(meta: dict, B: int) -> dict:
+    """Where every table of a batch of at most B cochains sits in one row of the epoch tables (`cochain_epoch_tables`): name ->
+    offset in int64 elements, and 'len' (a multiple of 2: rows stay 16-byte aligned).  Per packed key `dst_<key>` [B + 1] and
+    `src_<key>` [B]; `cell_off` [2 B] (both rows of an index); `seg` [B + 1] (the batch vector's segments = the head's `ptr`);
+    `row0` [B] (first cell of every cochain in packed order), `one_dst` [B + 1] and `zero_src` [B] (a plan's leading zero);
+    `counts` [8]: EPOCH_COUNTS, then zeros."""
+    off, run = {}, 0
+    for name, n in ([(p + key, B + (p == 'dst_')) for key in meta['keys'] for p in ('dst_', 'src_')]
+                    + [('cell_off', 2 * B), ('seg', B + 1), ('row0', B), ('one_dst', B + 1), ('zero_src', B), ('counts', 8)]):
+        off[name] = run
+        run += n
+    off['len'] = run + (run & 1)
+    return off
+
+
+def cochain_epoch_tables(meta: dict, batches, B: int) -> np.ndarray:
+    """int64 [len(batches), layout['len']]: row j holds `cochain_tables(meta, batches[j])` in the layout above, written for a
+    batch of CAPACITY B -- the places of the cochains a shorter batch does not have are empty segments behind the last one
+    (dst / seg / cell_off repeat the total, src / row0 are 0), so that a collate over B segments copies nothing for them.
+    numpy in, numpy out: one array per epoch, one H2D copy."""
+    lay = cochain_epoch_layout(meta, B)
+    row0 = np.cumsum(meta['n_cells']) - meta['n_cells']
+    out = np.zeros((len(batches), lay['len']), dtype=np.int64)
+    for j, idx in enumerate(batches):
+        t = cochain_tables(meta, idx)
+        b, r = t['B'], out[j]
+        if b > B:
+            raise ValueError(f'batch {j}: {b} cochains exceed the capacity {B}')
+        idx = np.asarray(idx, dtype=np.int64).reshape(-1)
+        for key in meta['keys']:
+            o = lay['dst_' + key]
+            r[o:o + b + 1], r[o + b + 1:o + B + 1] = t['dst'][key], t['dst'][key][-1]
+            r[lay['src_' + key]:lay['src_' + key] + b] = t['src'][key]
+        for o in (lay['cell_off'], lay['cell_off'] + B):
+            r[o:o + b], r[o + b:o + B] = t['cell_off'], t['num_cells']
+        o = lay['seg']
+        r[o:o + b + 1], r[o + b + 1:o + B + 1] = t['seg'], t['num_cells']
+        r[lay['row0']:lay['row0'] + b] = row0[idx]
+        r[lay['one_dst'] + 1:lay['one_dst'] + B + 1] = 1
+        c = lay['counts']
+        r[c:c + 4] = [t['num_cells']] + [int(t['dst'][k][-1]) if k in t['dst'] else 0 for k in ('upper_index', 'lower_index')] + [b]
+    return out
+
+
 class PackedCochains:
     """A dataset of `Cochain`s (CPU tensors, one `dim`) packed on `device`; `collate(idx)` is the CochainBatch
     `CochainBatch.from_cochain_list([cochains[i] for i in idx]).to(device)` would be, field for field, from ONE small H2D

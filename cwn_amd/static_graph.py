@@ -713,3 +713,133 @@ class RoutedTrainStep:
                         out[order[k + j]] = losses[j].clone()
                 k += n
         return out
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# The edge-flow experiment: captured forwards and training steps over a static batch of COCHAINS
+# ------------------------------------------------------------------------------------------------------------------------------
+# EdgeOrient / EdgeMPNN over static_cochains.StaticCochainBatch: per step
+#     cwn_table_advance -> cwn_collate -> L x cwn_oriented_layer_f32 (m_dev) -> cwn_flow_head_dev_f32
+# and, for a training step, the fused cross-entropy over the cochains that exist, the backward (cwn_oriented_dz_f32, the layer
+# kernel over the transposed plans, cwn_gemm_tn_f32, cwn_flow_head_bwd_dev_f32) and FlatAdam -- captured once on ONE stream
+# (no parallel branches), replayed for every batch of every epoch.  The step drivers are the ones of the complexes: only what
+# fills the buffers and what restores the inputs differs.
+from .static_cochains import StaticCochainBatch      # noqa: E402
+
+
+def refuse_unsupported_flow_model(model: torch.nn.Module, who: str, training: bool = False) -> None:
+    """NotImplementedError naming the layer or option a static batch of cochains does not serve.  Served: models.EdgeOrient /
+    EdgeMPNN in float32 whose every layer is ONE cwn_oriented_layer_f32 launch (bias-free Linear or ZeroUpdate update maps,
+    'add' reduces, one of the five activations, widths <= 128) and whose head is the counted one (sum / mean readout, no
+    active dropout, widths <= 128, <= 64 outputs): only those launches know which rows of the capacity exist."""
+    from . import models
+    from .layers import FUSED_ORIENTED, OrientedConv, ZeroUpdate, _act_name_of_function
+    if not isinstance(model, (models.EdgeOrient, models.EdgeMPNN)):
+        raise NotImplementedError(f'{who}: {type(model).__name__} is not served by a static batch of cochains (EdgeOrient / EdgeMPNN)')
+    if any(p.dtype != torch.float32 for p in model.parameters()):
+        raise NotImplementedError(f'{who}: float64 parameters: the oriented layer and the counted head compute in float32 only')
+    if not FUSED_ORIENTED:
+        raise NotImplementedError(f'{who}: CWN_FUSED_ORIENTED=0 (layers.FUSED_ORIENTED = False): only the one-launch layer carries '
+                                  'the row count')
+    for i, conv in enumerate(model.convs):
+        name = f'convs.{i}'
+        if not isinstance(conv, OrientedConv) or not conv._own_hooks():
+            raise NotImplementedError(f'{who}: {name} ({type(conv).__name__}) is not a plain OrientedConv')
+        for attr in ('update_nn', 'update_up_nn', 'update_down_nn'):
+            nn = getattr(conv, attr)
+            if type(nn) is ZeroUpdate:
+                continue
+            if type(nn) is not torch.nn.Linear:
+                raise NotImplementedError(f'{who}: {name}.{attr} is a user callable ({type(nn).__name__}), not a bias-free '
+                                          'torch.nn.Linear or a ZeroUpdate')
+            if nn.bias is not None:
+                raise NotImplementedError(f'{who}: {name}.{attr} is a Linear with a bias: ops.oriented_layer serves bias-free maps')
+            if max(nn.in_features, nn.out_features) > _ffi.ORIENTED_MAX_WIDTH:
+                raise NotImplementedError(f'{who}: {name}.{attr} is {nn.in_features} -> {nn.out_features} wide, beyond the layer '
+                                          f"launch's limit of {_ffi.ORIENTED_MAX_WIDTH}")
+        for attr in ('aggr_up', 'aggr_down'):
+            if (getattr(conv, attr) or 'add') != 'add':
+                raise NotImplementedError(f"{who}: {name} reduces with {attr}={getattr(conv, attr)!r}, not 'add'")
+        if _act_name_of_function(conv.act_fn) is None:
+            raise NotImplementedError(f'{who}: {name}.act_fn is not one of the activations of models.get_nonlinearity')
+    if model.readout not in ('sum', 'mean'):
+        raise NotImplementedError(f'{who}: readout {model.readout!r} (the counted head pools with sum or mean)')
+    if training and model.dropout_rate > 0:
+        raise NotImplementedError(f'{who}: dropout_rate = {model.dropout_rate}: dropout inside the head is not served by the '
+                                  'counted head')
+    (H, K), O = model.lin1.weight.shape, int(model.lin2.weight.size(0))
+    if max(H, K) > _ffi.FLOW_HEAD_MAX_WIDTH or O > _ffi.FLOW_HEAD_MAX_OUT:
+        raise NotImplementedError(f'{who}: a head of width {max(H, K)} with {O} outputs is beyond the counted head\'s limits '
+                                  f'({_ffi.FLOW_HEAD_MAX_WIDTH} / {_ffi.FLOW_HEAD_MAX_OUT})')
+
+
+def _require_static_cochains(static, who: str) -> None:
+    if not isinstance(static, StaticCochainBatch):
+        raise TypeError(f'{who} takes a static_cochains.StaticCochainBatch')
+    x = static.input
+    if x is None or x.dtype != torch.float32:
+        raise NotImplementedError(f'{who}: the packed cochains carry no float32 features')
+
+
+class StaticCochainForward(StaticForward):
+    """`model(batch)` (eval, no autograd) for the next batches of a StaticCochainBatch as one captured graph: per batch advance
+    -> collate -> the layers -> the counted head.  `run_epoch(batches)` returns the per-batch predictions (rows of absent
+    cochains dropped); `.sb.packed` is the dataset, so evaluate.evaluate / infer take it the way they take CochainForward.
+    `include_partial` is not served (the model is called with its default)."""
+
+    def __init__(self, model: torch.nn.Module, static: StaticCochainBatch):
+        _require_static_cochains(static, 'StaticCochainForward')
+        refuse_unsupported_flow_model(model, 'StaticCochainForward')
+        self.model, self.sb = model, static
+        self._graphs = {}
+
+    def _state(self):
+        # The oriented layer and the head read the parameters where they live (no packed copies): new VALUES need no new
+        # capture -- a test pass after every training epoch replays --, a parameter that has MOVED (FlatAdam re-homes them) does.
+        return tuple(p.data_ptr() for p in self.model.parameters())
+
+    def _run(self, n_slots: Optional[int] = None) -> List[torch.Tensor]:
+        sb = self.sb
+        outs = []
+        for _ in range(sb.S if n_slots is None else int(n_slots)):
+            sb.advance()
+            sb.restore()
+            with sb.dynamic():
+                outs.append(self.model(sb.batch))
+            sb.restore()
+        return outs
+
+
+class StaticCochainTrainStep(StaticTrainStep):
+    """Optimisation steps (zero_grad, forward, cross-entropy / the task's fused criterion over the cochains that exist,
+    backward, FlatAdam) on the next batches of a StaticCochainBatch, captured ONCE on one stream: StaticTrainStep's interface
+    (`lr`, `opt` with its param group, `state_dict` / `load_state_dict`, `step`, `run_epoch(batches)` -> losses, a shorter
+    captured sequence for an epoch's tail).  A step past the epoch's last batch changes nothing.  World size 1."""
+
+    def __init__(self, model: torch.nn.Module, static: StaticCochainBatch, task_type: str = 'classification', lr: float = 1e-3,
+                 use_graph: bool = True, optimizer=None):
+        _require_static_cochains(static, 'StaticCochainTrainStep')
+        refuse_unsupported_flow_model(model, 'StaticCochainTrainStep', training=True)
+        if static.y_per_cochain != 1:
+            raise NotImplementedError('StaticCochainTrainStep: one label per cochain (the fused criterion counts the cochains that '
+                                      f'exist); this dataset has {static.y_per_cochain}')
+        self.sb = static
+        TrainStep.__init__(self, model, [static.batch] * static.S, task_type=task_type, lr=lr, use_graph=use_graph,
+                           optimizer=optimizer, rebuild_plans=False, stages=1)
+        if self.world > 1:
+            raise NotImplementedError('StaticCochainTrainStep: data-parallel training is not served')
+        self.inputs = [[static.input]] * static.S          # the inputs ARE the static buffer (the collate writes through raw pointers)
+        self._actives = [static.active] * static.S
+        self._global_active = torch.ones(1, dtype=torch.int64, device=static.device)
+
+    @staticmethod
+    def _cochains(b):
+        return [b]
+
+    def _n_local(self, i: int):
+        return self._actives[i]                       # (the weight of a rank in a gradient all-reduce: world size 1, never read)
+
+    def _forward_backward(self, i: int, pieces=None):
+        self.sb.advance()
+        with self.sb.dynamic():
+            return TrainStep._forward_backward(self, i, pieces)

@@ -1310,6 +1310,37 @@ int cwn_flow_head_bwd_f32(const float* g_out, int64_t ldg, const float* h, const
                           size_t workspace_floats, cwn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The counted form of that head: the same kernels under a CAPACITY (a static batch of cochains inside a captured graph).
+ *
+ * Every argument the two launches above take, with the same meaning, limits and arithmetic, and two device words:
+ *   - N and C are CAPACITIES: x / dx hold N rows, ptr holds C + 1 entries, out / pooled_out / h_out / g_out / h / dh_out
+ *     hold C rows, the workspace is the one the query returns for (N, C, K), the grids are sized by them.
+ *   - c_dev: DEVICE int64, the cochains of the batch (required when C > 0; clamped to [0, C]).  n_dev: DEVICE int64, the
+ *     rows of x that exist (clamped to [0, N]), or NULL: ptr[*c_dev] is read instead.  Both are read by every workgroup
+ *     before anything else; entries of ptr at or beyond *c_dev + 1 are never read.
+ *   - Slots, chunks, clamps and the order of every sum are those of the host-count launch given (n, c) = (*n_dev, *c_dev)
+ *     over the first n rows and c cochains: out, pooled_out, h_out, dh_out of a live cochain and dx of a live row have the
+ *     SAME BITS as that launch writes.
+ *   - A workgroup whose slot lies behind the last live one (slot >= n / CWN_FLOW_HEAD_CHUNK + c) leaves without touching
+ *     memory: rows of dx in [n, N) are NEVER WRITTEN (rows of x there are never read: they may hold anything, NaN included),
+ *     rows of the workspace behind the live slots neither.
+ *   - A cochain in [c, C) is ABSENT: its rows of out, pooled_out and h_out (forward) and of dh_out (backward) are written
+ *     as ZEROS, its row of g_out / h is never read -- so a reduction over all C rows downstream (cwn_gemm_tn_f32 without
+ *     a count) adds nothing for it; with m_dev = c_dev the rows are not read at all.
+ *   - The weight gradients go through cwn_gemm_tn_f32 with M = C and m_dev = c_dev.
+ * Same error codes; in addition CWN_ERR_BAD_ARG for c_dev NULL with C > 0 and CWN_ERR_ALIGN for n_dev / c_dev off 8 bytes.
+ * C == 0: CWN_OK, nothing is launched.  Nothing is allocated or synchronised: graph-capturable.
+ * ------------------------------------------------------------------------------------------ */
+int cwn_flow_head_dev_f32(const float* x, int64_t N, int64_t ldx, const int64_t* ptr, int64_t C, const float* W1, const float* b1,
+                          const float* W2, const float* b2, float* out, int64_t ldout, float* pooled_out, float* h_out, int32_t K,
+                          int32_t H, int32_t O, int32_t take_abs, int32_t mean, const int64_t* n_dev, const int64_t* c_dev,
+                          float* workspace, size_t workspace_floats, cwn_stream_t stream);
+int cwn_flow_head_bwd_dev_f32(const float* g_out, int64_t ldg, const float* h, const float* x, int64_t N, int64_t ldx,
+                              const int64_t* ptr, int64_t C, const float* W1, const float* W2, float* dx, int64_t lddx,
+                              float* dh_out, int32_t K, int32_t H, int32_t O, int32_t take_abs, int32_t mean, const int64_t* n_dev,
+                              const int64_t* c_dev, float* workspace, size_t workspace_floats, cwn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * The float64 dense path (csrc/cwn_dense_f64.hip): the Linear layers of a double model, inference only.
  *
  * The strongly-regular-graph experiments (exp/test_sr.py: SparseCIN in double, hidden 16, batches of 8 graphs) put
@@ -1802,6 +1833,17 @@ int cwn_collate_tables(const int64_t* meta, int64_t num, int32_t D, int32_t K, c
 #define CWN_ERR_BIT_CAPACITY 32               /* *err_flag bit: a batch beyond the capacity of its static buffers was dropped */
 int cwn_collate_guard(int64_t* tables, int32_t D, int32_t K, int64_t B, int32_t n_slots, int64_t slot_stride, const int64_t* caps,
                       int32_t* err_flag, cwn_stream_t stream);
+
+/* The next batch of an epoch whose segment tables the HOST cut in advance (a dataset of cochains: static_cochains.py):
+ * epoch = device int64 [n_rows, row_len], one row per batch -- every table the collate descriptors of a capacity-sized batch
+ * point into and the batch's live counts, laid out as the caller likes; cursor = device int64, the row to take; table =
+ * device int64 [row_len], the fixed block the descriptors (and every m_dev / n_dev / c_dev of the step) point into.
+ *     table[:] = epoch[*cursor, :];  *cursor += 1          0 <= *cursor < n_rows
+ *     table[:] = 0                                          otherwise (a batch without cochains; the cursor stays)
+ * One workgroup, graph-capturable: a captured step begins with it and needs nothing from the host but the replay.  The
+ * launches of the previous step that read `table` lie in front of it in stream order.  CWN_ERR_BAD_ARG: a NULL pointer,
+ * n_rows < 1, row_len < 1; CWN_ERR_ALIGN: a pointer off 8 bytes; CWN_ERR_TOO_LARGE: row_len beyond int32. */
+int cwn_table_advance(const int64_t* epoch, int64_t n_rows, int64_t row_len, int64_t* cursor, int64_t* table, cwn_stream_t stream);
 
 /* Embedding lookup with a sum over index columns (torch.nn.Embedding for cols = 1; the OGB
  * Atom/BondEncoder sum over one table per integer feature column, mp/molec_models.py:44-52, 237-245):

@@ -13,9 +13,16 @@ thousands of adjacency entries per cochain), batch 64, EdgeOrient hidden 64 x 4 
   optimisation step    examples/train_flow.py's loop without and with --packed: wall time per step over epochs of shuffled
                        batches (collate, forward, loss, backward, Adam), the epochs of the two forms alternating.
 
+  optimisation step,   the --packed loop (one collate, ~120 launches issued from Python, torch.optim.Adam per step) against the
+  static               captured step of --static (static_graph.StaticCochainTrainStep over a static_cochains.StaticCochainBatch:
+                       advance, collate, forward, cross-entropy, backward and FlatAdam replayed from one hipGraph, an epoch's
+                       tables uploaded once), the epochs of the two forms alternating, every epoch a new permutation: never-seen
+                       batches.  Kernels per step from torch.profiler over one epoch of each form.
+
 Per scope and form: the median of the round values and the run-to-run spread, their 10th .. 90th percentile.
 
     python tools/bench_flow.py [--train 512] [--rounds 21] [--out profiles/flow_packed.md]
+    python tools/bench_flow.py --static-only [--slots 8] [--out profiles/flow_static.md]      the last scope alone
 
 Results are printed as a markdown table and appended to --out when given."""
 import argparse
@@ -40,15 +47,15 @@ def stats(ts):
     return ts[len(ts) // 2], ts[len(ts) // 10], ts[len(ts) * 9 // 10]
 
 
-def cell(ts, unit=''):
+def cell(ts, unit='', digits=1):
     m, lo, hi = stats(ts)
-    return f'{m:.1f} [{lo:.1f} .. {hi:.1f}]{unit}', m, hi - lo
+    return f'{m:.{digits}f} [{lo:.{digits}f} .. {hi:.{digits}f}]{unit}', m, hi - lo
 
 
-def verdict(old, new):
+def verdict(old, new, digits=1):
     (_, mo, so), (_, mn, sn) = cell(old), cell(new)
     spread = max(so, sn)
-    return f'{"yes" if mo - mn > spread else "no"} ({mo - mn:+.1f} against {spread:.1f}; x{mo / mn:.2f})'
+    return f'{"yes" if mo - mn > spread else "no"} ({mo - mn:+.{digits}f} against {spread:.{digits}f}; x{mo / mn:.2f})'
 
 
 def kernels_per_call(fn) -> int:
@@ -93,6 +100,56 @@ def host_batch(cochains, idx, parts=None):
     return b
 
 
+def static_scope(args, pc, lines):
+    """'optimisation step, static': the --packed loop against the captured step, alternating epoch by epoch."""
+    from cwn_amd.static_cochains import StaticCochainBatch
+    from cwn_amd.static_graph import StaticCochainTrainStep
+    B = args.batch
+    was = models.FUSED_FLOW_HEAD
+    models.FUSED_FLOW_HEAD = True
+    try:
+        torch.manual_seed(0)
+        m_packed = models.EdgeOrient(1, 2, args.layers, args.hidden, nonlinearity='id').to(DEV).train()
+        opt = torch.optim.Adam(m_packed.parameters(), lr=1e-3)
+        torch.manual_seed(0)
+        m_static = models.EdgeOrient(1, 2, args.layers, args.hidden, nonlinearity='id').to(DEV)
+        sb = StaticCochainBatch(pc, B, slots=args.slots)
+        step = StaticCochainTrainStep(m_static, sb, 'classification', lr=1e-3)
+        epoch = [0]
+
+        def run(form):
+            batches = pc.batch_indices(B, shuffle=True, seed=0, epoch=epoch[0])       # a permutation neither form has seen
+            epoch[0] += 1
+            if form == 'static':
+                step.run_epoch(batches, keep_losses=False)
+                return len(batches)
+            for idx in batches:
+                b = pc.collate(idx)
+                opt.zero_grad(set_to_none=True)
+                loss = torch.nn.functional.cross_entropy(m_packed(b), b.y.view(-1))
+                loss.backward()
+                opt.step()
+            return len(batches)
+        times, counts = {'packed': [], 'static': []}, {}
+        for r in range(args.rounds + 2):
+            for form in ('packed', 'static'):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                steps = run(form)
+                torch.cuda.synchronize()
+                if r >= 2:                                   # (two warm-up epochs per form: the captures)
+                    times[form].append((time.perf_counter() - t0) * 1e3 / steps)
+        counts['packed'] = kernels_per_call(lambda: run('packed')) / steps
+        # (the profiler does not list the kernels of a graph replay: the SAME launches issued one by one -- what the capture recorded)
+        counts['static'] = kernels_per_call(lambda: step._eager(0))
+        assert m_packed.last_head_route == 'fused' and m_static.last_head_route == 'counted'
+        lines.append(f'| optimisation step, static, ms (epochs of {steps} never-seen shuffled batches, {args.slots} steps per replay; '
+                     f'{counts["packed"]:.0f} against {counts["static"]:.0f} kernels per step) | {cell(times["packed"], digits=2)[0]} (--packed) | '
+                     f'{cell(times["static"], digits=2)[0]} (--static) | {verdict(times["packed"], times["static"], 2)} |')
+    finally:
+        models.FUSED_FLOW_HEAD = was
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--train', type=int, default=512)
@@ -103,6 +160,8 @@ def main():
     ap.add_argument('--rounds', type=int, default=21)
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--slots', type=int, default=8, help='steps per replay of the static form')
+    ap.add_argument('--static-only', action='store_true', help="the scope 'optimisation step, static' alone")
     args = ap.parse_args()
     B = args.batch
     cochains = edge_flows(args.train, args.side, seed=0)
@@ -117,6 +176,10 @@ def main():
              f'median [p10 .. p90]; '
              f'packing the dataset once (upload + the CSRs of every cochain): {t_pack * 1e3:.0f} ms', '',
              '| scope | parent route | packed / fused | faster by more than the larger spread |', '|---|---|---|---|']
+
+    if args.static_only:
+        static_scope(args, pc, lines)
+        return finish(lines, args)
 
     # ---- batch construction ----------------------------------------------------------------------------------------------------
     times = {'host': [], 'packed': []}
@@ -206,6 +269,11 @@ def main():
                      f'{verdict(times[False], times[True])} |')
     finally:
         models.FUSED_FLOW_HEAD = was
+    static_scope(args, pc, lines)
+    finish(lines, args)
+
+
+def finish(lines, args):
     text = '\n'.join(lines)
     print(text)
     if args.out:
