@@ -53,6 +53,14 @@ inline at::Tensor row_major(const at::Tensor& t) {      // ops._rowmajor
     return t;
 }
 
+inline at::Tensor row_major16(const at::Tensor& t) {    // ops._rowmajor16: an operand read 16 bytes at a time, no element-wise twin
+    at::Tensor r = row_major(t);
+    // (clone, not contiguous(): ONE row off 16 bytes is "contiguous" as it lies)
+    if ((reinterpret_cast<uintptr_t>(r.data_ptr()) & 15u) != 0 || (r.size(0) > 1 && r.stride(0) % 4 != 0))
+        return r.clone(at::MemoryFormat::Contiguous);
+    return r;
+}
+
 // ---- tensors a prepared record was derived from: unchanged since? ------------------------------------------------------------
 class TensorMarks {
  public:
@@ -197,8 +205,9 @@ class MlpCall {
         hold.reserve(2 * n_);
         int64_t off = 0;
         for (int i = 0; i < n_; ++i) {
-            hold.push_back(row_major(xs_up[i]));
-            hold.push_back(row_major(xs_b[i]));
+            const bool narrow = dims_[i].in_width > 0 && dims_[i].in_width < F_;      // (staged element-wise: any window)
+            hold.push_back(narrow ? row_major(xs_up[i]) : row_major16(xs_up[i]));
+            hold.push_back(narrow ? row_major(xs_b[i]) : row_major16(xs_b[i]));
             const at::Tensor &u = hold[2 * i], &b = hold[2 * i + 1];
             cwn_mlp_dim& a = dims_[i];
             a.x_up = u.data_ptr<float>();

@@ -1135,6 +1135,9 @@ def _head_parts(x):
         return None, 0
     blocks = list(x) if isinstance(x, (list, tuple)) else [x]
     blocks = [_f32c(b, 'x') for b in blocks]
+    # (cwn_head_f32 reads a row 16 bytes at a time: ONE row of a wider matrix is "contiguous" wherever it starts and whatever its
+    #  stride says)
+    blocks = [b.clone(memory_format=torch.contiguous_format) if b.data_ptr() % 16 or b.stride(0) % 4 else b for b in blocks]
     if len(blocks) > 1:
         w = int(blocks[0].size(1))
         if any(b.size(1) != w or b.size(0) != blocks[0].size(0) or b.stride(0) != blocks[0].stride(0) for b in blocks) \
@@ -1258,7 +1261,8 @@ class HeadLaunch:
             ld = blocks[0].stride(0)
             for b in blocks:
                 if (b.dtype != torch.float32 or b.dim() != 2 or b.size(0) != rows or b.size(1) != w or b.device != self.dev
-                        or (w > 1 and b.stride(1) != 1) or b.stride(0) != ld or (rows > 1 and ld < w)):
+                        or (w > 1 and b.stride(1) != 1) or b.stride(0) != ld or (rows > 1 and ld < w)
+                        or b.data_ptr() % 16 or ld % 4):       # (cwn_head_f32: 16-byte rows -- the long way copies)
                     return None
             D = self.arr[d]
             D.x, D.ldx = blocks[0].data_ptr(), ld
@@ -1454,9 +1458,11 @@ def dropout_apply(x: Tensor, rec: '_ffi.Dropout', out: Optional[Tensor] = None) 
     """out = x * multipliers(rec) over the last dimension's rows (cwn_dropout_f32)."""
     x2 = x if x.dim() == 2 else x.reshape(-1, x.size(-1) if x.dim() else 1)
     x2 = _rowmajor(x2, 'x')
+    M, N = int(x2.size(0)), int(x2.size(1))
     if out is None:
         out = torch.empty(x2.shape, dtype=torch.float32, device=x2.device)
-    M, N = int(x2.size(0)), int(x2.size(1))
+    elif out.dim() == 2:
+        _out_window(out, M, N, 'out')
     ld = lambda t: int(t.stride(0)) if t.size(0) > 1 else int(t.size(1))
     if M and N:
         _ffi.check(_ffi.lib().cwn_dropout_f32(x2.data_ptr(), out.data_ptr(), M, N, ld(x2), ld(out), rec, _ffi.dyn(M),
@@ -1513,6 +1519,28 @@ def _rowmajor(t: Tensor, name: str) -> Tensor:
     if t.size(0) > 1 and t.stride(0) < t.size(1):
         t = t.contiguous()
     return t
+
+
+def _rowmajor16(t: Tensor, name: str) -> Tensor:
+    """`_rowmajor` for an operand a kernel reads 16 bytes at a time with no element-wise twin (the F-wide inputs of
+    cwn_update_mlp_f32 / cwn_update_mlp3_f32): a window that starts off 16 bytes or whose row stride is no multiple of 4 is
+    copied, where the entry point would refuse it (include/cwn_hip.h, "OPERAND WINDOWS")."""
+    t = _rowmajor(t, name)
+    if t.data_ptr() % 16 or (t.size(0) > 1 and t.stride(0) % 4):
+        t = t.clone(memory_format=torch.contiguous_format)      # (not .contiguous(): ONE row off 16 bytes is "contiguous" as it lies)
+    return t
+
+
+def _out_window(out: Tensor, rows: int, cols: int, name: str) -> Tensor:
+    """A preallocated output handed to a launch by address and row stride: it has to BE row-major (a column window of a wider
+    matrix is) -- a transposed or column-strided view would receive a row-major image beside its own elements.  An output
+    cannot be copied the way `_rowmajor` copies an input: it is refused."""
+    if out.dim() != 2 or tuple(out.shape) != (rows, cols) or out.dtype != torch.float32:
+        raise ValueError(f'{name} must be a float32 [{rows}, {cols}] matrix (got {out.dtype} {tuple(out.shape)})')
+    if (cols > 1 and out.stride(1) != 1) or (rows > 1 and out.stride(0) < cols):
+        raise ValueError(f'{name} must be row-major (unit column stride, row stride >= {cols}); got strides {tuple(out.stride())}: '
+                         'a window of a wider matrix is fine, a transposed or column-strided view is not')
+    return out
 
 
 @dataclass
@@ -1629,6 +1657,9 @@ def run_gemm(gemms: Sequence[Gemm], device) -> List[Tensor]:
         if Y is None:
             Y = torch.empty(gm.X.size(0), gm.W.size(1 if gm.w_trans else 0), dtype=torch.float32,
                             device=device)
+        else:
+            _ffi.require_gpu(Y, 'out')
+            _out_window(Y, int(gm.X.size(0)), int(gm.W.size(1 if gm.w_trans else 0)), 'out')
         outs.append(Y)
         if Y.numel():
             descs.append(gm.desc(Y))
@@ -3532,7 +3563,8 @@ def update_mlp(dims: Sequence[MlpDim]) -> List[Tensor]:
     arr = (_ffi.MlpDim * len(dims))()
     outs, keep = [], []
     for i, D in enumerate(dims):
-        xu, xb = _rowmajor(D.x_up, 'x_up'), _rowmajor(D.x_b, 'x_b')
+        rm = _rowmajor if int(D.x_up.size(1)) < F else _rowmajor16     # (narrow inputs are staged element-wise: any window)
+        xu, xb = rm(D.x_up, 'x_up'), rm(D.x_b, 'x_b')
         w_in = int(xu.size(1))
         y = torch.empty(xu.size(0), F, dtype=torch.float32, device=dev)
         outs.append(y)
@@ -3586,7 +3618,7 @@ def update_mlp3(dims: Sequence[Mlp3Dim]) -> List[Tensor]:
     for i, D in enumerate(dims):
         a = arr[i]
         for k in range(3):
-            x = _rowmajor(D.xs[k], 'x')
+            x = _rowmajor16(D.xs[k], 'x')
             keep.append(x)
             a.x[k] = x.data_ptr()
             a.ldx[k] = x.stride(0) if x.size(0) > 1 else F
@@ -3658,7 +3690,8 @@ class MlpLaunch:
         outs = buf.split(rows)
         base, off, hold = buf.data_ptr(), 0, []
         for i in range(n):
-            xu, xb, M = _rowmajor(xs_up[i], 'x_up'), _rowmajor(xs_b[i], 'x_b'), rows[i]
+            rm = _rowmajor if self.w_in[i] < F else _rowmajor16
+            xu, xb, M = rm(xs_up[i], 'x_up'), rm(xs_b[i], 'x_b'), rows[i]
             hold += [xu, xb]                       # (a contiguous copy lives until the launch is enqueued)
             a = self.arr[i]
             a.x_up, a.x_b, a.y, a.M = xu.data_ptr(), xb.data_ptr(), base + off * 4 * F, M

@@ -34,6 +34,20 @@
  *     cwn_collate_guard, zeroes the counts of a batch beyond its capacities before any of them is read).
  *     tests/test_gpu_row_counts.py pins the contract per entry point at counts of 0, 1, the capacity and around every tile
  *     height.
+ *   - OPERAND WINDOWS.  A dense operand [rows, width] with a row stride of its own (ldx, ldx2, ldw, ldy, lddz, lddx, ldout ...)
+ *     may be a window of a wider matrix: a column block of a jumping-knowledge cat, one half of out[:, :F] | out[:, F:], a
+ *     weight half W[:, F:], a view of a capacity-sized buffer.  A kernel reads and writes the [rows, width] window of each
+ *     operand ONLY: what lies between `width` and the row stride is never written and never influences a result (a kernel
+ *     may LOAD it into a tile, inside the allocation, but discards it by selection, so a NaN there stays there).  Per-column
+ *     vectors (bias, scale, shift, mean, rstd, s1, s2 ...) are read over [0, width) only.  Each entry states its own
+ *     alignment and stride rule -- "16-B aligned, strides multiples of 4" for the kernels that have the 16-byte form only,
+ *     "4-byte alignment, 16-byte accesses where pointer, stride and widths allow, element by element otherwise" for those
+ *     with an element-wise twin -- and refuses everything else BEFORE launching, with nothing written: CWN_ERR_ALIGN for a
+ *     pointer off its alignment, CWN_ERR_BAD_ARG for a row stride below the width or not a multiple of 4 where 4 is asked
+ *     for (entries that answer a stride with CWN_ERR_ALIGN say so: cwn_norm_bwd_f32, cwn_gemm_bnb, cwn_target_head_*).
+ *     cwn_gemm_would_split / cwn_gemm_tn_would_split return 0 for a window their 16-byte kernels cannot take, and the
+ *     launch runs on the other kernel.  tests/test_gpu_windows.py pins the contract per f32 entry point;
+ *     tests/test_windows_host.py the refusals and the two predicates.
  */
 #ifndef CWN_HIP_H
 #define CWN_HIP_H
@@ -608,7 +622,7 @@ size_t cwn_layer_variant_lds_bytes(int32_t F, int32_t variant, int32_t max_gemm_
  * layout); bias / scale / shift per stage in the order
  * (1u, 2u, 1b, 2b, c), bias may be NULL.  At most cwn_update_mlp_max_rows() rows per dimension
  * (CWN_ERR_TOO_LARGE beyond; the same networks as grouped launches: cwn_gemm_f32).
- * Every pointer 16-B aligned, row strides multiples of 4; no workspace, no host sync.
+ * Every pointer 16-B aligned (CWN_ERR_ALIGN), row strides multiples of 4 (CWN_ERR_BAD_ARG); no workspace, no host sync.
  * ------------------------------------------------------------------------------------------ */
 typedef struct cwn_mlp_dim {
     const float* x_up;          /* [M, F], row stride ldx_up */
@@ -729,7 +743,8 @@ typedef struct cwn_bn_live {
  * (in_scale / in_shift per input column or NULL, in_relu bit 0: X, bit 1: X2).  Arithmetic: the exact three-way bf16
  * split of csrc/cwn_split.h (fp32 in, fp32 accumulate, fp32 out; the inference kernels' path), weights pre-packed by
  * cwn_update_mlp_pack_weights_f32 or its _many form: w_packed = the block that multiplies X, w2_packed the block that multiplies X2.
- * F = 64 or 128 = the width of X, X2 and Y; pointers 16-B aligned, strides multiples of 4.
+ * F = 64 or 128 = the width of X, X2 and Y; pointers 16-B aligned (CWN_ERR_ALIGN), strides multiples of 4 (CWN_ERR_BAD_ARG):
+ * any window of a wider matrix that keeps both, refused before the launch otherwise (the same for _ex and _bwd).
  * ------------------------------------------------------------------------------------------ */
 typedef struct cwn_stage_desc {
     const float* X;          /* [M, F] */
@@ -839,6 +854,11 @@ int cwn_dense_stage_bwd_f32(const cwn_stage_bwd_desc* descs_host, int n, int32_t
  *             col_sum / col_sumsq [CWN_STAT_ROWS(M), N] -- BatchNorm batch statistics, summed over
  *             the bands by cwn_bn_finalize_f32;
  *             then * out_scale[n] + out_shift[n] (BatchNorm eval), then ReLU if relu.
+ *   windows:  every matrix may be a window (see "Conventions"): any row stride >= its width, 4-byte alignment
+ *             (CWN_ERR_BAD_ARG / CWN_ERR_ALIGN).  The exact kernel moves 16 bytes a lane when X, X2, W and Y are 16-byte
+ *             aligned and ldx, ldx2, ldw, ldy, K and K2 are multiples of 4, and goes element by element otherwise, in
+ *             the same k order: the same bits.  X2 needs K % 4 == 0 (CWN_ERR_BAD_ARG).  The vectors are read element by
+ *             element: 4-byte alignment.
  * ------------------------------------------------------------------------------------------ */
 /* bands of 32 rows the statistics epilogue writes one partial sum for */
 #define CWN_STAT_ROWS(M) (((M) + 31) / 32)
@@ -888,7 +908,8 @@ typedef struct cwn_gemm_desc {
     int32_t flags;          /* CWN_GEMM_* bits, 0: none */
     int32_t pad_;
     const cwn_gemm_bnb* bnb;  /* HOST pointer or NULL, see the struct above: w_trans launches with 16-byte aligned operands and
-                               K <= 128 (the launch's tile shapes for K <= 128: any N); CWN_ERR_BAD_ARG otherwise */
+                               K <= 128 (the launch's tile shapes for K <= 128: any N); CWN_ERR_BAD_ARG otherwise -- except z / dz
+                               off 16 bytes or ldz / lddz no multiple of 4, which are checked first: CWN_ERR_ALIGN */
     const int64_t* m_dev;     /* (ABI 23) or NULL: the rows that exist (M = capacity, see "Conventions"): the workgroups walk the
                                * row tiles below *m_dev only, and the tile the count ends in stores its rows below the count
                                * only (ADD_OUT: adds onto) -- a static batch's message products used to be taken over the

@@ -56,6 +56,8 @@ class _Dim:
         N = sum(rows)
         self.x_full = torch.randn(N, K + 3, generator=g, dtype=F64).to(dtype)
         self.w_full = (torch.randn(H, K + 2, generator=g, dtype=F64) / K ** 0.5).to(dtype)
+        # (NaN beside both windows: a load that strays and is not discarded shows in the result)
+        self.x_full[:, K:] = self.w_full[:, 0] = self.w_full[:, K + 1:] = float('nan')
         self.b = torch.randn(H, generator=g, dtype=F64).to(dtype) if bias else None
         self.ptr = torch.tensor(np.concatenate([[0], np.cumsum(rows)]).astype(np.int64))
 

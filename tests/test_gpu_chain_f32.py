@@ -112,6 +112,7 @@ def test_update_chain_allocates_its_outputs_and_takes_strided_operands():
         net, n = _Net(F, H, seed=3), 70
         g = torch.Generator().manual_seed(4)
         wide_up, wide_b = 2 * torch.randn(n, F + 9, generator=g), 2 * torch.randn(n, F + 4, generator=g)
+        wide_up[:, :3] = wide_up[:, 3 + F:] = wide_b[:, F:] = float('nan')     # (beside the windows: nothing of it reaches a result)
         in_up, in_b = wide_up.to(DEV)[:, 3:3 + F], wide_b.to(DEV)[:, :F]
         assert in_up.stride(0) == F + 9 and in_b.stride(0) == F + 4
         ref = net.reference(wide_up[:, 3:3 + F], wide_b[:, :F], 'elu')

@@ -86,6 +86,7 @@ def test_linear_many_one_product_seven_products_and_weight_slices():
     items, refs = [], []
     for M, K, N, act, hb in shapes:
         wide, w, b = r(M, K + 3), r(N, K), (r(N) if hb else None)
+        wide[:, 0] = wide[:, K + 1:] = float('nan')                  # (beside the window: nothing of it reaches a result)
         x, xd = wide[:, 1:K + 1], wide.to(DEV)[:, 1:K + 1]          # x is a view with a row stride of K + 3
         assert M < 2 or xd.stride(0) == K + 3
         name = {None: 'id', 2: 'elu'}.get(act, act)
@@ -187,6 +188,7 @@ def test_update_chain_allocates_its_outputs_and_takes_strided_inputs():
     nets_dev = [copy.deepcopy(m).to(DEV) for m in nets]
     g = torch.Generator().manual_seed(4)
     wide_up, wide_b = torch.randn(n, F + 4, generator=g, dtype=F64), torch.randn(n, F + 2, generator=g, dtype=F64)
+    wide_up[:, :2] = wide_up[:, 2 + F:] = wide_b[:, F:] = float('nan')      # (beside the windows: nothing of it reaches a result)
     in_up, in_b = wide_up.to(DEV)[:, 2:2 + F], wide_b.to(DEV)[:, :F]
     assert in_up.stride(0) == F + 4 and in_b.stride(0) == F + 2
     with torch.no_grad():

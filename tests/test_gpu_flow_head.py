@@ -65,7 +65,8 @@ def test_forward_against_float64(K, O, C, mean):
     ptr = _ptr(rows)
     x = _x(int(ptr[-1]), K, seed=K + C)
     w = _weights(K, O, seed=3 * K + O)
-    wide = torch.zeros(x.size(0), K + 3, device=DEV)               # a row stride that is no multiple of 4: element loads
+    # a row stride that is no multiple of 4: element loads; NaN beside the window (a zero there would hide a load that strays)
+    wide = torch.full((x.size(0), K + 3), float('nan'), device=DEV)
     wide[:, :K] = x.to(DEV)
     outs = {}
     for take_abs in (True, False):

@@ -135,23 +135,24 @@ def test_strided_operands_inside_wider_buffers(w, H, x0, o0, e0, n, mode):
     x, stages = _operands(w, H, n, 77 + w)
     idx, _, _, _, adj = _plan(n)
     e, how = _edge(n, w, mode)
-    buf = torch.full((n, width), -9.0, device=DEV)
+    buf = torch.full((n, width), float('nan'), device=DEV)      # (NaN around the x and e slices: a load that strays shows in out)
     buf[:, x0:x0 + w] = x.to(DEV)
-    ebuf = torch.full((e.size(0), e0 + w + 3), 7.0, device=DEV)
+    ebuf = torch.full((e.size(0), e0 + w + 3), float('nan'), device=DEV)
     ebuf[:, e0:e0 + w] = e.to(DEV)
     before, ebefore = buf.clone(), ebuf.clone()
     sd = _dev(stages)
     out = _raw(buf[:, x0:x0 + w], adj, ebuf[:, e0:e0 + w], mode, None, sd, 'relu', 'id', out=buf[:, o0:o0 + H])
+    assert not torch.isnan(out).any(), 'a NaN beside the x or e slice reached the output'
     gate(out, _gine.gine_formula64(x, idx, e, how, 0.0, stages, 'relu'), f'strided {w}x{H} {mode}')
     keep = torch.ones(width, dtype=torch.bool, device=DEV)
     keep[o0:o0 + H] = False
     assert torch.equal(buf[:, keep].view(torch.int32), before[:, keep].view(torch.int32)), 'an element outside the slice was written'
-    assert torch.equal(ebuf, ebefore)
+    assert torch.equal(ebuf.view(torch.int32), ebefore.view(torch.int32))
     # the op does the same through its `out` argument
     buf2 = before.clone()
     with torch.no_grad():
         got = ops.gine_layer(buf2[:, x0:x0 + w], adj, ebuf[:, e0:e0 + w], None, sd, 'relu', out=buf2[:, o0:o0 + H], edge_mode=mode)
-    assert got.data_ptr() == buf2.data_ptr() + 4 * o0 and torch.equal(buf2, buf)
+    assert got.data_ptr() == buf2.data_ptr() + 4 * o0 and torch.equal(buf2.view(torch.int32), buf.view(torch.int32))
 
 
 @pytest.mark.parametrize('w,H', [(5, 64), (128, 128)])

@@ -45,7 +45,9 @@ ROWS = (1, 31, 32, 33, 130)
 def _case(g, M, K, K2, N, bias, pro, x_slice=False):
     """Operands on the device, the float64 reference of Y and of both band arrays."""
     if x_slice:                     # X a column slice of a wider matrix: row stride K + 2, start 4 bytes into a row
-        X = _rand(g, M, K + 2).to(DEV)[:, 1:K + 1]
+        Xw = _rand(g, M, K + 2)
+        Xw[:, 0] = Xw[:, K + 1] = float('nan')      # (NaN beside the window: a load that strays and is not discarded shows in Y)
+        X = Xw.to(DEV)[:, 1:K + 1]
     else:
         X = _rand(g, M, K).to(DEV)
     X2 = _rand(g, M, K2).to(DEV) if K2 else None
@@ -117,7 +119,8 @@ def test_launch_equals_gemm_f32_bit_for_bit_and_float64_inside_the_gate(K, K2, N
 @pytest.mark.parametrize('K,N,M', [(13, 24, 33), (48, 48, 130)])
 def test_x_as_a_column_slice_with_an_odd_row_stride(K, N, M):
     """X[:, 1 : K + 1] of an [M, K + 2] matrix: a row stride that is no multiple of 4 and a start that is not 16-byte aligned
-    -- the element-by-element path at a width the 16-byte path would otherwise take."""
+    -- the element-by-element path at a width the 16-byte path would otherwise take.  The two columns beside the window hold
+    NaN: nothing of them reaches Y or a band sum."""
     g = torch.Generator().manual_seed(K * N)
     kw, y, s1, s2 = _case(g, M, K, 0, N, True, 3, x_slice=True)
     assert kw['X'].stride(0) % 4 != 0 and kw['X'].data_ptr() % 16 != 0

@@ -33,6 +33,17 @@ def _view(t: torch.Tensor, pad: int, off: int) -> torch.Tensor:
     return v
 
 
+def _padding_untouched(v: torch.Tensor, what: str) -> None:
+    """Every element of the buffer behind a `_view` that lies outside the view still holds its NaN: the floats in front of it,
+    the `pad` floats behind every row."""
+    buf = v._base
+    keep = torch.ones(buf.numel(), dtype=torch.bool, device=buf.device)
+    rows, cols = v.shape
+    idx = v.storage_offset() + torch.arange(rows, device=buf.device)[:, None] * v.stride(0) + torch.arange(cols, device=buf.device)
+    keep[idx.reshape(-1)] = False
+    assert bool(torch.isnan(buf.reshape(-1)[keep]).all()), f'{what}: an element beside the output window was written'
+
+
 def _launch(X, X2, W, bias, Y, w_trans=False, m_dev=None):
     d = ops._wide_desc(X, X2, W, bias, Y, w_trans)
     if m_dev is not None:
@@ -63,7 +74,8 @@ def test_parity_against_float64_in_both_weight_layouts(K, K2, N, w_trans):
             o, Y, ref = _operands(g, M, K, K2, N, bias=bias, pad=pad, off=off, w_trans=w_trans)
             _launch(o['X'], o['X2'], o['W'], o['bias'], Y, w_trans)
             gate(Y, ref, f'linear_wide {"W" if w_trans else "W^T"} M={M} K={K}+{K2} N={N} bias={bias} pad={pad} off={off}')
-            if K2:          # ... and without X2: the first K columns alone
+            _padding_untouched(Y, f'linear_wide M={M} K={K}+{K2} N={N} pad={pad} off={off}')
+            if K2:       # ... and without X2: the first K columns alone
                 W1 = o['W'][:K] if w_trans else o['W'][:, :K]
                 Y1 = torch.full((M, N), NAN, device=DEV)
                 _launch(o['X'], None, W1, o['bias'], Y1, w_trans)
