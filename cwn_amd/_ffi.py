@@ -10,6 +10,8 @@ from typing import Optional, Sequence
 
 import torch
 
+from ._window import ld
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('CWN_HIP_LIB') or os.path.join(_HERE, 'libcwn_hip.so')   # override: A/B experiments
 
@@ -978,7 +980,7 @@ def flow_head(x: torch.Tensor, ptr_dev: torch.Tensor, w1, b1, w2, b2, take_abs: 
     pooled = torch.empty(Cn, K, dtype=torch.float32, device=dev) if keep else None
     h = torch.empty(Cn, H, dtype=torch.float32, device=dev) if keep else None
     ws = _flow_workspace(N, Cn, K, dev)
-    check(lib().cwn_flow_head_f32(x.data_ptr() if N else None, N, x.stride(0) if N > 1 else K, ptr_dev.data_ptr(), Cn, w1.data_ptr(),
+    check(lib().cwn_flow_head_f32(x.data_ptr() if N else None, N, ld(x), ptr_dev.data_ptr(), Cn, w1.data_ptr(),
                                   ptr(b1), w2.data_ptr(), ptr(b2), out.data_ptr(), O, ptr(pooled), ptr(h), K, H, O, int(take_abs),
                                   int(mean), ws.data_ptr(), ws.numel(), stream_ptr(dev)), 'cwn_flow_head_f32')
     return out, pooled, h
@@ -993,10 +995,9 @@ def flow_head_bwd(g: torch.Tensor, h: torch.Tensor, x: torch.Tensor, ptr_dev: to
     dx = torch.empty(N, K, dtype=torch.float32, device=dev) if need_dx else None
     dh = torch.empty(Cn, H, dtype=torch.float32, device=dev)
     ws = _flow_workspace(N, Cn, K, dev)
-    check(lib().cwn_flow_head_bwd_f32(g.data_ptr(), g.stride(0) if Cn > 1 else O, h.data_ptr(), x.data_ptr() if N else None, N,
-                                      x.stride(0) if N > 1 else K, ptr_dev.data_ptr(), Cn, w1.data_ptr(), w2.data_ptr(), ptr(dx), K,
-                                      dh.data_ptr(), K, H, O, int(take_abs), int(mean), ws.data_ptr(), ws.numel(), stream_ptr(dev)),
-          'cwn_flow_head_bwd_f32')
+    check(lib().cwn_flow_head_bwd_f32(g.data_ptr(), ld(g, O), h.data_ptr(), x.data_ptr() if N else None, N, ld(x), ptr_dev.data_ptr(),
+                                      Cn, w1.data_ptr(), w2.data_ptr(), ptr(dx), K, dh.data_ptr(), K, H, O, int(take_abs), int(mean),
+                                      ws.data_ptr(), ws.numel(), stream_ptr(dev)), 'cwn_flow_head_bwd_f32')
     return dx, dh
 
 
@@ -1011,7 +1012,7 @@ def flow_head_counted(x: torch.Tensor, ptr_dev: torch.Tensor, n_dev: Optional[to
     pooled = torch.empty(Cn, K, dtype=torch.float32, device=dev) if keep else None
     h = torch.empty(Cn, H, dtype=torch.float32, device=dev) if keep else None
     ws = _flow_workspace(N, Cn, K, dev)
-    check(lib().cwn_flow_head_dev_f32(x.data_ptr() if N else None, N, x.stride(0) if N > 1 else K, ptr_dev.data_ptr(), Cn, w1.data_ptr(),
+    check(lib().cwn_flow_head_dev_f32(x.data_ptr() if N else None, N, ld(x), ptr_dev.data_ptr(), Cn, w1.data_ptr(),
                                       ptr(b1), w2.data_ptr(), ptr(b2), out.data_ptr(), O, ptr(pooled), ptr(h), K, H, O, int(take_abs),
                                       int(mean), ptr(n_dev), c_dev.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr(dev)),
           'cwn_flow_head_dev_f32')
@@ -1027,11 +1028,10 @@ def flow_head_counted_bwd(g: torch.Tensor, h: torch.Tensor, x: torch.Tensor, ptr
     dev = x.device
     dh = torch.empty(Cn, H, dtype=torch.float32, device=dev)
     ws = _flow_workspace(N, Cn, K, dev)
-    check(lib().cwn_flow_head_bwd_dev_f32(g.data_ptr(), g.stride(0) if Cn > 1 else O, h.data_ptr(), x.data_ptr() if N else None, N,
-                                          x.stride(0) if N > 1 else K, ptr_dev.data_ptr(), Cn, w1.data_ptr(), w2.data_ptr(), ptr(dx),
-                                          dx.stride(0) if dx is not None and N > 1 else K, dh.data_ptr(), K, H, O, int(take_abs),
-                                          int(mean), ptr(n_dev), c_dev.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr(dev)),
-          'cwn_flow_head_bwd_dev_f32')
+    check(lib().cwn_flow_head_bwd_dev_f32(g.data_ptr(), ld(g, O), h.data_ptr(), x.data_ptr() if N else None, N, ld(x),
+                                          ptr_dev.data_ptr(), Cn, w1.data_ptr(), w2.data_ptr(), ptr(dx), K if dx is None else ld(dx, K),
+                                          dh.data_ptr(), K, H, O, int(take_abs), int(mean), ptr(n_dev), c_dev.data_ptr(), ws.data_ptr(),
+                                          ws.numel(), stream_ptr(dev)), 'cwn_flow_head_bwd_dev_f32')
     return dh
 
 

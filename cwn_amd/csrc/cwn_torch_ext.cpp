@@ -48,14 +48,14 @@ inline void check_feature(const at::Tensor& x, int64_t rows, int64_t F, int dev,
         throw py::type_error(std::string(who) + ": features must be float32 tensors on the GPU this launch was prepared for");
 }
 
-inline at::Tensor row_major(const at::Tensor& t) {      // ops._rowmajor
+inline at::Tensor row_major(const at::Tensor& t) {      // cwn_amd/_window.py: rowmajor (behind ops._rowmajor)
     if ((t.size(1) > 1 && t.stride(1) != 1) || (t.size(0) > 1 && t.stride(0) < t.size(1))) return t.contiguous();
     return t;
 }
 
-inline at::Tensor row_major16(const at::Tensor& t) {    // ops._rowmajor16: an operand read 16 bytes at a time, no element-wise twin
+// cwn_amd/_window.py: rowmajor16(t, ld(t)), behind ops._rowmajor16 (F-wide operands: ONE row is judged by its address alone)
+inline at::Tensor row_major16(const at::Tensor& t) {
     at::Tensor r = row_major(t);
-    // (clone, not contiguous(): ONE row off 16 bytes is "contiguous" as it lies)
     if ((reinterpret_cast<uintptr_t>(r.data_ptr()) & 15u) != 0 || (r.size(0) > 1 && r.stride(0) % 4 != 0))
         return r.clone(at::MemoryFormat::Contiguous);
     return r;

@@ -45,6 +45,7 @@ from torch import Tensor
 from torch.nn import BatchNorm1d, Identity, Linear
 
 from . import _ffi, ops
+from ._window import aligned16, is_vec16, ld
 
 # True: BatchNorm backward as ONE launch per stage (cwn_norm_bwd_f32: column-owning workgroups, sums bit-reproducible and added
 # straight into gamma.grad / beta.grad).  OFF: measured on the ZINC-128 step the launch takes 28 us against 6.3 + 5.9 us
@@ -111,7 +112,6 @@ def _norm_desc(z: Tensor, *, dy: Optional[Tensor] = None, out: Optional[Tensor] 
                s12=None, relu: bool = True) -> _ffi.NormDesc:
     """aff = (scale, shift, mean, rstd) rows of one [4, N] tensor, or None for an identity norm."""
     M, N = z.shape
-    ld = lambda t: t.stride(0) if t.size(0) > 1 else t.size(1)
     return _ffi.NormDesc(
         dy=_ffi.ptr(dy), z=z.data_ptr(),
         scale=None if aff is None else aff[0].data_ptr(), shift=None if aff is None else aff[1].data_ptr(),
@@ -178,12 +178,12 @@ class _DenseTrain(torch.autograd.Function):
         widths = [st.lin.out_features for st in bns]
         F0 = int(A0[0][0].size(1))
         live = bool(LIVE_BN and ops.STAGE_KERNEL and bns and len(bns) == len(stages) and F0 in (64, 128) and nb * nd <= _ffi.MAX_DESCS
-                    and all(a.size(1) == F0 and a.stride(0) % 4 == 0 and a.data_ptr() % 16 == 0 for pair in A0 for a in pair)
+                    and all(a.size(1) == F0 and is_vec16(a) for pair in A0 for a in pair)
                     and all(tuple(P[id(st)][0].shape) == (F0, F0) and ops.packed_stage_block(P[id(st)][0], 0) is not None
                             for i in range(nd) for chain in plan.chains[i] for st in chain)
                     and all(tuple(P[id(st)][0].shape) == (F0, nb * F0)
                             and all(ops.packed_stage_block(P[id(st)][0], c * F0) is not None for c in range(nb)) for st in (plan.cb or []))
-                    and all(t is None or (t.numel() == F0 and t.data_ptr() % 16 == 0 and t.is_contiguous())
+                    and all(t is None or (t.numel() == F0 and aligned16(t) and t.is_contiguous())
                             for st in stages for t in P[id(st)][1:]))
         if plan.cb is not None and nb > 2 and not live:
             raise CombineNeedsStageKernel('a combine stage over more than two branches runs on cwn_dense_stage_ex_f32 with live '
@@ -331,8 +331,7 @@ class _DenseTrain(torch.autograd.Function):
             for i, (z, h) in enumerate(zip(Z3, H)):
                 st = plan.cb[i]
                 Fw = int(z.size(1)) if z.dim() == 2 else 0
-                if (not st.is_bn or Fw not in (64, 128) or not z.numel() or z.stride(1) != 1 or z.stride(0) % 4
-                        or z.data_ptr() % 16):
+                if (not st.is_bn or Fw not in (64, 128) or not z.numel() or z.stride(1) != 1 or not is_vec16(z)):
                     ext.append(None)
                     continue
                 slots = ops.zeros_scratch(4 * _ffi.BN_SLOTS * 2 * Fw, dev).view(torch.float32)[:_ffi.BN_SLOTS * 2 * Fw]
@@ -380,7 +379,7 @@ class _DenseTrain(torch.autograd.Function):
         # With the one-launch BatchNorm backward (opt-in; every matrix within its row cap, 16-byte aligned) the sums go
         # straight INTO gamma.grad / beta.grad.
         fused_norm = FUSED_NORM_BACKWARD and all(
-            z.size(0) <= _ffi.NORM_BWD_FUSED_MAX_ROWS and z.size(1) % 4 == 0 and z.stride(0) % 4 == 0 and z.data_ptr() % 16 == 0
+            z.size(0) <= _ffi.NORM_BWD_FUSED_MAX_ROWS and z.size(1) % 4 == 0 and is_vec16(z)
             for z in [zz for i in range(nd) for br in range(nb) for zz in Z[i][br]] + Z3)
         sizes, targets, norm_targets = [], [], {}
         for st in stages:
@@ -390,7 +389,7 @@ class _DenseTrain(torch.autograd.Function):
             direct = None
             if st.is_bn:
                 tg, tbeta = ops._grad_target(st.norm.weight), ops._grad_target(st.norm.bias)
-                if tg is not None and tbeta is not None and (not fused_norm or (tg.data_ptr() % 16 == 0 and tbeta.data_ptr() % 16 == 0)):
+                if tg is not None and tbeta is not None and (not fused_norm or (aligned16(tg) and aligned16(tbeta))):
                     direct = (tbeta, tg)                      # (s1 = d beta, s2 = d gamma)
             norm_targets[id(st)] = direct
             sizes.append((0 if tw is not None else W.numel(), 0 if (b is None or tb is not None) else b.numel()))
@@ -421,17 +420,15 @@ class _DenseTrain(torch.autograd.Function):
 
         def out_record(st: Optional[Stage], z: Tensor):
             """The cwn_bn_bwd_live record with which a launch whose dx is `st`'s dy takes over the reduce of its backward."""
-            if not live_bwd or st is None or not st.is_bn or not z.numel() or z.stride(1) != 1 or z.stride(0) % 4 or z.data_ptr() % 16:
+            if not live_bwd or st is None or not st.is_bn or not z.numel() or z.stride(1) != 1 or not is_vec16(z):
                 return None
             return _ffi.BnBwdLive(z=z.data_ptr(), aff=aff_of[id(st)].data_ptr(), slots=bslot_of[id(st)].data_ptr(),
                                   ldz=z.stride(0))
 
         drop_of = {}          # id(combine stage) -> (cwn_dropout record, the multiplied gradient the reduce launch writes)
-        ld = lambda t: t.stride(0) if t.size(0) > 1 else t.size(1)
-
         def bnb_ok(dy, z):
             return (FUSED_NORM_APPLY and not fused_norm and z.size(1) in (64, 128) and z.numel() > 0
-                    and all(t.data_ptr() % 16 == 0 and t.stride(0) % 4 == 0 and t.stride(1) == 1 for t in (dy, z)))
+                    and all(is_vec16(t) and t.stride(1) == 1 for t in (dy, z)))
 
         def counted(z):
             return z.numel() > 0 and _ffi.dyn(z.size(0)) is not None
@@ -461,7 +458,7 @@ class _DenseTrain(torch.autograd.Function):
                 aff = aff_of.get(id(st))
                 s12 = G[id(st)][2]
                 tgt = norm_targets[id(st)]
-                if fused_norm and dy.stride(0) % 4 == 0 and dy.data_ptr() % 16 == 0 and (s12 is None or s12.data_ptr() % 16 == 0):
+                if fused_norm and is_vec16(dy) and (s12 is None or aligned16(s12)):
                     (direct if tgt is not None else scratch).append(
                         _norm_desc(z, dy=dy, out=dz, aff=aff, s12=tgt if tgt is not None else s12))
                     outs.append(dz)
@@ -511,8 +508,6 @@ class _DenseTrain(torch.autograd.Function):
                 return None, None
             a = aff_of[id(st)]
             return a[0], a[1]
-
-        ld = lambda t: t.stride(0) if t.size(0) > 1 else t.size(1)
 
         # weight gradients whose targets are all the parameters' own .grad buffers may wait for the end of the backward
         can_defer = ops.ACCUMULATE_INTO_GRAD and all(tw is not None and (st.lin.bias is None or tb is not None)
@@ -641,7 +636,7 @@ class _DenseTrain(torch.autograd.Function):
                     items.append((chain[s], dy[i][br], Z[i][br][s]))
             # (the lazy form hands dz to the input-gradient GEMM's prologue, which exists for 16-byte rows only: a first layer
             #  over 1-wide features -- REDDIT-BINARY's constant vertex feature, mp/models.py:112-260 -- takes the apply launch)
-            wide = all(P[id(chain[s])][0].size(1) % 4 == 0 and P[id(chain[s])][0].stride(0) % 4 == 0
+            wide = all(P[id(chain[s])][0].size(1) % 4 == 0 and P[id(chain[s])][0].stride(0) % 4 == 0      # (no address test: not is_vec16)
                        for i in range(nd) for chain in plan.chains[i])
             stage_s = nd * nb <= _ffi.MAX_DESCS and all(ops.stage_bwd_takes(P[id(st_)][0], int(z_.size(1))) for st_, _, z_ in items)
             pend = norm_backward(items, lazy=wide, stage_ok=stage_s)

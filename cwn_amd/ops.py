@@ -17,6 +17,7 @@ import torch
 from torch import Tensor
 
 from . import _ffi
+from ._window import aligned16, is_rowmajor, is_vec16, ld, rowmajor, rowmajor16
 from .csr import Adjacency, wait_ready
 
 MSG_A, MSG_A_PLUS_B, MSG_A_TIMES_B, MSG_RELU_A_PLUS_B, MSG_A_MASK_RELU, MSG_RELU_A_PLUS_B_SQ, MSG_A_TIMES_2RELU = range(7)
@@ -1041,7 +1042,7 @@ def _front_backward_fused(ctx, g0, g1, g2) -> Optional[List[Optional[Tensor]]]:
     dev = iv.device
     n0 = int(iv.size(0))
     gs = [None if g is None else _f32c(g, 'grad') for g in (g0, g1, g2)]
-    if any(g is not None and g.data_ptr() % 16 for g in gs):
+    if any(g is not None and not aligned16(g) for g in gs):
         return None
     t1 = adj1.t_src if (adj1 is not None and n1 > 0) else None      # per vertex its edges
     t2 = adj2.t_src if (adj2 is not None and n2 > 0 and gs[2] is not None) else None      # per edge its rings
@@ -1135,9 +1136,7 @@ def _head_parts(x):
         return None, 0
     blocks = list(x) if isinstance(x, (list, tuple)) else [x]
     blocks = [_f32c(b, 'x') for b in blocks]
-    # (cwn_head_f32 reads a row 16 bytes at a time: ONE row of a wider matrix is "contiguous" wherever it starts and whatever its
-    #  stride says)
-    blocks = [b.clone(memory_format=torch.contiguous_format) if b.data_ptr() % 16 or b.stride(0) % 4 else b for b in blocks]
+    blocks = [rowmajor16(b) for b in blocks]       # (cwn_head_f32 reads a row 16 bytes at a time; the RECORDED stride is judged)
     if len(blocks) > 1:
         w = int(blocks[0].size(1))
         if any(b.size(1) != w or b.size(0) != blocks[0].size(0) or b.stride(0) != blocks[0].stride(0) for b in blocks) \
@@ -1258,14 +1257,13 @@ class HeadLaunch:
             n_b, rows, w = shape
             if len(blocks) != n_b:
                 return None
-            ld = blocks[0].stride(0)
+            ldx = blocks[0].stride(0)
             for b in blocks:
                 if (b.dtype != torch.float32 or b.dim() != 2 or b.size(0) != rows or b.size(1) != w or b.device != self.dev
-                        or (w > 1 and b.stride(1) != 1) or b.stride(0) != ld or (rows > 1 and ld < w)
-                        or b.data_ptr() % 16 or ld % 4):       # (cwn_head_f32: 16-byte rows -- the long way copies)
+                        or b.stride(0) != ldx or not is_rowmajor(b) or not is_vec16(b)):   # (cwn_head_f32: 16-byte rows -- the long way copies)
                     return None
             D = self.arr[d]
-            D.x, D.ldx = blocks[0].data_ptr(), ld
+            D.x, D.ldx = blocks[0].data_ptr(), ldx
             for q in range(1, n_b):
                 D.x_more[q - 1] = blocks[q].data_ptr()
         out = torch.empty(self.C, self.O, dtype=torch.float32, device=self.dev)
@@ -1463,7 +1461,6 @@ def dropout_apply(x: Tensor, rec: '_ffi.Dropout', out: Optional[Tensor] = None) 
         out = torch.empty(x2.shape, dtype=torch.float32, device=x2.device)
     elif out.dim() == 2:
         _out_window(out, M, N, 'out')
-    ld = lambda t: int(t.stride(0)) if t.size(0) > 1 else int(t.size(1))
     if M and N:
         _ffi.check(_ffi.lib().cwn_dropout_f32(x2.data_ptr(), out.data_ptr(), M, N, ld(x2), ld(out), rec, _ffi.dyn(M),
                                               _ffi.stream_ptr(x2.device)), 'cwn_dropout_f32')
@@ -1514,21 +1511,13 @@ def _rowmajor(t: Tensor, name: str) -> Tensor:
     if t.dtype != torch.float32 or t.dim() != 2:
         raise TypeError(f'{name} must be a 2-D float32 tensor (got {t.dtype}, {t.dim()}-D): the GEMM kernels are fp32 MFMA '
                         'only; float64 products run on torch.nn.Linear')
-    if t.size(1) > 1 and t.stride(1) != 1:
-        t = t.contiguous()
-    if t.size(0) > 1 and t.stride(0) < t.size(1):
-        t = t.contiguous()
-    return t
+    return rowmajor(t)
 
 
 def _rowmajor16(t: Tensor, name: str) -> Tensor:
-    """`_rowmajor` for an operand a kernel reads 16 bytes at a time with no element-wise twin (the F-wide inputs of
-    cwn_update_mlp_f32 / cwn_update_mlp3_f32): a window that starts off 16 bytes or whose row stride is no multiple of 4 is
-    copied, where the entry point would refuse it (include/cwn_hip.h, "OPERAND WINDOWS")."""
+    """`_rowmajor` for the F-wide inputs of cwn_update_mlp_f32 / _mlp3_f32, read 16 bytes at a time: copied where the entry refuses it."""
     t = _rowmajor(t, name)
-    if t.data_ptr() % 16 or (t.size(0) > 1 and t.stride(0) % 4):
-        t = t.clone(memory_format=torch.contiguous_format)      # (not .contiguous(): ONE row off 16 bytes is "contiguous" as it lies)
-    return t
+    return rowmajor16(t, ld(t))
 
 
 def _out_window(out: Tensor, rows: int, cols: int, name: str) -> Tensor:
@@ -1537,7 +1526,7 @@ def _out_window(out: Tensor, rows: int, cols: int, name: str) -> Tensor:
     cannot be copied the way `_rowmajor` copies an input: it is refused."""
     if out.dim() != 2 or tuple(out.shape) != (rows, cols) or out.dtype != torch.float32:
         raise ValueError(f'{name} must be a float32 [{rows}, {cols}] matrix (got {out.dtype} {tuple(out.shape)})')
-    if (cols > 1 and out.stride(1) != 1) or (rows > 1 and out.stride(0) < cols):
+    if not is_rowmajor(out):
         raise ValueError(f'{name} must be row-major (unit column stride, row stride >= {cols}); got strides {tuple(out.stride())}: '
                          'a window of a wider matrix is fine, a transposed or column-strided view is not')
     return out
@@ -1611,9 +1600,7 @@ class Gemm:
             out_scale=_ffi.ptr(self.out_scale), out_shift=_ffi.ptr(self.out_shift),
             col_sum=None if cs is None else cs[0].data_ptr(),
             col_sumsq=None if cs is None else cs[1].data_ptr(),
-            Y=Y.data_ptr(), M=X.size(0), ldx=X.stride(0) if X.size(0) > 1 else max(K, 1),
-            ldx2=(X2.stride(0) if X2.size(0) > 1 else max(K2, 1)) if X2 is not None else 0,
-            ldw=W.stride(0) if W.size(0) > 1 else W.size(1), ldy=Y.stride(0) if Y.size(0) > 1 else Y.size(1),
+            Y=Y.data_ptr(), M=X.size(0), ldx=ld(X, max(K, 1)), ldx2=ld(X2, max(K2, 1)) if X2 is not None else 0, ldw=ld(W), ldy=ld(Y),
             N=W.size(1 if self.w_trans else 0), K=K, K2=K2, relu=int(self.relu), in_relu=int(self.in_relu),
             w_trans=int(self.w_trans), bnb=None if self.bnb is None else C.pointer(self.bnb),
             # (a static batch: the rows that exist -- the launch walks the row tiles below the device-side count only)
@@ -1728,7 +1715,7 @@ def _grad_target(p: Optional[Tensor]) -> Optional[Tensor]:
         return None
     g = p.grad
     if (g is None or g.dtype != torch.float32 or g.shape != p.shape or g.device != p.device
-            or (g.dim() == 2 and (g.stride(1) != 1 or g.stride(0) < g.size(1)))
+            or (g.dim() == 2 and (g.stride(1) != 1 or g.stride(0) < g.size(1)))       # (stricter than is_rowmajor: ONE row is judged too)
             or (g.dim() == 1 and g.stride(0) != 1)):
         return None
     return g
@@ -1742,7 +1729,6 @@ def _gemm_backward(gemms, tensors, outs, needs, gs, acc=None) -> List[Optional[T
     epilogue (CWN_GEMM_ADD_OUT) instead of written to a new matrix, and its slot gets None -- the caller hands the buffer on."""
     n = len(gemms)
     grads: List[Optional[Tensor]] = [None] * (4 * n)
-    ld = lambda t: t.stride(0) if t.size(0) > 1 else t.size(1)
     live = []
     nn_specs, nn_slot, tn_jobs, total = [], [], [], 0
     for k, gm in enumerate(gemms):
@@ -1866,7 +1852,7 @@ def linear_wide_applies(K: int, K2: int, N: int) -> bool:
 
 def _wide_desc(X: Tensor, X2: Optional[Tensor], W: Tensor, bias: Optional[Tensor], Y: Tensor, w_trans: bool) -> '_ffi.LinearWideDesc':
     return _ffi.LinearWideDesc(X=X.data_ptr(), X2=_ffi.ptr(X2), W=W.data_ptr(), bias=_ffi.ptr(bias), Y=Y.data_ptr(),
-                               M=X.size(0), ldx=_ld(X), ldx2=0 if X2 is None else _ld(X2), ldw=_ld(W), ldy=_ld(Y),
+                               M=X.size(0), ldx=ld(X), ldx2=0 if X2 is None else ld(X2), ldw=ld(W), ldy=ld(Y),
                                N=Y.size(1), K=X.size(1), K2=0 if X2 is None else X2.size(1), w_trans=int(w_trans))
 
 
@@ -1943,16 +1929,16 @@ class _LinearWide(torch.autograd.Function):
             if want_b and tb is None:
                 db = tgt_b
             if g.size(0):
-                tn = dict(dZ=g.data_ptr(), in_scale=None, in_shift=None, in_scale2=None, in_shift2=None, M=g.size(0), lddz=_ld(g),
+                tn = dict(dZ=g.data_ptr(), in_scale=None, in_shift=None, in_scale2=None, in_shift2=None, M=g.size(0), lddz=ld(g),
                           lddw=tgt_w.stride(0), N=N, in_relu=0)
                 if X2 is None or K % 4 == 0:
-                    tns = [_ffi.GemmTnDesc(X=X.data_ptr(), X2=_ffi.ptr(X2), dW=tgt_w.data_ptr(), db=_ffi.ptr(tgt_b), ldx=_ld(X),
-                                           ldx2=0 if X2 is None else _ld(X2), K=K, K2=K2, **tn)]
+                    tns = [_ffi.GemmTnDesc(X=X.data_ptr(), X2=_ffi.ptr(X2), dW=tgt_w.data_ptr(), db=_ffi.ptr(tgt_b), ldx=ld(X),
+                                           ldx2=0 if X2 is None else ld(X2), K=K, K2=K2, **tn)]
                 else:
                     # (cwn_gemm_tn_f32 wants K % 4 == 0 next to X2: two descriptors into the column halves of dW)
-                    tns = [_ffi.GemmTnDesc(X=X.data_ptr(), X2=None, dW=tgt_w.data_ptr(), db=_ffi.ptr(tgt_b), ldx=_ld(X), ldx2=0,
+                    tns = [_ffi.GemmTnDesc(X=X.data_ptr(), X2=None, dW=tgt_w.data_ptr(), db=_ffi.ptr(tgt_b), ldx=ld(X), ldx2=0,
                                            K=K, K2=0, **tn),
-                           _ffi.GemmTnDesc(X=X2.data_ptr(), X2=None, dW=tgt_w.data_ptr() + 4 * K, db=None, ldx=_ld(X2), ldx2=0,
+                           _ffi.GemmTnDesc(X=X2.data_ptr(), X2=None, dW=tgt_w.data_ptr() + 4 * K, db=None, ldx=ld(X2), ldx2=0,
                                            K=K2, K2=0, **tn)]
                 # in-place targets only (nothing handed back to autograd): the launch may wait for the end of the backward
                 _ffi.gemm_tn(tns, dev, keep=[g, X, X2, tgt_w, tgt_b], deferrable=ACCUMULATE_INTO_GRAD and in_place)
@@ -1983,7 +1969,7 @@ def _ln_descs(zs, gammas, betas, outs, epss, relu: bool, stats=None) -> List['_f
         M, N = z.shape
         if M:
             d = _ffi.LnDesc(z=z.data_ptr(), gamma=_ffi.ptr(gammas[k]), beta=_ffi.ptr(betas[k]), out=out.data_ptr(),
-                            M=M, ldz=_ld(z), ldout=_ld(out), N=N, relu=int(relu), eps=float(epss[k]))
+                            M=M, ldz=ld(z), ldout=ld(out), N=N, relu=int(relu), eps=float(epss[k]))
             if stats is not None:
                 d.mean, d.rstd = stats[0, off:].data_ptr(), stats[1, off:].data_ptr()
             descs.append(d)
@@ -2055,7 +2041,7 @@ class _LayerNormActMany(torch.autograd.Function):
                 descs.append(_ffi.LnDesc(
                     z=z.data_ptr(), gamma=_ffi.ptr(gamma), out=out.data_ptr(), mean=stats[0, row0:].data_ptr(),
                     rstd=stats[1, row0:].data_ptr(), dy=dy.data_ptr(), dz=dz.data_ptr(), dgamma=_ffi.ptr(dgamma),
-                    dbeta=_ffi.ptr(dbeta), M=M, ldz=_ld(z), ldout=_ld(out), lddy=_ld(dy), lddz=_ld(dz), N=N,
+                    dbeta=_ffi.ptr(dbeta), M=M, ldz=ld(z), ldout=ld(out), lddy=ld(dy), lddz=ld(dz), N=N,
                     relu=int(relu), eps=float(ctx.epss[k]), accumulate=int(bool(acc))))
         if descs:
             _ffi.layer_norm_bwd(descs, dev)
@@ -2282,8 +2268,7 @@ def target_head_applies(x: Tensor, target_rows: Tensor, weight: Tensor, bias: Op
         return False
     if x.dim() != 2 or weight.dim() != 2 or x.size(1) != weight.size(1) or (bias is not None and tuple(bias.shape) != (weight.size(0),)):
         return False
-    return (_ffi.target_head_served(int(weight.size(1)), int(weight.size(0))) and x.stride(1) == 1 and x.stride(0) % 4 == 0
-            and x.data_ptr() % 16 == 0)
+    return (_ffi.target_head_served(int(weight.size(1)), int(weight.size(0))) and x.stride(1) == 1 and is_vec16(x))
 
 
 def target_head(x: Tensor, target_rows: Tensor, weight: Tensor, bias: Optional[Tensor] = None) -> Tensor:
@@ -2534,8 +2519,7 @@ def _act_code(act) -> int:
 
 def _rows_contiguous(t: Tensor, dim: int) -> bool:
     """`dim`-D with unit stride along the last axis; a 2-D tensor may be a row-strided view whose rows do not overlap."""
-    return (t.dim() == dim and (t.numel() == 0 or t.stride(-1) == 1)
-            and (dim != 2 or t.size(0) <= 1 or t.stride(0) >= t.size(1)))
+    return t.dim() == dim and (t.numel() == 0 or (t.stride(-1) == 1 and (dim != 2 or is_rowmajor(t))))
 
 
 def _operand_dtype(t, name: str, dtypes, what: str, hint: str) -> None:
@@ -2568,10 +2552,6 @@ _F64_ROWS = dict(dtypes=(torch.float64,), rows_got=True,
                  hint='this kernel computes in fp64 only (float32 runs through the MFMA launches: gemm_many, update_mlp)')
 
 
-def _ld(t: Tensor) -> int:
-    return int(t.stride(0)) if t.size(0) > 1 else int(t.size(1))
-
-
 def linear_many_f64(items) -> List[Tensor]:
     """[act(x @ weight.T + bias) for (x, weight, bias, act) in items] in float64 from ONE launch (16 products at most per
     launch; a longer list takes more).  x [M, K] and weight [N, K] may be row-strided views -- the two column slices
@@ -2599,8 +2579,8 @@ def _linear_many_f64(items) -> List[Tensor]:
         dev = x.device
         y = torch.empty(M, N, dtype=torch.float64, device=dev)
         outs.append(y)
-        descs.append(_ffi.LinearDescF64(X=x.data_ptr(), W=w.data_ptr(), bias=_ffi.ptr(b), Y=y.data_ptr(), M=M, ldx=_ld(x),
-                                        ldw=_ld(w), ldy=N, K=K, N=N, act=_act_code(act)))
+        descs.append(_ffi.LinearDescF64(X=x.data_ptr(), W=w.data_ptr(), bias=_ffi.ptr(b), Y=y.data_ptr(), M=M, ldx=ld(x),
+                                        ldw=ld(w), ldy=N, K=K, N=N, act=_act_code(act)))
     for lo in range(0, len(descs), _ffi.LINEAR_F64_MAX_DESCS):
         part = descs[lo:lo + _ffi.LINEAR_F64_MAX_DESCS]
         _ffi.check(_ffi.lib().cwn_linear_many_f64((_ffi.LinearDescF64 * len(part))(*part), len(part), _ffi.stream_ptr(dev)),
@@ -2684,9 +2664,8 @@ def update_chain_f64(dims: Sequence[ChainDim]) -> List[Tensor]:
         dev = d.in_up.device
         out = torch.empty(n, H, dtype=torch.float64, device=dev) if d.out is None else d.out[:n]
         outs.append(out)
-        D = _ffi.ChainDescF64(in_up=d.in_up.data_ptr(), in_b=d.in_b.data_ptr(), out=out.data_ptr(), n=n, ld_up=_ld(d.in_up),
-                              ld_b=_ld(d.in_b), ld_out=int(d.out.stride(0)) if d.out is not None and d.out.size(0) > 1 else H,
-                              F=F, H=H, act=_act_code(d.act))
+        D = _ffi.ChainDescF64(in_up=d.in_up.data_ptr(), in_b=d.in_b.data_ptr(), out=out.data_ptr(), n=n, ld_up=ld(d.in_up),
+                              ld_b=ld(d.in_b), ld_out=H if d.out is None else ld(d.out, H), F=F, H=H, act=_act_code(d.act))
         for s in range(5):
             D.W[s], D.bias[s] = d.weights[s].data_ptr(), _ffi.ptr(d.biases[s])
             D.scale[s], D.shift[s] = _ffi.ptr(d.folds[s][0]), _ffi.ptr(d.folds[s][1])
@@ -2752,9 +2731,8 @@ def update_chain_f32(dims: Sequence[ChainDim]) -> List[Tensor]:
         dev = d.in_up.device
         out = torch.empty(n, H, dtype=torch.float32, device=dev) if d.out is None else d.out[:n]
         outs.append(out)
-        D = _ffi.ChainDescF32(in_up=d.in_up.data_ptr(), in_b=d.in_b.data_ptr(), out=out.data_ptr(), n=n, ld_up=_ld(d.in_up),
-                              ld_b=_ld(d.in_b), ld_out=int(d.out.stride(0)) if d.out is not None and d.out.size(0) > 1 else H,
-                              F=F, H=H, act=_act_code(d.act))
+        D = _ffi.ChainDescF32(in_up=d.in_up.data_ptr(), in_b=d.in_b.data_ptr(), out=out.data_ptr(), n=n, ld_up=ld(d.in_up),
+                              ld_b=ld(d.in_b), ld_out=H if d.out is None else ld(d.out, H), F=F, H=H, act=_act_code(d.act))
         for s in range(5):
             D.W[s], D.bias[s] = d.weights[s].data_ptr(), _ffi.ptr(d.biases[s])
             D.scale[s], D.shift[s] = _ffi.ptr(d.folds[s][0]), _ffi.ptr(d.folds[s][1])
@@ -2801,8 +2779,7 @@ class ChainLaunch:
         outs = []
         for D, (u, b), (F, H) in zip(self.arr, ins, self.widths):
             for x in (u, b):
-                if (x.dim() != 2 or x.size(1) != F or x.dtype != torch.float32 or x.device != self.dev or (F > 1 and x.stride(1) != 1)
-                        or (x.size(0) > 1 and x.stride(0) < F)):
+                if (x.dim() != 2 or x.size(1) != F or x.dtype != torch.float32 or x.device != self.dev or not is_rowmajor(x)):
                     return None
             n = u.size(0)
             if b.size(0) != n:
@@ -2810,7 +2787,7 @@ class ChainLaunch:
             out = torch.empty(n, H, dtype=torch.float32, device=self.dev)
             outs.append(out)
             D.in_up, D.in_b, D.out, D.n = u.data_ptr(), b.data_ptr(), out.data_ptr(), n
-            D.ld_up, D.ld_b = (u.stride(0), b.stride(0)) if n > 1 else (F, F)
+            D.ld_up, D.ld_b = ld(u), ld(b)
             D.m_dev = _ffi.dyn(n)
         rc = self.fn(self.arr, self.n, _ffi.stream_ptr(self.dev))
         if rc != 0:
@@ -2867,7 +2844,7 @@ def embed_pool(xs, cell_ptrs, n_complexes: int, weights, biases, act, mean: bool
         out = torch.empty(C_, H, dtype=dtype, device=dev)
         outs.append(out)
         descs.append(_ffi.EmbedPoolDesc(x=x.data_ptr() if N else None, cell_ptr=ptr.data_ptr(), W=w.data_ptr(), bias=_ffi.ptr(b),
-                                        out=out.data_ptr(), N=N, C=C_, ldx=_ld(x), ldw=_ld(w), ldo=H, K=K, H=H, act=code,
+                                        out=out.data_ptr(), N=N, C=C_, ldx=ld(x), ldw=ld(w), ldo=H, K=K, H=H, act=code,
                                         mean=int(bool(mean))))
     fn, name = _ffi.typed_entry('embed_pool', dtype)
     for lo in range(0, len(descs), _ffi.MAX_DESCS):
@@ -2905,10 +2882,10 @@ def agnostic_head(pooled, lin1_w: Tensor, lin1_b: Optional[Tensor], lin2_w: Tens
     dev = lin1_w.device
     out = torch.empty(C_, O, dtype=dtype, device=dev)
     D = _ffi.AgnosticHeadDesc(W1=lin1_w.data_ptr(), b1=_ffi.ptr(lin1_b), W2=lin2_w.data_ptr(), b2=_ffi.ptr(lin2_b),
-                              out=out.data_ptr(), C=C_, ldw1=_ld(lin1_w), ldw2=_ld(lin2_w), ldo=O, D=len(pooled), H=H, O=O,
+                              out=out.data_ptr(), C=C_, ldw1=ld(lin1_w), ldw2=ld(lin2_w), ldo=O, D=len(pooled), H=H, O=O,
                               act=_act_code(act))
     for d, p in enumerate(pooled):
-        D.P[d], D.ldp[d] = (p.data_ptr() if p is not None and C_ else None), (_ld(p) if p is not None else H)
+        D.P[d], D.ldp[d] = (p.data_ptr() if p is not None and C_ else None), (ld(p) if p is not None else H)
     fn, name = _ffi.typed_entry('agnostic_head', dtype)
     _ffi.check(fn(C.byref(D), _ffi.stream_ptr(dev)), name)
     return out
@@ -3005,7 +2982,7 @@ def _gin_descriptor(op: str, entry: str, rows: dict, layer: str, x, eps, stages,
             raise ValueError(f'{op}: out is {tuple(out.shape)} on {out.device}, the result {(n, H)} on {x.device}')
     if n == 0:
         return x, out, None
-    d = _ffi.GinDesc(x=x.data_ptr(), eps_dev=_ffi.ptr(eps), out=out.data_ptr(), n=n, ldx=_ld(x), ldout=_ld(out), w=w, H=H,
+    d = _ffi.GinDesc(x=x.data_ptr(), eps_dev=_ffi.ptr(eps), out=out.data_ptr(), n=n, ldx=ld(x), ldout=ld(out), w=w, H=H,
                      act=_act_code(act), act_post=_act_code(act_post))
     (d.W1, d.b1, d.scale1, d.shift1), (d.W2, d.b2, d.scale2, d.shift2) = [[_ffi.ptr(t) for t in s] for s in named]
     d._keep = (eps, named)             # (what the descriptor points at, alive until the launch is issued)
@@ -3081,7 +3058,7 @@ def gine_layer(x: Tensor, adj: Optional[Adjacency], edge: Optional[Tensor], eps,
         return out
     D = _ffi.GineDesc(g=d)
     if _gin_plan(D.g, 'gine_layer', adj, int(x.size(0))):
-        D.e, D.lde, D.n_e = edge.data_ptr(), _ld(edge), int(edge.size(0))
+        D.e, D.lde, D.n_e = edge.data_ptr(), ld(edge), int(edge.size(0))
         D.eidx = (adj.aux if edge_mode == 'aux' else adj.perm).data_ptr()
     _ffi.gine_layer(D, x.device)
     return out
@@ -3204,7 +3181,7 @@ def _blocked_backward_impl(ctx, gs, ys, g_tensors, g_needs, s_tensors, s_needs):
             e3 = dims[d].eps3
             e3 = None if e3 is None else _f32c(e3.detach(), 'eps3')
             g_down = _f32c(g_down, 'gradient of out_down')
-            if not dxs[d].is_contiguous() or dxs[d].numel() % 4 or dxs[d].data_ptr() % 16 or g_down.data_ptr() % 16:
+            if not dxs[d].is_contiguous() or dxs[d].numel() % 4 or not aligned16(dxs[d]) or not aligned16(g_down):
                 dxs[d].add_(g_down) if e3 is None else dxs[d].addcmul_(g_down, (1.0 + e3).view(1, 1))
                 continue
             keep += [g_down, e3, dxs[d]]
@@ -3432,15 +3409,15 @@ def pack_layer_weights_many(weights: Sequence[Tensor], transposed: bool = False)
         nbytes = int(L.cwn_layer_packed_weight_bytes(F))
         outs = [torch.empty(nbytes, dtype=torch.uint8, device=w.device) for _, w in ws]
         Wp = (C.c_void_p * n)(*[w.data_ptr() for _, w in ws])
-        ld = (C.c_int64 * n)(*[w.stride(0) for _, w in ws])
+        lds = (C.c_int64 * n)(*[w.stride(0) for _, w in ws])
         Op = (C.c_void_p * n)(*[o.data_ptr() for o in outs])
         outs_t = [torch.empty(nbytes, dtype=torch.uint8, device=w.device) for _, w in ws] if transposed else None
         if transposed:
             Ot = (C.c_void_p * n)(*[o.data_ptr() for o in outs_t])
-            _ffi.check(L.cwn_layer_pack_weights_both_many_f32(Wp, ld, F, Op, Ot, n, _ffi.stream_ptr(ws[0][1].device)),
+            _ffi.check(L.cwn_layer_pack_weights_both_many_f32(Wp, lds, F, Op, Ot, n, _ffi.stream_ptr(ws[0][1].device)),
                        'cwn_layer_pack_weights_both_many_f32')
         else:
-            _ffi.check(L.cwn_layer_pack_weights_many_f32(Wp, ld, F, Op, n, _ffi.stream_ptr(ws[0][1].device)),
+            _ffi.check(L.cwn_layer_pack_weights_many_f32(Wp, lds, F, Op, n, _ffi.stream_ptr(ws[0][1].device)),
                        'cwn_layer_pack_weights_many_f32')
         for (weight, w), out in zip(ws, outs):
             key = id(weight)
@@ -3565,14 +3542,11 @@ def update_mlp(dims: Sequence[MlpDim]) -> List[Tensor]:
     for i, D in enumerate(dims):
         rm = _rowmajor if int(D.x_up.size(1)) < F else _rowmajor16     # (narrow inputs are staged element-wise: any window)
         xu, xb = rm(D.x_up, 'x_up'), rm(D.x_b, 'x_b')
-        w_in = int(xu.size(1))
         y = torch.empty(xu.size(0), F, dtype=torch.float32, device=dev)
         outs.append(y)
         a = arr[i]
         a.x_up, a.x_b, a.y, a.M = xu.data_ptr(), xb.data_ptr(), y.data_ptr(), xu.size(0)
-        a.ldx_up = xu.stride(0) if xu.size(0) > 1 else w_in
-        a.ldx_b = xb.stride(0) if xb.size(0) > 1 else w_in
-        a.m_dev = _ffi.dyn(xu.size(0))
+        a.ldx_up, a.ldx_b, a.m_dev = ld(xu), ld(xb), _ffi.dyn(xu.size(0))
         keep += _mlp_dim_static(a, D, F) + [xu, xb]
     _ffi.check(_ffi.lib().cwn_update_mlp_f32(arr, len(dims), F, _ffi.stream_ptr(dev)), 'cwn_update_mlp_f32')
     return outs
@@ -3620,8 +3594,7 @@ def update_mlp3(dims: Sequence[Mlp3Dim]) -> List[Tensor]:
         for k in range(3):
             x = _rowmajor16(D.xs[k], 'x')
             keep.append(x)
-            a.x[k] = x.data_ptr()
-            a.ldx[k] = x.stride(0) if x.size(0) > 1 else F
+            a.x[k], a.ldx[k] = x.data_ptr(), ld(x, F)
         a.y, a.M, a.ldy = buf.data_ptr() + off * 4 * F, rows[i], F
         a.m_dev = _ffi.dyn(rows[i])
         off += rows[i]
@@ -3690,13 +3663,12 @@ class MlpLaunch:
         outs = buf.split(rows)
         base, off, hold = buf.data_ptr(), 0, []
         for i in range(n):
-            rm = _rowmajor if self.w_in[i] < F else _rowmajor16
-            xu, xb, M = rm(xs_up[i], 'x_up'), rm(xs_b[i], 'x_b'), rows[i]
+            xu, xb, M = xs_up[i], xs_b[i], rows[i]          # (dtype, device and shape were checked above)
+            xu, xb = (rowmajor(xu), rowmajor(xb)) if self.w_in[i] < F else (rowmajor16(xu, ld(xu)), rowmajor16(xb, ld(xb)))
             hold += [xu, xb]                       # (a contiguous copy lives until the launch is enqueued)
             a = self.arr[i]
             a.x_up, a.x_b, a.y, a.M = xu.data_ptr(), xb.data_ptr(), base + off * 4 * F, M
-            a.ldx_up = xu.stride(0) if M > 1 else self.w_in[i]
-            a.ldx_b = xb.stride(0) if M > 1 else self.w_in[i]
+            a.ldx_up, a.ldx_b = (xu.stride(0), xb.stride(0)) if M > 1 else (self.w_in[i],) * 2      # (inline on the eager path: _window.ld)
             a.m_dev = _ffi.dyn(M)
             off += M
         rc = self.fn(self.arr, n, F, _ffi.stream_ptr(self.dev))
@@ -3772,7 +3744,7 @@ def pack_stage_weights_many(weights: Sequence[Tensor], transposed: bool = True, 
         w = weight.detach()
         F = int(w.size(0)) if w.dim() == 2 else 0
         if F not in (64, 128) or w.size(1) not in (F, 2 * F, 3 * F, 4 * F) or not w.is_cuda or w.dtype != torch.float32 \
-                or w.stride(1) != 1 or w.data_ptr() % 16 or w.stride(0) % 4:
+                or w.stride(1) != 1 or not is_vec16(w):
             continue
         for c0 in range(0, int(w.size(1)), F):
             by_F.setdefault(F, []).append((weight, w, c0))
@@ -3786,17 +3758,17 @@ def pack_stage_weights_many(weights: Sequence[Tensor], transposed: bool = True, 
             buf = torch.empty(n * nbytes, dtype=torch.uint8, device=dev)
             outs = [buf[k * nbytes: (k + 1) * nbytes] for k in range(n)]
             Wp = (C.c_void_p * n)(*[w.data_ptr() + 4 * c0 for _, w, c0 in part])
-            ld = (C.c_int64 * n)(*[w.stride(0) for _, w, _ in part])
+            lds = (C.c_int64 * n)(*[w.stride(0) for _, w, _ in part])
             Op = (C.c_void_p * n)(*[o.data_ptr() for o in outs])
             outs_t = [None] * n
             if transposed:                      # ... and the blocks of the transposed weight (cwn_dense_stage_bwd_f32: dX = dz W)
                 buf_t = torch.empty(n * nbytes, dtype=torch.uint8, device=dev)
                 outs_t = [buf_t[k * nbytes: (k + 1) * nbytes] for k in range(n)]
                 Tp = (C.c_void_p * n)(*[o.data_ptr() for o in outs_t])
-                _ffi.check(L.cwn_update_mlp_pack_weights_both_many_f32(Wp, ld, F, Op, Tp, n, _ffi.stream_ptr(dev)),
+                _ffi.check(L.cwn_update_mlp_pack_weights_both_many_f32(Wp, lds, F, Op, Tp, n, _ffi.stream_ptr(dev)),
                            'cwn_update_mlp_pack_weights_both_many_f32')
             else:
-                _ffi.check(L.cwn_update_mlp_pack_weights_many_f32(Wp, ld, F, Op, n, _ffi.stream_ptr(dev)),
+                _ffi.check(L.cwn_update_mlp_pack_weights_many_f32(Wp, lds, F, Op, n, _ffi.stream_ptr(dev)),
                            'cwn_update_mlp_pack_weights_many_f32')
             for (weight, w, c0), o, ot in zip(part, outs, outs_t):
                 # (a weak reference to the tensor that was packed: an entry whose weight has died -- a layer that is gone, its
@@ -3848,7 +3820,7 @@ class step_arena:
                 a.high = 0
             a.want = 0
         flat = self.flat
-        if flat is not None and (flat.dtype != torch.float32 or not flat.is_contiguous() or flat.data_ptr() % 16 or (4 * flat.numel()) % 16):
+        if flat is not None and (flat.dtype != torch.float32 or not flat.is_contiguous() or not aligned16(flat) or (4 * flat.numel()) % 16):
             flat.zero_()
             flat = None
         global _drop_site
@@ -3914,8 +3886,7 @@ def run_stage_bwd(entries, device, live=None) -> bool:
         return False
     arr = (_ffi.StageBwdDesc * len(entries))()
     keep = []
-    ok_t = lambda t, w: (t.dtype == torch.float32 and t.is_cuda and t.dim() == 2 and t.size(1) == w and t.stride(1) == 1
-                         and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0)
+    ok_t = lambda t, w: t.dtype == torch.float32 and t.is_cuda and t.dim() == 2 and t.size(1) == w and t.stride(1) == 1 and is_vec16(t)
     for k, ent in enumerate(entries):
         dy, b, W, dx, dx2 = ent[:5]
         c0 = int(ent[5]) if len(ent) > 5 else 0          # (a wider weight: the blocks W[:, c0 : c0 + F (+ F)])
@@ -3932,7 +3903,6 @@ def run_stage_bwd(entries, device, live=None) -> bool:
         ptrs = [b.scale, b.shift, b.mean, b.rstd, b.s1, b.s2, b.acc1, b.acc2, b.z, b.dz]
         if any(p is not None and p % 16 for p in ptrs) or b.ldz % 4 or (b.dz is not None and b.lddz % 4):
             return False
-        ld = lambda t: int(t.stride(0)) if t.size(0) > 1 else int(t.size(1))
         arr[k] = _ffi.StageBwdDesc(dy=dy.data_ptr(), z=b.z, dz=b.dz, scale=b.scale, shift=b.shift, mean=b.mean, rstd=b.rstd,
                                    s1=b.s1, s2=b.s2, acc1=b.acc1, acc2=b.acc2, wt_packed=w1.data_ptr(), wt2_packed=_ffi.ptr(w2),
                                    dx=dx.data_ptr(), dx2=_ffi.ptr(dx2), M=M, lddy=ld(dy), ldz=int(b.ldz), lddz=int(b.lddz),
@@ -3976,7 +3946,7 @@ def run_stage(gemms: Sequence['Gemm'], device) -> Optional[List[Tensor]]:
             return None
         for t in [X, X2] + [m[0] for m in more]:
             if t is not None and (t.dtype != torch.float32 or not t.is_cuda or t.dim() != 2 or t.size(1) != F or t.stride(1) != 1
-                                  or t.stride(0) % 4 or t.data_ptr() % 16 or t.size(0) != X.size(0)):
+                                  or not is_vec16(t) or t.size(0) != X.size(0)):
                 return None
         w1 = packed_stage_block(W, 0)
         w2 = packed_stage_block(W, F) if X2 is not None else None
@@ -3985,7 +3955,7 @@ def run_stage(gemms: Sequence['Gemm'], device) -> Optional[List[Tensor]]:
             return None
         cons = [g.bias, g.in_scale, g.in_shift, g.in_scale2, g.in_shift2]
         cons = [None if t is None else _f32c(t, 'constant') for t in cons]
-        if any(t is not None and (t.numel() != F or t.data_ptr() % 16) for t in cons):
+        if any(t is not None and (t.numel() != F or not aligned16(t)) for t in cons):
             return None
         cs = g.col_stats
         M = int(X.size(0))
@@ -3996,7 +3966,6 @@ def run_stage(gemms: Sequence['Gemm'], device) -> Optional[List[Tensor]]:
                                or not ss.is_contiguous()):
             return None
         Y = torch.empty(M, F, dtype=torch.float32, device=X.device)
-        ld = lambda t: int(t.stride(0)) if t.size(0) > 1 else F
         arr[k] = _ffi.StageDesc(X=X.data_ptr(), X2=_ffi.ptr(X2), w_packed=w1.data_ptr(), w2_packed=_ffi.ptr(w2),
                                 bias=_ffi.ptr(cons[0]), in_scale=_ffi.ptr(cons[1]), in_shift=_ffi.ptr(cons[2]),
                                 in_scale2=_ffi.ptr(cons[3]), in_shift2=_ffi.ptr(cons[4]), Y=Y.data_ptr(),
@@ -4070,13 +4039,12 @@ def run_linear_stats(gemms: Sequence['Gemm'], device) -> Optional[List[Tensor]]:
         if not Y.numel():
             continue
         cs = g.col_stats
-        ld = lambda t, w: int(t.stride(0)) if t.size(0) > 1 else max(w, 1)
         descs.append(_ffi.GemmDesc(
             X=X.data_ptr(), X2=_ffi.ptr(X2), W=W.data_ptr() + 4 * (g.w_col0 or 0), bias=_ffi.ptr(cons['bias']),
             in_scale=_ffi.ptr(cons['in_scale']), in_shift=_ffi.ptr(cons['in_shift']),
             in_scale2=_ffi.ptr(cons['in_scale2']), in_shift2=_ffi.ptr(cons['in_shift2']),
             col_sum=None if cs is None else cs[0].data_ptr(), col_sumsq=None if cs is None else cs[1].data_ptr(),
-            Y=Y.data_ptr(), M=M, ldx=ld(X, K1), ldx2=ld(X2, K2) if X2 is not None else 0, ldw=ld(W, int(W.size(1))), ldy=ld(Y, N),
+            Y=Y.data_ptr(), M=M, ldx=ld(X), ldx2=ld(X2, max(K2, 1)) if X2 is not None else 0, ldw=ld(W), ldy=ld(Y, N),
             N=N, K=K1, K2=K2, relu=0, in_relu=int(g.in_relu) & (3 if X2 is not None else 1), w_trans=0, bnb=None,
             m_dev=_ffi.dyn(M), flags=_ffi.GEMM_EXACT))
     if descs:
@@ -4238,7 +4206,7 @@ def layer_backward(dims: Sequence[LayerDim], table, ys_of, gs_of, wt_of, bwd_tab
                 if e is None or rows[d] == 0:
                     continue
                 token, z, aff, slots, _ = e
-                if (z.shape != D.x.shape or z.stride(1) != 1 or z.stride(0) % 4 or z.data_ptr() % 16 or aff.data_ptr() % 16
+                if (z.shape != D.x.shape or z.stride(1) != 1 or not is_vec16(z) or not aligned16(aff)
                         or aff.numel() != 4 * F or slots.numel() != _ffi.BN_SLOTS * 2 * F):
                     continue
                 arr[d].out_bn = _ffi.BnBwdLive(z=z.data_ptr(), aff=aff.data_ptr(), slots=slots.data_ptr(), ldz=z.stride(0))

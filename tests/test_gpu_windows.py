@@ -1181,3 +1181,66 @@ def test_weight_packers_take_a_window_of_a_wider_weight(cls):
         assert torch.equal(a, b), f'packers {cls}: pack {k} differs from the pack of the contiguous copy'
         assert bool(a.any()), k
     _form(f'packers {cls}', f'{len(got)} packs, byte-identical to the contiguous weight')
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# 12. ONE-row windows through the ops wrappers: the two forms of the 16-byte rule
+# ------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('case', ['run_stage-W3', 'run_stage-W2', 'target_head_applies-W3', 'head-W3', 'head-W2', 'update_mlp-W3'])
+def test_one_row_windows_through_the_wrappers(case):
+    """M = 1, F = 64: the smallest shapes at which "16-byte readable" judged on the RECORDED row stride and judged on the stride
+    a descriptor carries (one row: the width) differ -- W3 is [1, 67][:, :64], aligned with an odd recorded stride; W2 starts
+    4 bytes off.  Each wrapper's decision is pinned as it stands:
+      ops.run_stage             judges the recorded stride: declines both windows (None; it takes the contiguous row);
+      ops.target_head_applies   judges the recorded stride: False on W3 (True on the contiguous row);
+      ops.head                  judges the recorded stride: both blocks are copied -- the bits of the contiguous launch;
+      ops.update_mlp            `_rowmajor16` judges the stride the descriptor carries: the W3 row is kept AS IT LIES (the W2
+                                row is copied) -- the bits of the contiguous launch.
+    Inputs keep their bits in every case."""
+    op, cls = case.split('-')
+    F = 64
+    g = torch.Generator().manual_seed(len(case))
+    X, X2 = _rand(g, 1, F), _rand(g, 1, F)
+    ws = Windows(DEV)
+    x = ws.inp('x', X, cls)
+    assert x.size(0) == 1 and (x.stride(0) % 4 != 0 if cls == 'W3' else not aligned16(x)), case
+    if op == 'run_stage':
+        W, bias = _stage_weight(g, F, 1), _rand(g, F).to(DEV)
+        taken = ops.run_stage([ops.Gemm(X=X.to(DEV), W=W.detach(), bias=bias)], DEV)
+        assert taken is not None, f'{case}: the contiguous row was to run on the stage kernel'
+        gm = ops.Gemm(X=x, W=W.detach(), bias=bias)
+        assert ops.run_stage([gm], DEV) is None, case
+        ref = X.double() @ W.detach().cpu().double().t() + bias.cpu().double()
+        gate(taken[0], ref, case + ' (contiguous, stage kernel)')
+        gate(ops.run_gemm([gm], DEV)[0], ref, case + ' (cwn_gemm_f32)')
+        _form(case, 'ops.run_stage declines (None), cwn_gemm_f32 serves the window')
+    elif op == 'target_head_applies':
+        Wd, bd, rows = (_rand(g, 5, F) / F ** 0.5).to(DEV), _rand(g, 5).to(DEV), torch.zeros(1, dtype=torch.int32, device=DEV)
+        assert ops.target_head_applies(X.to(DEV), rows, Wd, bd) is True, case
+        assert ops.target_head_applies(x, rows, Wd, bd) is False, case
+        _form(case, 'ops.target_head_applies: False')
+    elif op == 'head':
+        H2, O = 8, 3
+        W1, b1, W2, b2 = _rand(g, H2, F) / F ** 0.5, _rand(g, H2), _rand(g, O, H2) / H2 ** 0.5, _rand(g, O)
+        dev = [t.to(DEV) for t in (W1, b1, W2, b2)]
+        ptr = _cell_ptr(1)
+        ptr_d, Cn = ptr.to(DEV), ptr.numel() - 1
+        run = lambda t: ops.head([t], [ptr_d], Cn, [dev[0]], [dev[1]], dev[2], dev[3])
+        got, want = run(x), run(X.to(DEV))
+        rp = torch.stack([X[ptr[c]:ptr[c + 1]].double().sum(0) for c in range(Cn)])
+        ws.no_leak(got, case)
+        gate(got, (rp @ W1.double().t() + b1.double()).relu() @ W2.double().t() + b2.double(), case)
+        assert torch.equal(got, want), f'{case}: not the bits of the contiguous launch'
+        _form(case, 'ops.head copies the block')
+    else:
+        lins, folds = _mlp_net(g, F, F, 2)
+        xb = ws.inp('xb', X2, cls)
+        assert ops._rowmajor16(x, 'x_up') is x and ops._rowmajor16(xb, 'x_b') is xb, f'{case}: the row was to be kept as it lies'
+        run = lambda u, b: ops.update_mlp([ops.MlpDim(x_up=u, x_b=b, linears=lins, folds=_mlp_dev_folds(folds))])[0]
+        got, want = run(x, xb), run(X.to(DEV), X2.to(DEV))
+        ws.no_leak(got, case)
+        gate(got, _mlp_ref([X, X2], lins, folds, 1), case)
+        assert torch.equal(got, want), f'{case}: not the bits of the contiguous launch'
+        _form(case, 'ops.update_mlp keeps the row as it lies')
+    torch.cuda.synchronize()
+    ws.neighbours(case)
