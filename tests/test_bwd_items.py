@@ -174,6 +174,104 @@ def test_owner_table_executed_on_the_cpu_reproduces_autograd(n, F, kind):
             np.testing.assert_allclose(gy2[d], gy2_ref[d].numpy(), rtol=1e-10, atol=1e-10)
 
 
+def _int_problem(b, F, seed):
+    """`_problem` with integer values (x in [-3, 3], W in {-1, 0, 1}, bias, gU, gB in [-2, 2]) and eps that are multiples of
+    1/4, distinct per level and per stream: every sum is exact in float64, and masks really tie at 0."""
+    g = torch.Generator().manual_seed(seed)
+    P = _problem(b, F, seed)
+    ri = lambda lo, hi, *shape: torch.randint(lo, hi + 1, shape, generator=g).double()
+    for d in range(len(P['x'])):
+        n = P['x'][d].size(0)
+        P['x'][d], P['W'][d], P['bias'][d] = ri(-3, 3, n, F), ri(-1, 1, F, 2 * F), ri(-2, 2, F)
+        P['gU'][d], P['gB'][d] = ri(-2, 2, n, F), ri(-2, 2, n, F)
+        P['eps1'][d], P['eps2'][d] = (0.5, 0.25, 1.0)[d], (-0.25, 0.75, -0.5)[d]
+    return P
+
+
+# case -> {F: None (no table) or [(dimension, flags, {field: value})]: a record with these fields exists}
+_N_O, _N_A, _NE_A, _NE_B, _NE_BD = R_OWN_N, R_ABOVE_N, R_UPA_NE, R_UPB_NE, R_BND_NE
+_ALL = PA | PB | TOP
+_BOTH = lambda recs: {128: recs, 64: recs}
+_ONLY_64 = lambda recs: {128: None, 64: recs}
+_STRUCTURE_RECORDS = {
+    'K6': _BOTH([(1, _ALL, {_N_O: 15, _N_A: 20})]),
+    'K7': _ONLY_64([(1, _ALL, {_N_O: 21, _N_A: 35})]),
+    'strip16': _BOTH([(1, _ALL, {_N_O: 33, _N_A: 16})]),
+    'strip17': _ONLY_64([(1, _ALL, {_N_O: 35, _N_A: 17})]),
+    'strip33': _ONLY_64([(1, _ALL, {_N_O: 67, _N_A: 33})]),
+    'ring18': _BOTH([(1, _ALL, {_N_A: 1, _NE_A: 306})]),
+    'ring16': _BOTH([(1, _ALL, {_N_A: 1, _NE_A: 240})]),
+    'star32': _BOTH([(0, PA | TOP, {_N_O: 33, _N_A: 32})]),
+    'star33': _ONLY_64([(0, PA | TOP, {_N_A: 33})]),
+    'star64': _ONLY_64([(0, PA | TOP, {_N_O: 65, _N_A: 64})]),
+    'star65': {128: None, 64: None},
+    'path33': _BOTH([(0, PA | TOP, {_N_O: 33, _N_A: 32})]),
+    'path34': _ONLY_64([(0, PA | TOP, {_N_A: 33})]),
+    # the isolated vertex: a record of one owned row and nothing else; the lone bond: an edges record whose TOP block is empty
+    'mixed': _BOTH([(0, PA, {_N_O: 1, _N_A: 0, _NE_A: 0, _NE_B: 0, _NE_BD: 0}), (1, _ALL, {_N_O: 1, _N_A: 0, _NE_A: 0})]),
+    'bag600': _BOTH([]),
+}
+
+
+@pytest.mark.parametrize('F', [128, 64])
+@pytest.mark.parametrize('case', list(_STRUCTURE_RECORDS))
+def test_owner_table_of_non_molecular_structures(case, F):
+    """Structures the molecular generators never produce (tests/_structures.py): TOP row counts of 1, of a power of two, at
+    the cap and one past it; rows with 32, 33 and 64 matches; own rows one past a round of lane groups; records without
+    entries or without TOP rows; items over several complexes some of which are empty in a dimension.  Where the table
+    exists its records are the expected ones and, executed on integers, reproduce autograd with one writer per row; where a
+    complex is beyond a workgroup there is none.  (Separates a wrong table from a wrong kernel: tests/test_gpu_bwd_structures.py
+    runs the same cases on the device.)"""
+    from cwn_amd.blockplan import BlockPlan
+    from tests import _structures as S
+    assert set(_STRUCTURE_RECORDS) == set(S.CASES)
+    b = S.host_batch(case)
+    P = _int_problem(b, F, seed=11)
+    has_up = [u is not None for u in P['up']]
+    t = BlockPlan.from_batch(b).bwd_items(F, has_up)
+    want = _STRUCTURE_RECORDS[case][F]
+    assert (want is not None) == S.CASES[case][2 if F == 128 else 3], 'tests/_structures.py: CASES disagrees'
+    if want is None:
+        assert t is None
+        return
+    assert t is not None
+    tab = t.host
+    assert tab.shape[1] == 16 and tab.dtype == np.int32
+    assert 0 < t.lds_bytes <= 160 * 1024 and int(tab[:, R_LDS].max()) == t.lds_bytes
+    assert (tab[:, R_OWN_N] <= (256 if F == 64 else 96)).all() and (tab[:, R_OWN_N] > 0).all()
+    top = (tab[:, R_FLAGS] & TOP) != 0
+    assert (tab[top, R_ABOVE_N] <= 1024 // (F // 4)).all()
+    assert (tab[:, [R_UPA_NE, R_UPB_NE, R_BND_NE]] <= 1024).all()
+    for dim, flags, fields in want:
+        hits = [r for r in tab if int(r[R_DIM]) == dim and (int(r[R_FLAGS]) & 7) == flags
+                and all(int(r[k]) == v for k, v in fields.items())]
+        assert hits, (case, F, dim, flags, fields, tab[:, :14].tolist()[:8])
+    if case == 'mixed':
+        assert t.n_items == 5
+    if case == 'bag600':
+        C = len(b.cochains[0].__num_cells_list__)
+        assert C == 600 and t.n_items < 2 * C
+        # an item spans several complexes (the largest complex of the bag has five vertices and six edges) ...
+        assert tab[tab[:, R_DIM] == 0, R_OWN_N].max() > 5 and tab[tab[:, R_DIM] == 1, R_OWN_N].max() > 6
+        # ... some of them empty in a dimension: 600 complexes, fewer with an edge, fewer still with a 2-cell
+        n1, n2 = (np.asarray([n or 0 for n in b.cochains[d].__num_cells_list__]) for d in (1, 2))
+        assert (n1 == 0).any() and ((n1 > 0) & (n2 == 0)).any() and (n2 > 0).any()
+    dx_ref, gy1_ref, gy2_ref, Y1, Y2 = _autograd(P, F)
+    # the masks of this problem really tie: some live entry has Y1[src] + Y2[cof] == 0 in some column, some a negative sum
+    sums = torch.cat([(Y1[d][P['up'][d][0]] + Y2[d + 1][P['sh'][d]]).flatten() for d in range(len(has_up)) if has_up[d]])
+    assert (sums == 0).any() and (sums < 0).any() and (sums > 0).any()
+    dx, gy1, gy2, cnt = _execute(tab, P, Y1, Y2, F)
+    for d in range(len(dx)):
+        assert (cnt['dx'][d] == 1).all(), f'dx[{d}]: a row without exactly one owner'
+        np.testing.assert_allclose(dx[d], dx_ref[d].numpy(), rtol=1e-10, atol=1e-10)
+        if gy1_ref[d] is not None:
+            assert (cnt['gy1'][d] == 1).all(), f'gY1[{d}]: a row without exactly one owner'
+            np.testing.assert_allclose(gy1[d], gy1_ref[d].numpy(), rtol=1e-10, atol=1e-10)
+        if gy2_ref[d] is not None:
+            assert (cnt['gy2'][d] == 1).all(), f'gY2[{d}]: a row without exactly one owner'
+            np.testing.assert_allclose(gy2[d], gy2_ref[d].numpy(), rtol=1e-10, atol=1e-10)
+
+
 def test_owner_table_limits_and_bad_arguments():
     """A complex beyond a workgroup gives no table (the caller keeps the streaming backward); argument checks."""
     from cwn_amd import _ffi

@@ -419,24 +419,8 @@ def test_blocked_layer_random_structures_vs_oracle(seed):
         cs.append(lifting.ring_lift(n, bonds, torch.zeros(n, 1), torch.zeros(3, 1), max_k=6, y=torch.zeros(1)))
     b = ComplexBatch.from_complex_list(cs, max_dim=2)
     # duplicate a few entries inside their complex's slice (kept grouped: the table is per complex)
-    for d in range(2):
-        c = b.cochains[d]
-        if c.upper_index is None or c.upper_index.size(1) == 0:
-            continue
-        sl = list(c.__slices__['upper_index'])
-        cols, new_sl = [], [0]
-        for s0, e0 in zip(sl[:-1], sl[1:]):
-            idx = list(range(s0, e0))
-            if idx and rng.random() < 0.5:
-                idx += [int(rng.choice(idx))] * int(rng.integers(1, 3))
-            cols += idx
-            new_sl.append(len(cols))
-        perm = torch.tensor(cols, dtype=torch.long)
-        c.upper_index = c.upper_index[:, perm].contiguous()
-        c.shared_coboundaries = c.shared_coboundaries[perm].contiguous()
-        c.__slices__['upper_index'] = new_sl
-        if 'shared_coboundaries' in c.__slices__:
-            c.__slices__['shared_coboundaries'] = new_sl
+    from tests._structures import duplicate_entries
+    duplicate_entries(b, rng)
     b = b.to(DEV)
     F = 128 if seed % 2 == 0 else 64
     g = torch.Generator().manual_seed(seed)
