@@ -843,7 +843,9 @@ def embed_front(v_weights: Sequence[Tensor], v_feats: Tensor, e_weights: Optiona
     H = int(v_weights[0].size(1))
     keep: list = []
     tv = _embed_table(v_weights, v_feats, keep)
-    te = _embed_table(e_weights, e_feats, keep) if e_weights is not None else None
+    # (a batch without a single edge -- isolated vertices only -- has no edge features to hand over: an empty tensor's null
+    #  address is what cwn_embed_front_f32 refuses as a table without features; with n1 = 0 there is nothing to embed)
+    te = _embed_table(e_weights, e_feats, keep) if e_weights is not None and int(n1) > 0 else None
     n0 = int(v_feats.size(0))
     # one allocation for the three outputs (rows of H floats: every block 16-B aligned)
     buf = torch.empty(n0 + n1 + n2, H, dtype=torch.float32, device=dev)
@@ -898,7 +900,7 @@ class FrontLaunch:
         self.H = H = int(v_weights[0].size(1))
         self.keep: list = []
         self.tv = _embed_table(v_weights, v_feats, self.keep)
-        self.te = _embed_table(e_weights, e_feats, self.keep) if e_weights is not None else None
+        self.te = _embed_table(e_weights, e_feats, self.keep) if e_weights is not None and int(n1) > 0 else None    # (embed_front)
         self.dtypes = (v_feats.dtype, None if e_feats is None else e_feats.dtype)
         self.adjs, self.bi = (adj1, adj2), (bi1, bi2)
         self.marks = _marks(list(v_weights) + list(e_weights or []) + [bi1, bi2])       # (the plans belong to the indices' values)
@@ -920,7 +922,7 @@ class FrontLaunch:
         n0, n1, n2 = self.n
         for f, n, dt, tab in ((v_feats, n0, self.dtypes[0], self.tv), (e_feats, n1, self.dtypes[1], self.te)):
             if tab is None:
-                if f is not None:
+                if f is not None and (n > 0 or f.size(0) > 0):
                     return None
                 continue
             if (f is None or f.dtype != dt or f.dim() != 2 or f.size(0) != n or f.size(1) != tab.cols or not f.is_contiguous()

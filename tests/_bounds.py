@@ -77,6 +77,40 @@ def scale(x: Tracked, s, shift=None) -> Tracked:
     return Tracked(v, c)
 
 
+# elementwise forms (an optimizer's update): every result is rounded once, and the incoming amplifications pass through the
+# first derivatives
+def scalar(x, c: float = 0.0) -> Tracked:
+    """A scalar that broadcasts: a hyperparameter as the kernel holds it (c = 0), or a value computed on the way (c > 0)."""
+    return Tracked(torch.tensor(float(x), dtype=torch.float64), torch.tensor(float(c), dtype=torch.float64))
+
+
+def sub(a: Tracked, b: Tracked) -> Tracked:
+    v = a.v - b.v
+    return Tracked(v, a.c + b.c + v.abs())
+
+
+def mul(a: Tracked, b: Tracked) -> Tracked:
+    v = a.v * b.v
+    return Tracked(v, a.c * b.v.abs() + a.v.abs() * b.c + v.abs())
+
+
+def div(a: Tracked, b: Tracked) -> Tracked:
+    v = a.v / b.v
+    return Tracked(v, a.c / b.v.abs() + v.abs() * b.c / b.v.abs() + v.abs())
+
+
+def sqrt(a: Tracked) -> Tracked:
+    """d sqrt(x) = dx / (2 sqrt(x)); a.v > 0."""
+    v = a.v.sqrt()
+    return Tracked(v, a.c / (2 * v) + v.abs())
+
+
+def power(a: Tracked, t: float) -> Tracked:
+    """a^t for an exact exponent t >= 1: d a^t = t a^(t-1) da."""
+    v = a.v ** t
+    return Tracked(v, a.c * t * a.v.abs() ** (t - 1) + v.abs())
+
+
 def cat(xs) -> Tracked:
     return Tracked(torch.cat([x.v for x in xs], 1), torch.cat([x.c for x in xs], 1))
 

@@ -147,6 +147,24 @@ def test_argument_errors_without_gpu():
     assert lib.cwn_collate_guard(None, 3, 10, 8, 1, 0, None, None, None) == 1
 
 
+def test_embedding_backward_refuses_before_it_launches():
+    """cwn_embedding_bwd_f32 answers from its arguments alone (the addresses are never read): at a width other than 64 / 128 /
+    256 the whole table lives in one workgroup's LDS, so V * H * 4 beyond 60 KiB is CWN_ERR_TOO_LARGE; gradient rows of a
+    width that is a multiple of four are read 16 bytes a lane, so a misaligned g is CWN_ERR_ALIGN -- and is not at other widths."""
+    lib = _ffi.lib()
+    a = 1 << 20                                                     # a 16-byte aligned address nobody dereferences
+    assert lib.cwn_embedding_bwd_f32(a, a, None, None, a, 8, 1, 96, 161, 0, None, None) == 2      # 161 * 96 * 4 = 61 824 > 61 440
+    assert lib.cwn_embedding_bwd_f32(a, a, None, None, a, 8, 1, 30, 513, 0, None, None) == 2      # the scalar sub-branch too
+    assert lib.cwn_embedding_bwd_f32(a, a, None, None, a, 8, 3, 260, 60, 0, None, None) == 2
+    for H in (4, 12, 64, 96, 128, 256, 260):
+        assert lib.cwn_embedding_bwd_f32(a + 4, a, None, None, a, 8, 1, H, 8, 0, None, None) == 5, H
+        assert lib.cwn_embedding_bwd_f32(a + 8, a, None, None, a, 8, 1, H, 8, 0, None, None) == 5, H
+    assert lib.cwn_embedding_bwd_f32(a + 4, a, None, None, a, 8, 1, 96, 161, 0, None, None) == 5   # alignment is judged first
+    for bad in ((-1, 1, 64, 28), (8, 0, 64, 28), (8, 1, 0, 28), (8, 1, 64, 0)):                     # rows, cols, H, V
+        assert lib.cwn_embedding_bwd_f32(a, a, None, None, a, *bad, 0, None, None) == 1, bad
+    assert lib.cwn_embedding_bwd_f32(a, a, None, None, None, 8, 1, 30, 8, 0, None, None) == 1       # no dW
+
+
 def test_item_table_builder_rejects_tables_that_are_not_prefix_sums():
     """cwn_layer_items_build (host C++) reads caller-provided per-complex tables: one that does not start at 0,
     decreases, or sums past the int32 record fields is refused, not cut into records with negative counts."""

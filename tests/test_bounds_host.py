@@ -169,3 +169,135 @@ def test_equivariance_of_the_emulations():
     B.equivariant(grd, plain, B.grade_rows(M), B.grade_cols(N), 'split emulation')
     with pytest.raises(AssertionError, match='change under'):
         B.equivariant(grd + 1e-9, plain + 1e-9, B.grade_rows(M), B.grade_cols(N), 'split emulation with an absolute constant')
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Adam, one launch (tests/_adam.py): the gates of tests/test_gpu_adam_componentwise.py over numpy float32
+# ---------------------------------------------------------------------------------------------------------------------------
+from tests import _adam as A          # noqa: E402
+
+
+def test_elementwise_tracked_forms():
+    """mul, div, sqrt, power and sub bound float32 results on graded operands, and see a relative error of 2^-20."""
+    g = torch.Generator().manual_seed(4)
+    a = (torch.rand(300, generator=g) + 0.5) * B._grade(300, 7, 41, 20)
+    b = (torch.rand(300, generator=g) + 0.5) * B._grade(300, 11, 41, 20) * (torch.randint(0, 2, (300,), generator=g) * 2.0 - 1)
+    forms = {'mul': (a * b, B.mul(B.inp(a), B.inp(b))), 'div': (a / b, B.div(B.inp(a), B.inp(b))),
+             'sqrt': (a.sqrt(), B.sqrt(B.inp(a))), 'sub': (a - b, B.sub(B.inp(a), B.inp(b))),
+             'sqrt of a product': ((a * a).sqrt(), B.sqrt(B.mul(B.inp(a), B.inp(a)))),
+             'scaled': (a * 0.75, B.mul(B.scalar(0.75), B.inp(a))),
+             'cube': (a * a * a, B.power(B.inp(a), 3.0))}
+    for name, (got, t) in forms.items():
+        assert got.dtype == torch.float32
+        assert B.ratio(got, t, name) <= (B.RIGOROUS if name != 'cube' else 2 * B.RIGOROUS)      # (a a a: two roundings for power's one)
+        assert B.ratio(got * (1 + 2.0 ** -20), t, name + ' times 1 + 2^-20') > B.RIGOROUS
+    s = B.scalar(0.1)
+    assert float(s.c) == 0.0 and s.v.dtype == torch.float64 and float(B.scalar(2.0, 3.0).c) == 3.0
+
+
+@pytest.mark.parametrize('hyper', A.HYPERS, ids=A.HYPER_IDS)
+def test_adam_operands_are_graded_and_normal(hyper):
+    p, g, m, v = A.operands(4099, hyper)
+    tiny = 2.0 ** -120
+    assert float(g.abs().min()) < 2.0 ** -39 and 2.0 ** 9 <= float(g.abs().max()) < 2.0 ** 10
+    assert float(p.abs().min()) < 2.0 ** -19 and 0.5 <= float(p.abs().max()) < 1.0
+    for x in (p, g, m, v, (1 - A.f32(hyper[1])) * g.double() * g.double()):
+        assert float(x.abs().min()) > tiny
+    m1, v1, p1 = A.reference(p, g, m, v, 1, hyper)
+    eps = A.f32(A.EPS)
+    # sqrt(v') on both sides of eps: far below it without weight decay; with it wd |p| >= 2^-27 is a floor under |gr|
+    assert float(v1.v.sqrt().min()) < eps * (2.0 ** -10 if hyper[2] == 0 else 1.0) and float(v1.v.sqrt().max()) > eps * 2.0 ** 20
+    gr = g.double() + A.f32(hyper[2]) * p.double()
+    opposite = (m.double() * gr) < 0
+    assert 0.3 < float(opposite.double().mean()) < 0.7                    # b1 m and (1 - b1) gr of opposite sign
+    assert float(((p1.v - p.double()).abs() > p.double().abs() * 2.0 ** -10).double().mean()) > 0.3        # the update is visible in p'
+
+
+@pytest.mark.parametrize('t', A.STEPS)
+@pytest.mark.parametrize('hyper', A.HYPERS, ids=A.HYPER_IDS)
+def test_adam_float32_restatement_passes_both_gates(hyper, t):
+    """The kernel's formula in numpy float32 meets (R) on the moments and (E) on the parameter at every size, with room: (R)
+    with 2x to spare (measured 0.95 at the most), and its own p' ratio stays below 1, so the limit of (E) is MARGIN."""
+    for n in A.SIZES:
+        ops = A.operands(n, hyper)
+        good = A.restatement(*ops, t, hyper)
+        rm, rv, e, limit, rc = A.check(good, A.reference(*ops, t, hyper), good, f'Adam restatement {hyper} t={t} n={n}')
+        assert rm <= B.RIGOROUS / 2 and rv <= B.RIGOROUS / 2 and rc <= 1.0 and limit == B.MARGIN, (rm, rv, rc)
+
+
+def _altered_cases():
+    """(alteration, hyper, t, n) at which the alteration changes the float32 result at all: decoupled decay needs wd > 0; in
+    float32 sqrt(1 - b2^t) is 1 from t = 1e5 on (and 1 - 4e-5 at b2 = 0.99, t = 1000), where eps / bc2_sqrt is eps and the
+    corrections at t and t - 1 coincide; a tail exists where n % 4 != 0; the eps variants need elements with sqrt(v') below eps,
+    which a handful of elements need not hold."""
+    out = []
+    for hyper in A.HYPERS:
+        for t in A.STEPS:
+            short = t <= 10 or (t == 1000 and hyper[1] == 0.999)
+            out.append(('eps_in_root', hyper, t, 4099))
+            if short:
+                out.append(('eps_over_bc2', hyper, t, 4099))
+            if short and t >= 2:
+                out.append(('bias_at_t_minus_1', hyper, t, 4099))
+            if hyper[2] > 0:
+                out.append(('decoupled_wd', hyper, t, 4099))
+            out += [('tail_unwritten', hyper, t, n) for n in A.SIZES if n % 4]
+    return out
+
+
+def test_adam_altered_restatements_fail():
+    """Every wrong Adam of ALTERED is refused by the gates that pass the restatement, wherever it differs from it in float32
+    (_altered_cases) -- the p'-only ones by (E) alone, asserted at 10x the limit (measured: bias corrections at t - 1 = 999,
+    beta2 = 0.999: ratio 412 against 8; everywhere else above 9e3).
+
+    What the parameter gate these tests stand beside (tests/test_gpu_parity.py::test_flat_adam_matches_torch_adam: float32
+    torch.optim.Adam, rtol 2e-5 + atol 2e-6, five steps on randn parameters, gradients randn * 10^(it - 2), betas (0.9, 0.99),
+    wd 0.01) makes of the same alterations is measured by test_what_the_old_parameter_gate_makes_of_the_alterations below."""
+    for alt, hyper, t, n in _altered_cases():
+        ops = A.operands(n, hyper)
+        good, bad = A.restatement(*ops, t, hyper), A.restatement(*ops, t, hyper, alter=alt)
+        fig = A.judge(bad, A.reference(*ops, t, hyper), good, f'Adam {alt} {hyper} t={t} n={n}')
+        assert not A.passes(fig), (alt, hyper, t, n, fig)
+        rm, rv, e, limit, rc = fig
+        if alt in ('eps_in_root', 'eps_over_bc2', 'bias_at_t_minus_1'):
+            assert rm <= B.RIGOROUS and rv <= B.RIGOROUS and e > 10 * limit, (alt, hyper, t, n, fig)
+        if alt in ('decoupled_wd', 'tail_unwritten'):
+            assert rm > B.RIGOROUS and rv > B.RIGOROUS, (alt, hyper, t, n, fig)
+
+
+def _old_gate(alter, first_step, n=35000):
+    """tests/test_gpu_parity.py::test_flat_adam_matches_torch_adam with the restatement (altered from step `first_step` on) in
+    the kernel's place: max over five steps of |p - p_torch| / (2e-6 + 2e-5 |p_torch|); <= 1 passes."""
+    torch.manual_seed(0)
+    p = torch.randn(n)
+    q = torch.nn.Parameter(p.clone())
+    ref = torch.optim.Adam([q], lr=3e-3, betas=(0.9, 0.99), eps=1e-8, weight_decay=0.01)
+    m, v = torch.zeros(n), torch.zeros(n)
+    g = torch.Generator().manual_seed(1)
+    worst = 0.0
+    for it in range(5):
+        gr = torch.randn(n, generator=g) * 10.0 ** (it - 2)
+        q.grad = gr.clone()
+        ref.step()
+        m, v, p = A.restatement(p, gr, m, v, it + 1, (0.9, 0.99, 0.01), lr=3e-3, alter=alter if it + 1 >= first_step else None)
+        worst = max(worst, float(((p - q.data).abs() / (2e-6 + 2e-5 * q.data.abs())).max()))
+    return worst
+
+
+def test_what_the_old_parameter_gate_makes_of_the_alterations():
+    """The old gate, emulated on the CPU over its own data (35 000 elements, as its shapes hold), in units of its tolerance:
+
+        the restatement itself                               0.007    passes
+        eps divided by bc2_sqrt along with sqrt(v)           0.08     PASSES when wrong from step 2 on (at step 1 alone it
+                                                                      is refused whenever a |g| below ~1e-5 was drawn)
+        eps inside the root                                  270      refused
+        decoupled weight decay                               1.1e3    refused
+        bias corrections at t - 1 from step 2 on             800      refused
+
+    So on its data that gate does tell three of the four apart (its gradients randn * 1e-2 reach below sqrt(eps), and wd p is as
+    large as they are); what it never sees is the moments, beta2 = 0.999, the tail path and t beyond 5.  The tail alteration
+    cannot reach it: FlatGradBucket pads every parameter to a multiple of four."""
+    assert _old_gate(None, 1) <= 0.1
+    assert _old_gate('eps_over_bc2', 2) <= 0.5
+    for alt in ('eps_in_root', 'decoupled_wd', 'bias_at_t_minus_1'):
+        assert _old_gate(alt, 2) > 50, alt

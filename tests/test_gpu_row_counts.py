@@ -749,7 +749,7 @@ BAD_INDEX = 10 ** 6            # what the padding rows of an index input hold: f
 
 @pytest.mark.parametrize('H,sizes,f32', [(64, (28,), False), (128, (9, 5, 4), False), (32, (9, 5, 4), True)])
 def test_embedding_backward_device_side_row_count(H, sizes, f32):
-    """cwn_embedding_bwd_f32 (csrc/cwn_ends.hip): "n_dev: the actual number of rows (n_rows = capacity)" -- dW takes the live rows
+    """cwn_embedding_bwd_f32 (csrc/cwn_norm.hip): "n_dev: the actual number of rows (n_rows = capacity)" -- dW takes the live rows
     only; the padding rows hold NaN gradients and an index far outside the table, which is neither looked up nor reported.  The
     banded form (H = 64 / 128, one table and three) and the table-in-LDS form (H = 32), int64 and float32 indices; dW is added to
     (a count of 0 leaves it as it was).  Live counts: LIVES."""
