@@ -82,10 +82,7 @@ template <int VEC, bool NARROW, bool SMALL>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(SMALL ? 8 : 1, 8)))
 void aggregate_kernel(AggBatch B) {
     __shared__ float part[kThreads * VEC];
-    int di = 0;
-#pragma unroll
-    for (int i = 1; i < CWN_MAX_DESCS; ++i)
-        if (i < B.n && (int)blockIdx.x >= B.blk_start[i]) di = i;
+    const int di = cwn::group_of<CWN_MAX_DESCS>(B.blk_start, B.n, (int)blockIdx.x);
     // By VALUE.  hipcc passes the batch struct through a private copy that it normally folds back
     // into kernarg loads; with `const cwn_agg_desc& D = B.d[di]` and enough inlined uses of D (the
     // NARROW variant) it stopped doing so and the whole 1.2-KB struct landed in scratch: every
@@ -144,13 +141,15 @@ extern "C" int cwn_aggregate_f32(const cwn_agg_desc* descs, int n, cwn_stream_t 
         }
         if (v < vec) vec = v;
     }
+    cwn::BlockFill fill(B.blk_start);
     for (int i = 0; i < n; ++i) {
         B.d[i] = descs[i];
         B.fgroup[i] = pick_group(descs[i].F, vec);
         B.group[i] = B.fgroup[i] < 8 ? 8 : B.fgroup[i];     // narrow features: 8 lanes per row anyway
+        const int rows_per_block = kThreads / B.group[i];
+        if (!fill.push(i, (B.d[i].n_dst + rows_per_block - 1) / rows_per_block)) return CWN_ERR_TOO_LARGE;
     }
-    const int64_t blocks = fill_blk_start(B);
-    if (blocks < 0) return CWN_ERR_TOO_LARGE;
+    const int64_t blocks = fill.close(n);
     if (blocks == 0) return CWN_OK;
     hipStream_t stream = (hipStream_t)stream_;
     const dim3 grid((unsigned)blocks), block(kThreads);

@@ -24,6 +24,7 @@
 #include "cwn_act.h"
 #include "cwn_check.h"
 #include "cwn_mem.h"
+#include "cwn_group.h"
 
 namespace {
 
@@ -350,10 +351,7 @@ template <class real, bool SMALL>
 __global__ __launch_bounds__(kThreads) void aggregate_act_kernel(ActBatch<real> B) {
     constexpr int kMaxVec = 16 / (int)sizeof(real);
     __shared__ real part[kThreads * kMaxVec];
-    int di = 0;
-#pragma unroll
-    for (int i = 1; i < CWN_MAX_DESCS; ++i)
-        if (i < B.n && (int)blockIdx.x >= B.blk_start[i]) di = i;
+    const int di = cwn::group_of<CWN_MAX_DESCS>(B.blk_start, B.n, (int)blockIdx.x);
     // By VALUE: a reference into B put the whole batch struct of the f32 aggregate kernel in scratch (cwn_aggregate.hip).
     const typename DescOf<real>::type D = B.d[di];
     const int vec = B.vec[di];
@@ -437,14 +435,12 @@ int launch_act(const typename DescOf<real>::type* descs, int n, cwn_stream_t str
         small = small && (D.flags & CWN_AGG_SMALL_OPERANDS) != 0 &&
                 (uint64_t)D.n_dst * (uint64_t)D.F * sizeof(real) < (1ull << 32);
     }
-    int64_t blocks = 0;
+    cwn::BlockFill fill(B.blk_start);
     for (int i = 0; i < n; ++i) {
         const int rows_per_block = kThreads / B.group[i];
-        B.blk_start[i] = (int32_t)blocks;
-        blocks += (B.d[i].n_dst + rows_per_block - 1) / rows_per_block;
-        if (blocks >= INT32_MAX) return CWN_ERR_TOO_LARGE;
+        if (!fill.push(i, (B.d[i].n_dst + rows_per_block - 1) / rows_per_block)) return CWN_ERR_TOO_LARGE;
     }
-    for (int i = n; i <= CWN_MAX_DESCS; ++i) B.blk_start[i] = (int32_t)blocks;
+    const int64_t blocks = fill.close(n);
     if (blocks == 0) return CWN_OK;
     hipStream_t stream = (hipStream_t)stream_;
     const dim3 grid((unsigned)blocks), block(kThreads);

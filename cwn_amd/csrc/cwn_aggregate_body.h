@@ -13,6 +13,7 @@
 #pragma once
 #include "cwn_check.h"
 #include "cwn_act.h"
+#include "cwn_group.h"
 
 namespace {
 
@@ -263,7 +264,7 @@ __device__ __forceinline__ void run_desc(const desc_t& D, int blk, int nblk, int
     const bool has_long = D.long_rows != nullptr && D.n_long != nullptr && D.rowptr != nullptr;
     const int64_t row = (int64_t)blk * R + gq;
     // destination rows that exist (include/cwn_hip.h, "device-side row counts"; D.n_dst is then the capacity)
-    const int64_t n_dst = D.m_dev != nullptr ? *D.m_dev : D.n_dst;
+    const int64_t n_dst = cwn::rows_vouched(D.m_dev, D.n_dst);
     int start = 0, end = 0;
     if (row < n_dst && D.rowptr != nullptr) {
         start = D.rowptr[row];
@@ -388,21 +389,6 @@ inline int check_desc(const desc_t& D) {
     }
     if (D.n_dst >= INT32_MAX) return CWN_ERR_TOO_LARGE;
     return CWN_OK;
-}
-
-// First workgroup of every descriptor of a batch whose d / group are filled in; returns the grid
-// size, -1 when it does not fit int32.
-template <class Batch>
-int64_t fill_blk_start(Batch& B) {
-    int64_t blocks = 0;
-    for (int i = 0; i < B.n; ++i) {
-        const int rows_per_block = kThreads / B.group[i];
-        B.blk_start[i] = (int32_t)blocks;
-        blocks += (B.d[i].n_dst + rows_per_block - 1) / rows_per_block;
-        if (blocks >= INT32_MAX) return -1;
-    }
-    for (int i = B.n; i <= CWN_MAX_DESCS; ++i) B.blk_start[i] = (int32_t)blocks;
-    return blocks;
 }
 
 // NARROW kernel: some descriptor's rows have entry slots next to their feature lanes

@@ -79,10 +79,7 @@ template <int VEC, bool NARROW, bool SMALL>
 __global__ __launch_bounds__(kThreads)
 void aggregate_f64_kernel(AggBatch64 B) {
     __shared__ double part[kThreads * VEC];
-    int di = 0;
-#pragma unroll
-    for (int i = 1; i < CWN_MAX_DESCS; ++i)
-        if (i < B.n && (int)blockIdx.x >= B.blk_start[i]) di = i;
+    const int di = cwn::group_of<CWN_MAX_DESCS>(B.blk_start, B.n, (int)blockIdx.x);
     // By VALUE: a reference into B put the whole batch struct of the f32 NARROW kernel in scratch
     // (20x slower; the measurement is at the same line of aggregate_kernel).
     const cwn_agg_desc_f64 D = B.d[di];
@@ -141,15 +138,17 @@ extern "C" int cwn_aggregate_f64(const cwn_agg_desc_f64* descs, int n, cwn_strea
             if (p != nullptr && !al8(p)) return CWN_ERR_ALIGN;
         if (v < vec) vec = v;
     }
+    cwn::BlockFill fill(B.blk_start);
     for (int i = 0; i < n; ++i) {
         B.d[i] = descs[i];
         B.fgroup[i] = pick_group(descs[i].F, vec);
         // narrow features (fewer than 8 feature lanes): at least two entry slots per row
         const bool few = (descs[i].F + vec - 1) / vec < 8;
         B.group[i] = B.fgroup[i] < 8 ? 8 : (few ? 2 * B.fgroup[i] : B.fgroup[i]);
+        const int rows_per_block = kThreads / B.group[i];
+        if (!fill.push(i, (B.d[i].n_dst + rows_per_block - 1) / rows_per_block)) return CWN_ERR_TOO_LARGE;
     }
-    const int64_t blocks = fill_blk_start(B);
-    if (blocks < 0) return CWN_ERR_TOO_LARGE;
+    const int64_t blocks = fill.close(n);
     if (blocks == 0) return CWN_OK;
     hipStream_t stream = (hipStream_t)stream_;
     const dim3 grid((unsigned)blocks), block(kThreads);

@@ -31,6 +31,7 @@
 #include "../../include/cwn_hip.h"
 #include "cwn_act.h"
 #include "cwn_check.h"
+#include "cwn_group.h"
 
 namespace {
 
@@ -98,10 +99,7 @@ template <class real>
 __global__ __launch_bounds__(kThreads) void embed_pool_kernel(PoolBatch<real> B) {
     __shared__ real ws[kCols * kPitch];
     __shared__ real part[kThreads];
-    int di = 0;
-#pragma unroll
-    for (int i = 1; i < CWN_MAX_DESCS; ++i)
-        if (i < B.n && (int)blockIdx.x >= B.blk_start[i]) di = i;
+    const int di = cwn::group_of<CWN_MAX_DESCS>(B.blk_start, B.n, (int)blockIdx.x);
     const typename PoolDescOf<real>::type D = B.d[di];      // by value (cwn_aggregate_act.hip)
     const int blk = blockIdx.x - B.blk_start[di];
     const int nhb = (D.H + kCols - 1) / kCols;
@@ -151,7 +149,7 @@ int launch_pool(const typename PoolDescOf<real>::type* descs, int n, cwn_stream_
     if (n < 0 || n > CWN_MAX_DESCS || (n > 0 && descs == nullptr)) return CWN_ERR_BAD_ARG;
     PoolBatch<real> B{};
     B.n = n;
-    int64_t blocks = 0;
+    cwn::BlockFill fill(B.blk_start);
     for (int i = 0; i < n; ++i) {
         const Desc& D = descs[i];
         if (D.K < 1 || D.K > CWN_EMBED_POOL_MAX_K || D.H < 1 || D.H > CWN_AGNOSTIC_MAX_WIDTH) return CWN_ERR_BAD_ARG;
@@ -164,11 +162,9 @@ int launch_pool(const typename PoolDescOf<real>::type* descs, int n, cwn_stream_
             if (!aligned_to(p, sizeof(real))) return CWN_ERR_ALIGN;
         if (!aligned_to(D.cell_ptr, sizeof(int64_t))) return CWN_ERR_ALIGN;
         B.d[i] = D;
-        B.blk_start[i] = (int32_t)blocks;
-        blocks += D.C * ((D.H + kCols - 1) / kCols);
-        if (blocks >= INT32_MAX) return CWN_ERR_TOO_LARGE;
+        if (!fill.push(i, D.C * ((D.H + kCols - 1) / kCols))) return CWN_ERR_TOO_LARGE;
     }
-    for (int i = n; i <= CWN_MAX_DESCS; ++i) B.blk_start[i] = (int32_t)blocks;
+    const int64_t blocks = fill.close(n);
     if (blocks == 0) return CWN_OK;
     embed_pool_kernel<real><<<dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream_>>>(B);
     return hipGetLastError() == hipSuccess ? CWN_OK : CWN_ERR_LAUNCH;

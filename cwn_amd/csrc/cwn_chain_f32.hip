@@ -31,6 +31,7 @@
 #include "../../include/cwn_hip.h"
 #include "cwn_act.h"
 #include "cwn_check.h"
+#include "cwn_group.h"
 
 namespace {
 
@@ -144,17 +145,10 @@ __global__ __launch_bounds__(kThreads) void update_chain_f32_kernel(ChainBatch B
     __shared__ __attribute__((aligned(16))) float pa[kTM * kLdp];       // in_up, then u
     __shared__ __attribute__((aligned(16))) float pb[kTM * kLdp];       // in_b, then b
     __shared__ __attribute__((aligned(16))) float ph[kTM * kLdp];       // the hidden activation of the branch at work
-    int di = 0;
-#pragma unroll
-    for (int i = 1; i < CWN_CHAIN_F32_MAX_DIMS; ++i)
-        if (i < B.n && (int)blockIdx.x >= B.blk_start[i]) di = i;
+    const int di = cwn::group_of<CWN_CHAIN_F32_MAX_DIMS>(B.blk_start, B.n, (int)blockIdx.x);
     const cwn_chain_desc_f32 D = B.d[di];                // by value (a reference puts the batch struct in scratch)
     const int64_t row0 = (int64_t)((int)blockIdx.x - B.blk_start[di]) * kTM;
-    int64_t n = D.n;                                     // the capacity; with m_dev the rows that exist, clamped to it
-    if (D.m_dev != nullptr) {
-        const int64_t m = *D.m_dev;
-        n = m < 0 ? 0 : (m < n ? m : n);
-    }
+    const int64_t n = cwn::rows_clamped(D.m_dev, D.n);   // (D.n: the capacity)
     if (row0 >= n) return;                               // (uniform: before any barrier)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, g = lane >> 4;
     const int F = D.F, H = D.H, act = D.act;
@@ -217,7 +211,7 @@ extern "C" int cwn_update_chain_f32(const cwn_chain_desc_f32* descs, int n_dims,
     if (descs == nullptr || n_dims < 1 || n_dims > CWN_CHAIN_F32_MAX_DIMS) return CWN_ERR_BAD_ARG;
     ChainBatch B{};
     B.n = n_dims;
-    int64_t blocks = 0;
+    cwn::BlockFill fill(B.blk_start);
     for (int i = 0; i < n_dims; ++i) {
         const cwn_chain_desc_f32& D = descs[i];
         if (D.n < 0 || D.F < 1 || D.F > kMaxWidth || D.H < 1 || D.H > kMaxWidth || !known_act(D.act)) return CWN_ERR_BAD_ARG;
@@ -231,11 +225,9 @@ extern "C" int cwn_update_chain_f32(const cwn_chain_desc_f32* descs, int n_dims,
                 if (!al4(D.W[s]) || !al4(D.bias[s]) || !al4(D.scale[s]) || !al4(D.shift[s])) return CWN_ERR_ALIGN;
         }
         B.d[i] = D;
-        B.blk_start[i] = (int32_t)blocks;
-        blocks += (D.n + kTM - 1) / kTM;
-        if (blocks >= INT32_MAX) return CWN_ERR_TOO_LARGE;
+        if (!fill.push(i, (D.n + kTM - 1) / kTM)) return CWN_ERR_TOO_LARGE;
     }
-    for (int i = n_dims; i <= CWN_CHAIN_F32_MAX_DIMS; ++i) B.blk_start[i] = (int32_t)blocks;
+    const int64_t blocks = fill.close(n_dims);
     if (blocks == 0) return CWN_OK;
     update_chain_f32_kernel<<<dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream_>>>(B);
     return hipGetLastError() == hipSuccess ? CWN_OK : CWN_ERR_LAUNCH;

@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include "../../include/cwn_hip.h"
+#include "cwn_group.h"
 
 namespace {
 
@@ -40,30 +41,15 @@ struct CsrBatch {
     int dbg;   // timing experiments (CWN_CSR_DBG): 1 no rowptr stores, 2 no long-row notes, 4 no loads
 };
 
-// entries that exist: the host count, or -- a static buffer -- what the device says, never more than the capacity
-__device__ __forceinline__ int64_t live_entries(const cwn_csr_desc& D) {
-    if (D.e_dev == nullptr) return D.n_entries;
-    const int64_t e = *D.e_dev;
-    return e < 0 ? 0 : (e < D.n_entries ? e : D.n_entries);
-}
-
-__device__ __forceinline__ int find_desc(const int64_t* start, int n, int64_t b) {
-    int d = 0;
-#pragma unroll
-    for (int i = 1; i < CWN_CSR_MAX_DESCS; ++i)
-        if (i < n && b >= start[i]) d = i;
-    return d;
-}
-
 // One atomic per DISTINCT key per wavefront: the lanes that hold the same key elect a leader
 // (lowest lane), which adds the group's size; members take consecutive slots after the returned
 // base.  A hub row (REDDIT-like: one key in half of the lanes of many consecutive waves) then
 // costs 1/32 of the same-address atomics, which is what the kernel's time was going to.
 __global__ __launch_bounds__(kThreads) void count_kernel(CsrBatch B, int32_t* err) {
-    const int di = find_desc(B.blk_start, B.n, blockIdx.x);
+    const int di = cwn::group_of<CWN_CSR_MAX_DESCS>(B.blk_start, B.n, (int64_t)blockIdx.x);
     const cwn_csr_desc& D = B.d[di];
     const int64_t e = (int64_t)(blockIdx.x - B.blk_start[di]) * kThreads + threadIdx.x;
-    const bool in = e < live_entries(D);
+    const bool in = e < cwn::rows_clamped(D.e_dev, D.n_entries);
     int64_t k = -1;
     int bad = 0;
     if (in) {
@@ -251,7 +237,7 @@ __global__ __launch_bounds__(kScanThreads) void scan_single_kernel(CsrBatch B) {
 // ---- exclusive scan, multi block (tile sums -> scan of sums -> tile scan) ------------------
 __global__ __launch_bounds__(kScanThreads) void tile_sum_kernel(CsrBatch B) {
     __shared__ int lds[32];
-    const int di = find_desc(B.tile_start, B.n, blockIdx.x);
+    const int di = cwn::group_of<CWN_CSR_MAX_DESCS>(B.tile_start, B.n, (int64_t)blockIdx.x);
     const int64_t tile = blockIdx.x - B.tile_start[di];
     const int32_t* cnt = B.cnt[di];
     const int64_t n = B.d[di].n_dst;
@@ -279,7 +265,7 @@ __global__ __launch_bounds__(kScanThreads) void tile_scan_kernel(CsrBatch B) {
     __shared__ int lds[32];
     using Chunk = ScanChunk<kScanTile / kScanThreads>;
     __shared__ int xpose[Chunk::kLdsInts];
-    const int di = find_desc(B.tile_start, B.n, blockIdx.x);
+    const int di = cwn::group_of<CWN_CSR_MAX_DESCS>(B.tile_start, B.n, (int64_t)blockIdx.x);
     const int64_t tile = blockIdx.x - B.tile_start[di];
     const int64_t tiles = B.tile_start[di + 1] - B.tile_start[di];
     Chunk c;
@@ -293,10 +279,10 @@ __global__ __launch_bounds__(kScanThreads) void tile_scan_kernel(CsrBatch B) {
 }
 
 __global__ __launch_bounds__(kThreads) void place_kernel(CsrBatch B) {
-    const int di = find_desc(B.blk_start, B.n, blockIdx.x);
+    const int di = cwn::group_of<CWN_CSR_MAX_DESCS>(B.blk_start, B.n, (int64_t)blockIdx.x);
     const cwn_csr_desc& D = B.d[di];
     const int64_t e = (int64_t)(blockIdx.x - B.blk_start[di]) * kThreads + threadIdx.x;
-    if (e >= live_entries(D)) return;
+    if (e >= cwn::rows_clamped(D.e_dev, D.n_entries)) return;
     const int s = B.slot[di][e];
     if (s < 0) return;
     const int64_t r = D.key[e];
@@ -306,7 +292,7 @@ __global__ __launch_bounds__(kThreads) void place_kernel(CsrBatch B) {
 }
 
 __global__ __launch_bounds__(kThreads) void emit_kernel(CsrBatch B) {
-    const int di = find_desc(B.blk_start, B.n, blockIdx.x);
+    const int di = cwn::group_of<CWN_CSR_MAX_DESCS>(B.blk_start, B.n, (int64_t)blockIdx.x);
     const cwn_csr_desc& D = B.d[di];
     const int64_t p = (int64_t)(blockIdx.x - B.blk_start[di]) * kThreads + threadIdx.x;
     // valid positions are [0, rowptr[n_dst]); dropped (out-of-range) entries shorten the tail
@@ -381,7 +367,8 @@ __global__ __launch_bounds__(kSmallThreads) void csr_small_kernel(SmallBatch B, 
     const cwn_csr_desc& D = B.d[di];
     const int parts = B.part_start[di + 1] - B.part_start[di];
     const int part = blockIdx.x - B.part_start[di];
-    const int n = (int)D.n_dst, Ecap = (int)D.n_entries, E = (int)live_entries(D);      // (LDS is laid out for the capacity)
+    const int n = (int)D.n_dst, Ecap = (int)D.n_entries;                                // (LDS is laid out for the capacity)
+    const int E = (int)cwn::rows_clamped(D.e_dev, D.n_entries);
     const int rows_per = (n + parts - 1) / parts;
     const int lo = min(part * rows_per, n), hi = min(lo + rows_per, n);
     const int rows = hi - lo;
@@ -601,7 +588,8 @@ extern "C" int cwn_csr_build(const cwn_csr_desc* descs, int n, void* workspace, 
     static const int dbg = getenv("CWN_CSR_DBG") ? atoi(getenv("CWN_CSR_DBG")) : 0;
     B.dbg = dbg;
     char* ws = (char*)workspace;
-    int64_t blocks = 0, tiles = 0;
+    cwn::BlockFill fill(B.blk_start);
+    int64_t tiles = 0;
     for (int i = 0; i < n; ++i) {
         B.d[i] = descs[i];
         B.cnt[i] = (int32_t*)(ws + L.cnt_off[i]);
@@ -609,15 +597,12 @@ extern "C" int cwn_csr_build(const cwn_csr_desc* descs, int n, void* workspace, 
         B.tmp[i] = (int32_t*)(ws + L.tmp_off[i]);
         B.rows[i] = (int32_t*)(ws + L.rows_off[i]);
         B.tile_sums[i] = (int32_t*)(ws + L.tiles_off[i]);
-        B.blk_start[i] = blocks;
+        fill.push(i, (descs[i].n_entries + kThreads - 1) / kThreads);      // (the total is checked once, below)
         B.tile_start[i] = tiles;
-        blocks += (descs[i].n_entries + kThreads - 1) / kThreads;
         tiles += descs[i].n_dst > 0 ? (descs[i].n_dst + kScanTile - 1) / kScanTile : 1;   // >= 1: rowptr[0]
     }
-    for (int i = n; i <= CWN_CSR_MAX_DESCS; ++i) {
-        B.blk_start[i] = blocks;
-        B.tile_start[i] = tiles;
-    }
+    const int64_t blocks = fill.close(n);
+    for (int i = n; i <= CWN_CSR_MAX_DESCS; ++i) B.tile_start[i] = tiles;   // (the scan kernels' own prefix, >= 1 tile each: kept here)
     if (blocks >= INT32_MAX) return CWN_ERR_TOO_LARGE;
 
     if (((uintptr_t)ws & 15u) != 0) return CWN_ERR_ALIGN;
@@ -652,11 +637,7 @@ __global__ __launch_bounds__(1024) void long_rows_kernel(LongBatch B) {
     const cwn_long_rows_desc D = B.d[blockIdx.x];          // (a small struct, a launch-constant index per workgroup)
     if (threadIdx.x == 0) count = 0;
     __syncthreads();
-    int64_t n = D.n_rows;
-    if (D.m_dev != nullptr) {
-        const int64_t m = *D.m_dev;
-        n = m < 0 ? 0 : (m < n ? m : n);
-    }
+    const int64_t n = cwn::rows_clamped(D.m_dev, D.n_rows);
     for (int64_t r = threadIdx.x; r < n; r += blockDim.x) {
         if (D.rowptr[r + 1] - D.rowptr[r] > CWN_LONG_ROW) {
             const int p = atomicAdd(&count, 1);

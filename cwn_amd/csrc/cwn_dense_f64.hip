@@ -24,6 +24,7 @@
 #include "../../include/cwn_hip.h"
 #include "cwn_act.h"
 #include "cwn_check.h"
+#include "cwn_group.h"
 
 namespace {
 
@@ -109,10 +110,7 @@ __device__ __forceinline__ void linear_tile(const cwn_linear_desc_f64& D, int64_
 __global__ __launch_bounds__(kThreads) void linear_many_f64_kernel(LinearBatch B) {
     __shared__ double xs[kRows * kLinW];
     __shared__ double ws[kLinKc * kLinWld];
-    int di = 0;
-#pragma unroll
-    for (int i = 1; i < CWN_LINEAR_F64_MAX_DESCS; ++i)
-        if (i < B.n && (int)blockIdx.x >= B.blk_start[i]) di = i;
+    const int di = cwn::group_of<CWN_LINEAR_F64_MAX_DESCS>(B.blk_start, B.n, (int)blockIdx.x);
     const cwn_linear_desc_f64 D = B.d[di];               // by value (a reference puts the batch struct in scratch)
     const int64_t row0 = (int64_t)((int)blockIdx.x - B.blk_start[di]) * kRows;
     if (D.N <= 16) linear_tile<16>(D, row0, xs, ws);
@@ -180,10 +178,7 @@ __global__ __launch_bounds__(kThreads) void update_chain_f64_kernel(ChainBatch B
     __shared__ double a[kRows * kChainW];
     __shared__ double b[kRows * kChainW];
     __shared__ double ws[kChainW * kChainWld];
-    int di = 0;
-#pragma unroll
-    for (int i = 1; i < CWN_CHAIN_F64_MAX_DIMS; ++i)
-        if (i < B.n && (int)blockIdx.x >= B.blk_start[i]) di = i;
+    const int di = cwn::group_of<CWN_CHAIN_F64_MAX_DIMS>(B.blk_start, B.n, (int)blockIdx.x);
     const cwn_chain_desc_f64 D = B.d[di];
     const int64_t row0 = (int64_t)((int)blockIdx.x - B.blk_start[di]) * kRows;
     if (D.H <= 16) chain_tile<16>(D, row0, a, b, ws);
@@ -197,7 +192,7 @@ extern "C" int cwn_linear_many_f64(const cwn_linear_desc_f64* descs, int n, cwn_
     if (descs == nullptr || n < 1 || n > CWN_LINEAR_F64_MAX_DESCS) return CWN_ERR_BAD_ARG;
     LinearBatch B{};
     B.n = n;
-    int64_t blocks = 0;
+    cwn::BlockFill fill(B.blk_start);
     for (int i = 0; i < n; ++i) {
         const cwn_linear_desc_f64& D = descs[i];
         if (D.M < 0 || D.K < 1 || D.K > CWN_LINEAR_F64_MAX_WIDTH || D.N < 1 || D.N > CWN_LINEAR_F64_MAX_WIDTH || !known_act(D.act))
@@ -208,11 +203,9 @@ extern "C" int cwn_linear_many_f64(const cwn_linear_desc_f64* descs, int n, cwn_
             if (!al8(D.X) || !al8(D.W) || !al8(D.Y) || !al8(D.bias)) return CWN_ERR_ALIGN;
         }
         B.d[i] = D;
-        B.blk_start[i] = (int32_t)blocks;
-        blocks += (D.M + kRows - 1) / kRows;
-        if (blocks >= INT32_MAX) return CWN_ERR_TOO_LARGE;
+        if (!fill.push(i, (D.M + kRows - 1) / kRows)) return CWN_ERR_TOO_LARGE;
     }
-    for (int i = n; i <= CWN_LINEAR_F64_MAX_DESCS; ++i) B.blk_start[i] = (int32_t)blocks;
+    const int64_t blocks = fill.close(n);
     if (blocks == 0) return CWN_OK;
     linear_many_f64_kernel<<<dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream_>>>(B);
     return hipGetLastError() == hipSuccess ? CWN_OK : CWN_ERR_LAUNCH;
@@ -222,7 +215,7 @@ extern "C" int cwn_update_chain_f64(const cwn_chain_desc_f64* descs, int n_dims,
     if (descs == nullptr || n_dims < 1 || n_dims > CWN_CHAIN_F64_MAX_DIMS) return CWN_ERR_BAD_ARG;
     ChainBatch B{};
     B.n = n_dims;
-    int64_t blocks = 0;
+    cwn::BlockFill fill(B.blk_start);
     for (int i = 0; i < n_dims; ++i) {
         const cwn_chain_desc_f64& D = descs[i];
         if (D.n < 0 || D.F < 1 || D.F > CWN_CHAIN_F64_MAX_WIDTH || D.H < 1 || D.H > CWN_CHAIN_F64_MAX_WIDTH || !known_act(D.act))
@@ -239,11 +232,9 @@ extern "C" int cwn_update_chain_f64(const cwn_chain_desc_f64* descs, int n_dims,
             }
         }
         B.d[i] = D;
-        B.blk_start[i] = (int32_t)blocks;
-        blocks += (D.n + kRows - 1) / kRows;
-        if (blocks >= INT32_MAX) return CWN_ERR_TOO_LARGE;
+        if (!fill.push(i, (D.n + kRows - 1) / kRows)) return CWN_ERR_TOO_LARGE;
     }
-    for (int i = n_dims; i <= CWN_CHAIN_F64_MAX_DIMS; ++i) B.blk_start[i] = (int32_t)blocks;
+    const int64_t blocks = fill.close(n_dims);
     if (blocks == 0) return CWN_OK;
     update_chain_f64_kernel<<<dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream_>>>(B);
     return hipGetLastError() == hipSuccess ? CWN_OK : CWN_ERR_LAUNCH;

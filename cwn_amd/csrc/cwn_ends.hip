@@ -163,7 +163,7 @@ __global__ __launch_bounds__(256) void embed_front_kernel(FrontArgs A) {
     // (the index clamps of the reductions keep the capacities: they are there so that no address leaves the buffers)
     const int64_t cap0 = A.n0, cap1 = A.n1;
     int64_t live0 = A.n0, live1 = A.n1, live2 = A.n2;
-    if (A.n_dev != nullptr) {
+    if (A.n_dev != nullptr) {          // (open-coded cwn::rows_capped: one null test covers the triple of counts)
         const int64_t d0 = A.n_dev[0], d1 = A.n_dev[1], d2 = A.n_dev[2];
         live0 = d0 < live0 ? d0 : live0;
         live1 = d1 < live1 ? d1 : live1;
@@ -231,7 +231,7 @@ __device__ __forceinline__ float4 embed_cols(const float* __restrict__ W, const 
 __global__ __launch_bounds__(256) void embed_pair_kernel(FrontArgs A) {
     const int64_t cap0 = A.n0, cap1 = A.has_te ? A.n1 : 0;
     int64_t live0 = cap0, live1 = cap1;
-    if (A.n_dev != nullptr) {
+    if (A.n_dev != nullptr) {          // (open-coded cwn::rows_capped: one null test covers the triple of counts)
         const int64_t d0 = A.n_dev[0], d1 = A.n_dev[1];
         live0 = d0 < live0 ? d0 : live0;
         live1 = d1 < live1 ? d1 : live1;
@@ -255,7 +255,7 @@ __global__ __launch_bounds__(256) void embed_pair_kernel(FrontArgs A) {
 __global__ __launch_bounds__(256) void front_reduce_kernel(FrontArgs A) {
     const int64_t cap1 = A.has_te ? 0 : A.n1;          // edge rows of this launch
     int64_t live0 = A.n0, live1 = A.n1, live2 = A.n2;
-    if (A.n_dev != nullptr) {
+    if (A.n_dev != nullptr) {          // (open-coded cwn::rows_capped: one null test covers the triple of counts)
         const int64_t d0 = A.n_dev[0], d1 = A.n_dev[1], d2 = A.n_dev[2];
         live0 = d0 < live0 ? d0 : live0;
         live1 = d1 < live1 ? d1 : live1;

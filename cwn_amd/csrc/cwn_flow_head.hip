@@ -43,6 +43,7 @@
 #include "../../include/cwn_hip.h"
 #include "cwn_act.h"
 #include "cwn_check.h"
+#include "cwn_group.h"
 
 namespace {
 
@@ -70,9 +71,8 @@ __device__ __forceinline__ void cochain_rows(const int64_t* __restrict__ ptr, in
 __device__ __forceinline__ void live_counts(const int64_t* __restrict__ ptr, const int64_t* __restrict__ n_dev,
                                             const int64_t* __restrict__ c_dev, int64_t& N, int64_t& C) {
     if (c_dev == nullptr) return;
-    const int64_t c = *c_dev;
-    C = c < 0 ? 0 : (c > C ? C : c);
-    N = clamp_row(n_dev != nullptr ? *n_dev : ptr[C], N);
+    C = cwn::rows_clamped(c_dev, C);
+    N = clamp_row(n_dev != nullptr ? *n_dev : ptr[C], N);      // (open-coded: without n_dev the total is ptr's, not a count of its own)
 }
 
 // The cochain that owns slot b: the largest c < C with first(c) <= b, by a 64-ary search (every lane of the wave takes part).

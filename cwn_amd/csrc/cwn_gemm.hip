@@ -36,6 +36,7 @@
 #include "cwn_mem.h"
 #include "cwn_check.h"
 #include "cwn_act.h"
+#include "cwn_group.h"
 
 namespace {
 
@@ -277,6 +278,7 @@ __global__ __launch_bounds__(kThreads, (KP <= 128 && RT == 2 && !(CWN_GEMM_NOSPI
     constexpr int BM = 16 * RT * (4 / WN);   // rows per tile: WN waves side by side along N, 4/WN along M
     constexpr int BN = 32 * WN;         // columns per tile
     extern __shared__ __attribute__((aligned(16))) float smem[];   // two [BM][KP] X buffers
+    // (cwn::group_of, written out: through the helper this kernel's register allocation and schedule come out differently)
     int di = 0;
 #pragma unroll
     for (int i = 1; i < CWN_MAX_DESCS; ++i)
@@ -288,7 +290,7 @@ __global__ __launch_bounds__(kThreads, (KP <= 128 && RT == 2 && !(CWN_GEMM_NOSPI
     int64_t Mst = D.M;               // rows that are STORED (D.M bounds the addresses of the loads)
     if (D.m_dev != nullptr) {        // (uniform) a static batch: the row tiles below the rows that exist -- a PREFIX of the tile numbers
         const int64_t mv = *D.m_dev;
-        const int64_t live = (mv < 0 ? 0 : (mv < D.M ? mv : D.M));
+        const int64_t live = (mv < 0 ? 0 : (mv < D.M ? mv : D.M));      // (cwn::rows_clamped, written out: as for the search above)
         const int64_t t = (live + BM - 1) / BM * tiles_n;
         tiles = t < tiles ? (int)t : tiles;
         Mst = live;                  // the tile the count ends in stores its live rows only: the rows behind are never written
@@ -753,7 +755,7 @@ extern "C" int cwn_gemm_f32(const cwn_gemm_desc* descs, int n, cwn_stream_t stre
     // (K <= 128: measured on the 650 k-row shape -- 512 blocks 363 us, 768: 331, 1024: 318, 2048: 312,
     //  4096: 302, 8192: 324, one block per tile: 371; two are resident per CU, the queue behind them
     //  keeps every CU busy to the end while W is still re-staged only 16 times per CU)
-    int64_t blocks = 0;
+    cwn::BlockFill fill(B.blk_start);
     for (int i = 0; i < n; ++i) {
         int64_t nb = B.n_tiles[i];
         if (total_tiles > budget) {
@@ -761,10 +763,9 @@ extern "C" int cwn_gemm_f32(const cwn_gemm_desc* descs, int n, cwn_stream_t stre
             if (nb < 1 && B.n_tiles[i] > 0) nb = 1;
             if (nb > B.n_tiles[i]) nb = B.n_tiles[i];
         }
-        B.blk_start[i] = (int32_t)blocks;
-        blocks += nb;
+        fill.push(i, nb);        // (budgeted counts: never near the grid bound)
     }
-    for (int i = n; i <= CWN_MAX_DESCS; ++i) B.blk_start[i] = (int32_t)blocks;
+    const int64_t blocks = fill.close(n);
     // w_trans is a property of the launch (all descriptors or none), and excludes the prologue
     const bool wt = descs[0].w_trans != 0;
     bool fast = true, pro = false;

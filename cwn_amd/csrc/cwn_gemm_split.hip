@@ -30,6 +30,7 @@
 #include "cwn_mem.h"
 #include "cwn_check.h"
 #include "cwn_act.h"
+#include "cwn_group.h"
 
 namespace {
 
@@ -55,18 +56,14 @@ struct SplitBatch {
 template <bool MULTI>
 __global__ __launch_bounds__(kThreads, 2) void gemm_split_kernel(SplitBatch B) {
     __shared__ __attribute__((aligned(16))) uint16_t xs[3][TM][kRowStride];
-    int di = 0;
-#pragma unroll
-    for (int i = 1; i < CWN_MAX_DESCS; ++i)
-        if (i < B.n && (int)blockIdx.x >= B.blk_start[i]) di = i;
+    const int di = cwn::group_of<CWN_MAX_DESCS>(B.blk_start, B.n, (int)blockIdx.x);
     const cwn_gemm_desc D = B.d[di];         // by value (see cwn_aggregate.hip)
     const int blk = blockIdx.x - B.blk_start[di];
     const int nblk = B.blk_start[di + 1] - B.blk_start[di];
     int tiles = B.n_tiles[di];
     int64_t Mst = D.M;                       // rows that are STORED (D.M bounds the addresses of the loads)
     if (D.m_dev != nullptr) {                // (uniform) a static batch: the 64-row tiles below the rows that exist
-        const int64_t mv = *D.m_dev;
-        const int64_t live = (mv < 0 ? 0 : (mv < D.M ? mv : D.M));
+        const int64_t live = cwn::rows_clamped(D.m_dev, D.M);
         const int64_t t = (live + TM - 1) / TM;
         tiles = t < tiles ? (int)t : tiles;
         Mst = live;                          // the tile the count ends in stores its live rows only
@@ -249,17 +246,16 @@ int cwn_gemm_split_launch(const cwn_gemm_desc* descs, int n, hipStream_t stream)
     // four GEMMs of a batch-8192 layer, and the two workgroups that had to wait for a free slot
     // walked their 19 tiles after everyone else had finished (205 us instead of ~140)
     const int64_t cap = kMaxBlocks - n;
-    int64_t blocks = 0;
+    cwn::BlockFill fill(B.blk_start);
     for (int i = 0; i < n; ++i) {
         int64_t nb = B.n_tiles[i];
         if (total > cap) {
             nb = nb * cap / total;
             if (nb < 1 && B.n_tiles[i] > 0) nb = 1;
         }
-        B.blk_start[i] = (int32_t)blocks;
-        blocks += nb;
+        fill.push(i, nb);        // (at most kMaxBlocks in all)
     }
-    for (int i = n; i <= CWN_MAX_DESCS; ++i) B.blk_start[i] = (int32_t)blocks;
+    const int64_t blocks = fill.close(n);
     if (total > blocks) gemm_split_kernel<true><<<dim3((unsigned)blocks), dim3(kThreads), 0, stream>>>(B);
     else gemm_split_kernel<false><<<dim3((unsigned)blocks), dim3(kThreads), 0, stream>>>(B);
     return hipGetLastError() == hipSuccess ? CWN_OK : CWN_ERR_LAUNCH;

@@ -26,6 +26,7 @@
 #include "cwn_split.h"
 #include "cwn_check.h"
 #include "cwn_act.h"
+#include "cwn_group.h"
 
 namespace {
 
@@ -180,6 +181,7 @@ template <bool FAST>
 __global__ __launch_bounds__(kThreads, 4) void gemm_tn_kernel(TnBatch B) {
     __shared__ __attribute__((aligned(16))) float zt[kChunk * kLd];
     __shared__ __attribute__((aligned(16))) float xt[kChunk * kLd];
+    // (cwn::group_of, written out: through the helper this kernel's register allocation and schedule come out differently)
     int di = 0;
 #pragma unroll
     for (int i = 1; i < CWN_GEMM_TN_MAX_DESCS; ++i)
@@ -194,7 +196,7 @@ __global__ __launch_bounds__(kThreads, 4) void gemm_tn_kernel(TnBatch B) {
     // rows of the reduction that exist (include/cwn_hip.h, "device-side row counts"): D.M is then the capacity -- it shaped the
     // grid and bounds the addresses of the loads, which do not wait for this one
     const int64_t Mcap = D.M;
-    const int64_t M = D.m_dev != nullptr ? (*D.m_dev < Mcap ? *D.m_dev : Mcap) : Mcap;
+    const int64_t M = cwn::rows_capped(D.m_dev, Mcap);
     const int64_t band_rows = dev_band_rows(B.band_rows_of[di], B.bands[di], D.m_dev != nullptr && B.ws[di] == nullptr, M, kChunk);
     const int64_t row_lo = (int64_t)band * band_rows;
     const int64_t cap_hi = row_lo + band_rows < Mcap ? row_lo + band_rows : Mcap;
@@ -387,10 +389,7 @@ __global__ __launch_bounds__(kThreads2, CWN_TN_WGS) void gemm_tn_split_kernel(Tn
     // chunk c + 1 overwrites)
     __shared__ __attribute__((aligned(16))) uint16_t zp[2][3 * kPlane];
     __shared__ __attribute__((aligned(16))) uint16_t xp[2][3 * kPlane];
-    int di = 0;
-#pragma unroll
-    for (int i = 1; i < CWN_GEMM_TN_MAX_DESCS; ++i)
-        if (i < B.n && (int)blockIdx.x >= B.blk_start[i]) di = i;
+    const int di = cwn::group_of<CWN_GEMM_TN_MAX_DESCS>(B.blk_start, B.n, (int)blockIdx.x);
     const cwn_gemm_tn_desc& D = B.d[di];
     const int tn = B.tiles_n[di], tk = B.tiles_k[di];
     int b = blockIdx.x - B.blk_start[di];
@@ -401,7 +400,7 @@ __global__ __launch_bounds__(kThreads2, CWN_TN_WGS) void gemm_tn_split_kernel(Tn
     const int64_t Mcap = D.M;
     // (a static batch: the bands are cut from the batch's OWN rows -- dev_band_rows -- so this launch's first loads wait for the
     //  row count; a prepared batch: the host's cut, the count not waited for)
-    const int64_t M = D.m_dev != nullptr ? (*D.m_dev < Mcap ? *D.m_dev : Mcap) : Mcap;
+    const int64_t M = cwn::rows_capped(D.m_dev, Mcap);
     const int64_t band_rows = dev_band_rows(B.band_rows_of[di], B.bands[di], D.m_dev != nullptr && B.ws[di] == nullptr, M, kChunk2);
     const int64_t row_lo = (int64_t)band * band_rows;
     const int64_t cap_hi = row_lo + band_rows < Mcap ? row_lo + band_rows : Mcap;
@@ -595,7 +594,6 @@ extern "C" int cwn_gemm_tn_f32(const cwn_gemm_tn_desc* descs, int n, void* works
     if (workspace != nullptr && ws_bytes < cwn_gemm_tn_workspace_bytes(descs, n)) return CWN_ERR_WORKSPACE;
     TnBatch B{};
     B.n = n;
-    int64_t blocks = 0;
     bool fast = true;
     for (int i = 0; i < n; ++i) {
         const cwn_gemm_tn_desc& D = descs[i];
@@ -635,7 +633,7 @@ extern "C" int cwn_gemm_tn_f32(const cwn_gemm_tn_desc* descs, int n, void* works
     // rows r .. r + kBandRows - 1 are one partial sum whatever M is, and the bands past the rows that exist add zeros.  A
     // captured step over capacity-sized buffers (m_dev) then gives the bits of the eager step on the batch's own rows.
     const bool ordered = workspace != nullptr;
-    auto rows_of = [&](int i, int cand) {
+    auto band_len = [&](int i, int cand) {
         const int64_t nb = bands_of(i, cand);
         if (!split || nb == 0 || ordered) return (int64_t)cand;
         return ((descs[i].M + nb - 1) / nb + chunk - 1) / chunk * chunk;
@@ -649,7 +647,7 @@ extern "C" int cwn_gemm_tn_f32(const cwn_gemm_tn_desc* descs, int n, void* works
             int64_t nb = 0, longest = 0;
             for (int i = 0; i < n; ++i) {
                 nb += bands_of(i, cand) * B.tiles_n[i] * B.tiles_k[i];
-                longest = rows_of(i, cand) > longest ? rows_of(i, cand) : longest;
+                longest = band_len(i, cand) > longest ? band_len(i, cand) : longest;
             }
             const double cost = (double)((nb + kResident - 1) / kResident) * (fixed + per_chunk * (double)longest / (double)kChunk);
             if (cand == kBandRows || cost < best || (band_env == cand)) {
@@ -658,16 +656,14 @@ extern "C" int cwn_gemm_tn_f32(const cwn_gemm_tn_desc* descs, int n, void* works
             }
         }
     }
-    blocks = 0;
+    cwn::BlockFill fill(B.blk_start);
     for (int i = 0; i < n; ++i) {
         const int64_t bands = bands_of(i, band_rows);
         B.bands[i] = (int32_t)bands;
-        B.band_rows_of[i] = (int32_t)rows_of(i, band_rows);
-        B.blk_start[i] = (int32_t)blocks;
-        blocks += bands * B.tiles_n[i] * B.tiles_k[i];
-        if (blocks >= INT32_MAX) return CWN_ERR_TOO_LARGE;
+        B.band_rows_of[i] = (int32_t)band_len(i, band_rows);
+        if (!fill.push(i, bands * B.tiles_n[i] * B.tiles_k[i])) return CWN_ERR_TOO_LARGE;
     }
-    for (int i = n; i <= CWN_GEMM_TN_MAX_DESCS; ++i) B.blk_start[i] = (int32_t)blocks;
+    const int64_t blocks = fill.close(n);
     if (blocks == 0) return CWN_OK;
     static const int dbg = getenv("CWN_TN_DBG") ? atoi(getenv("CWN_TN_DBG")) : 0;
     B.dbg = dbg;

@@ -20,6 +20,7 @@
 #include "../../include/cwn_hip.h"
 #include "cwn_check.h"
 #include "cwn_act.h"
+#include "cwn_group.h"
 
 namespace {
 
@@ -36,14 +37,6 @@ struct LnBatch {
     int32_t vec[CWN_MAX_NORM_DESCS];              // 16-byte form
     int32_t n;
 };
-
-__device__ __forceinline__ int find_desc(const int32_t* start, int n, int b) {
-    int d = 0;
-#pragma unroll
-    for (int i = 1; i < CWN_MAX_NORM_DESCS; ++i)
-        if (i < n && b >= start[i]) d = i;
-    return d;
-}
 
 // A lane holds 4 * C elements of a row of up to 256 * C columns.  VEC: element e is column 4 * (lane + 64 * (e / 4)) + e % 4
 // (float4 number lane + 64 j: a wave's load is 1 KiB of consecutive bytes); otherwise column lane + 64 * e.
@@ -93,13 +86,6 @@ __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
     return v;
-}
-
-// rows that exist: the device-side count of a static batch, never beyond the capacity the addresses are bounded by
-__device__ __forceinline__ int64_t rows_of(const cwn_ln_desc& D) {
-    if (D.m_dev == nullptr) return D.M;
-    const int64_t m = *D.m_dev;
-    return m < D.M ? m : D.M;
 }
 
 // ---- forward ------------------------------------------------------------------------------------------------------------
@@ -159,10 +145,10 @@ __device__ __forceinline__ void fwd_band(const cwn_ln_desc& D, int64_t row0, int
 }
 
 __global__ __launch_bounds__(kThreads) void layernorm_act_kernel(LnBatch B) {
-    const int di = find_desc(B.blk_start, B.n, blockIdx.x);
+    const int di = cwn::group_of<CWN_MAX_NORM_DESCS>(B.blk_start, B.n, (int)blockIdx.x);
     const cwn_ln_desc& D = B.d[di];
     const int64_t row0 = (int64_t)((int)blockIdx.x - B.blk_start[di]) * kBand;
-    const int64_t Mv = rows_of(D);
+    const int64_t Mv = cwn::rows_capped(D.m_dev, D.M);
     if (row0 >= Mv) return;
     const int C = (D.N + 255) >> 8;
     if (B.vec[di]) {
@@ -269,11 +255,11 @@ __device__ __forceinline__ void bwd_band(const cwn_ln_desc& D, int64_t row0, int
 
 __global__ __launch_bounds__(kThreads) void layernorm_bwd_kernel(LnBatch B, float* __restrict__ ws) {
     __shared__ float red[kWaves][2][kMaxN];
-    const int di = find_desc(B.blk_start, B.n, blockIdx.x);
+    const int di = cwn::group_of<CWN_MAX_NORM_DESCS>(B.blk_start, B.n, (int)blockIdx.x);
     const cwn_ln_desc& D = B.d[di];
     const int64_t band = (int)blockIdx.x - B.blk_start[di];
     const int64_t row0 = band * kBand;
-    const int64_t Mv = rows_of(D);
+    const int64_t Mv = cwn::rows_capped(D.m_dev, D.M);
     if (row0 >= Mv) return;                                // (the sums kernel walks the bands below the count only)
     float* part = B.ws_off[di] >= 0 ? ws + B.ws_off[di] + band * 2 * D.N : nullptr;
     const int C = (D.N + 255) >> 8;
@@ -300,7 +286,7 @@ __global__ __launch_bounds__(kThreads) void layernorm_bwd_sums_kernel(LnBatch B,
     const int c = blockIdx.x * kThreads + threadIdx.x;
     const int N = D.N;
     if (c >= N || B.ws_off[blockIdx.y] < 0) return;
-    const int64_t Mv = rows_of(D);
+    const int64_t Mv = cwn::rows_capped(D.m_dev, D.M);
     const int64_t bands = Mv > 0 ? (Mv + kBand - 1) / kBand : 0;
     const float* p = ws + B.ws_off[blockIdx.y] + c;
     float s1 = 0.f, s2 = 0.f;
@@ -332,7 +318,8 @@ inline int64_t bands_of(int64_t M) { return (M + kBand - 1) / kBand; }
 int prepare(const cwn_ln_desc* descs, int n, bool bwd, LnBatch& B, int64_t* blocks_out, int64_t* ws_floats) {
     if (descs == nullptr || n <= 0 || n > CWN_MAX_NORM_DESCS) return CWN_ERR_BAD_ARG;
     B.n = n;
-    int64_t blocks = 0, ws = 0;
+    cwn::BlockFill fill(B.blk_start);
+    int64_t ws = 0;
     for (int i = 0; i < n; ++i) {
         const cwn_ln_desc& D = descs[i];
         if (D.M < 0 || D.N < 1 || D.N > kMaxN) return CWN_ERR_BAD_ARG;
@@ -352,17 +339,14 @@ int prepare(const cwn_ln_desc* descs, int n, bool bwd, LnBatch& B, int64_t* bloc
         else vec = vec && al16(D.beta);
         B.d[i] = D;
         B.vec[i] = vec ? 1 : 0;
-        B.blk_start[i] = (int32_t)blocks;
-        blocks += bands_of(D.M);
-        if (blocks >= INT32_MAX) return CWN_ERR_TOO_LARGE;
+        if (!fill.push(i, bands_of(D.M))) return CWN_ERR_TOO_LARGE;
         B.ws_off[i] = -1;
         if (bwd && (D.dgamma != nullptr || D.dbeta != nullptr)) {
             B.ws_off[i] = ws;
             ws += bands_of(D.M) * 2 * D.N;
         }
     }
-    for (int i = n; i <= CWN_MAX_NORM_DESCS; ++i) B.blk_start[i] = (int32_t)blocks;
-    *blocks_out = blocks;
+    *blocks_out = fill.close(n);
     *ws_floats = ws;
     return CWN_OK;
 }

@@ -34,6 +34,7 @@
 #include "../../include/cwn_hip.h"
 #include "cwn_mem.h"
 #include "cwn_check.h"
+#include "cwn_group.h"
 
 namespace {
 
@@ -176,17 +177,10 @@ __global__ __launch_bounds__(kThreads) void linear_wide_f32_kernel(WideBatch B) 
     __shared__ __attribute__((aligned(16))) float smem[kWFloats + kBM * kKC];
     float* const ldsW = smem;
     float* const ldsX = smem + kWFloats;
-    int di = 0;
-#pragma unroll
-    for (int i = 1; i < CWN_MAX_DESCS; ++i)
-        if (i < B.n && (int)blockIdx.x >= B.blk_start[i]) di = i;
+    const int di = cwn::group_of<CWN_MAX_DESCS>(B.blk_start, B.n, (int)blockIdx.x);
     const cwn_linear_wide_desc& D = B.d[di];
     const int64_t M = D.M;
-    int64_t live = M;
-    if (D.m_dev != nullptr) {
-        const int64_t mv = *D.m_dev;
-        live = mv < 0 ? 0 : (mv < M ? mv : M);
-    }
+    const int64_t live = cwn::rows_clamped(D.m_dev, M);
     const int N = D.N, K1 = D.K, Ktot = D.K + D.K2;
     const int tiles_n = (N + kBN - 1) / kBN;
     const int tile = (int)blockIdx.x - B.blk_start[di];
@@ -282,7 +276,7 @@ extern "C" int cwn_linear_wide_f32(const cwn_linear_wide_desc* descs, int n, cwn
     if (n < 0 || n > CWN_MAX_DESCS || (descs == nullptr && n > 0)) return CWN_ERR_BAD_ARG;
     WideBatch B{};
     B.n = n;
-    int64_t blocks = 0;
+    cwn::BlockFill fill(B.blk_start);
     for (int i = 0; i < n; ++i) {
         const cwn_linear_wide_desc& D = descs[i];
         if (D.M < 0 || D.N < 1 || D.N > CWN_LINEAR_WIDE_MAX_N || D.K < 1 || D.K2 < 0 || (int64_t)D.K + D.K2 > CWN_LINEAR_WIDE_MAX_K)
@@ -300,12 +294,10 @@ extern "C" int cwn_linear_wide_f32(const cwn_linear_wide_desc* descs, int n, cwn
                    (al16(D.W) && D.ldw % 4 == 0 && (D.w_trans ? D.N % 4 == 0 : k4) ? kVecW : 0) |
                    (al16(D.Y) && D.ldy % 4 == 0 ? kVecY : 0);
         B.d[i] = D;
-        B.blk_start[i] = (int32_t)blocks;
         // one workgroup per tile of the CAPACITY: those behind the count end at once
-        blocks += ((D.M + kBM - 1) / kBM) * ((D.N + kBN - 1) / kBN);
-        if (blocks >= INT32_MAX) return CWN_ERR_TOO_LARGE;
+        if (!fill.push(i, ((D.M + kBM - 1) / kBM) * ((D.N + kBN - 1) / kBN))) return CWN_ERR_TOO_LARGE;
     }
-    for (int i = n; i <= CWN_MAX_DESCS; ++i) B.blk_start[i] = (int32_t)blocks;
+    const int64_t blocks = fill.close(n);
     if (blocks == 0) return CWN_OK;
     if (descs[0].w_trans != 0)
         hipLaunchKernelGGL(linear_wide_f32_kernel<true>, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream_, B);

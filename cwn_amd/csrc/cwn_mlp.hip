@@ -30,6 +30,7 @@
 #include <stdlib.h>
 #include "../../include/cwn_hip.h"
 #include "cwn_tile.h"
+#include "cwn_group.h"
 
 namespace {
 
@@ -101,13 +102,13 @@ __global__ __launch_bounds__(kThreads, SEQ ? 4 : 1) void update_mlp_kernel(int32
     uint16_t* const bufD = reinterpret_cast<uint16_t*>(smem + 3 * kBufBytes);   // stage-1 output, boundary branch
     uint16_t* const bufU = reinterpret_cast<uint16_t*>(smem + 4 * kBufBytes);   // h_up
     static_assert(CWN_LAYER_MAX_DIMS == 3, "two preloaded block starts");
-    int di = 0, blk0 = 0;
+    int di = 0, blk0 = 0;              // (cwn::group_of, written out: its table is the two preloaded scalars, not B.blk_start)
     if (1 < n_pre && (int)blockIdx.x >= bs1_pre) { di = 1; blk0 = bs1_pre; }
     if (2 < n_pre && (int)blockIdx.x >= bs2_pre) { di = 2; blk0 = bs2_pre; }
     const cwn_mlp_dim& D = B.d[di];
     const int64_t row0 = (int64_t)((int)blockIdx.x - blk0) * TM;
     // rows that exist (include/cwn_hip.h, "device-side row counts"; D.M is then the capacity: it bounds the addresses)
-    const int64_t Mv = D.m_dev != nullptr ? *D.m_dev : D.M;
+    const int64_t Mv = cwn::rows_vouched(D.m_dev, D.M);
     if (row0 >= Mv) return;                         // (uniform) a tile past the batch's own rows
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int ct = wave % S::kNCT, rt0 = (wave / S::kNCT) * kRT;
@@ -311,12 +312,12 @@ extern "C" int cwn_update_mlp_f32(const cwn_mlp_dim* dims, int n_dims, int32_t F
     const int TM = 4096 / F;
     MlpBatch B{};
     B.n = n_dims;
-    int64_t blocks = 0;
+    cwn::BlockFill fill(B.blk_start);
     for (int i = 0; i < n_dims; ++i) {
         const cwn_mlp_dim& D = dims[i];
         if (D.M < 0) return CWN_ERR_BAD_ARG;
         if (D.M > cwn_update_mlp_max_rows()) return CWN_ERR_TOO_LARGE;
-        B.blk_start[i] = (int32_t)blocks;
+        fill.push(i, (D.M + TM - 1) / TM);     // (at most cwn_update_mlp_max_rows() rows each: the total fits)
         B.d[i] = D;
         if (D.M == 0) continue;
         if (D.x_up == nullptr || D.x_b == nullptr || D.y == nullptr) return CWN_ERR_BAD_ARG;
@@ -338,9 +339,8 @@ extern "C" int cwn_update_mlp_f32(const cwn_mlp_dim* dims, int n_dims, int32_t F
             if ((D.scale[s] == nullptr) != (D.shift[s] == nullptr)) return CWN_ERR_BAD_ARG;
             if (!(al16(D.bias[s]) && al16(D.scale[s]) && al16(D.shift[s]))) return CWN_ERR_ALIGN;
         }
-        blocks += (D.M + TM - 1) / TM;
     }
-    for (int i = n_dims; i <= CWN_LAYER_MAX_DIMS; ++i) B.blk_start[i] = (int32_t)blocks;
+    const int64_t blocks = fill.close(n_dims);
     if (blocks == 0) return CWN_OK;
     const int mode = mlp_form_mode();
     // more workgroups than the chip has CUs (one round of the alternating form): the sequential two-per-CU form

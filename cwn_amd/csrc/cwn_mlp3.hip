@@ -30,6 +30,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "cwn_tile.h"
+#include "cwn_group.h"
 
 namespace {
 
@@ -60,13 +61,10 @@ __global__ __launch_bounds__(kThreads, 4) void update_mlp3_kernel(Mlp3Batch B) {
     uint16_t* const P0 = reinterpret_cast<uint16_t*>(smem);
     uint16_t* const P1 = reinterpret_cast<uint16_t*>(smem + kBufBytes);
     uint16_t* const P2 = reinterpret_cast<uint16_t*>(smem + 2 * kBufBytes);
-    int di = 0;
-#pragma unroll
-    for (int i = 1; i < CWN_LAYER_MAX_DIMS; ++i)
-        if (i < B.n && (int)blockIdx.x >= B.blk_start[i]) di = i;
+    const int di = cwn::group_of<CWN_LAYER_MAX_DIMS>(B.blk_start, B.n, (int)blockIdx.x);
     const cwn_mlp3_dim& D = B.d[di];
     const int64_t row0 = (int64_t)((int)blockIdx.x - B.blk_start[di]) * TM;
-    const int64_t Mv = D.m_dev != nullptr ? *D.m_dev : D.M;      // rows that exist (D.M is then the capacity)
+    const int64_t Mv = cwn::rows_vouched(D.m_dev, D.M);      // rows that exist (D.M is then the capacity)
     if (row0 >= Mv) return;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int ct = wave % S::kNCT, rt0 = (wave / S::kNCT) * kRT;
@@ -158,12 +156,12 @@ extern "C" int cwn_update_mlp3_f32(const cwn_mlp3_dim* dims, int n_dims, int32_t
     const int TM = 4096 / F;
     Mlp3Batch B{};
     B.n = n_dims;
-    int64_t blocks = 0;
+    cwn::BlockFill fill(B.blk_start);
     for (int i = 0; i < n_dims; ++i) {
         const cwn_mlp3_dim& D = dims[i];
         if (D.M < 0) return CWN_ERR_BAD_ARG;
         if (D.M > cwn_update_mlp_max_rows()) return CWN_ERR_TOO_LARGE;
-        B.blk_start[i] = (int32_t)blocks;
+        fill.push(i, (D.M + TM - 1) / TM);     // (at most cwn_update_mlp_max_rows() rows each: the total fits)
         B.d[i] = D;
         if (D.M == 0) continue;
         if (D.y == nullptr || D.ldy < F || D.ldy % 4) return CWN_ERR_BAD_ARG;
@@ -180,9 +178,8 @@ extern "C" int cwn_update_mlp3_f32(const cwn_mlp3_dim* dims, int n_dims, int32_t
             if ((D.scale[s] == nullptr) != (D.shift[s] == nullptr)) return CWN_ERR_BAD_ARG;
             if (!(al16(D.bias[s]) && al16(D.scale[s]) && al16(D.shift[s]))) return CWN_ERR_ALIGN;
         }
-        blocks += (D.M + TM - 1) / TM;
     }
-    for (int i = n_dims; i <= CWN_LAYER_MAX_DIMS; ++i) B.blk_start[i] = (int32_t)blocks;
+    const int64_t blocks = fill.close(n_dims);
     if (blocks == 0) return CWN_OK;
     hipStream_t stream = (hipStream_t)stream_;
     return F == 128 ? launch_mlp3<128>(B, blocks, stream) : launch_mlp3<64>(B, blocks, stream);

@@ -20,6 +20,7 @@
 #include "cwn_dropout.h"
 #include "cwn_check.h"
 #include "cwn_act.h"
+#include "cwn_group.h"
 
 namespace {
 
@@ -39,14 +40,6 @@ struct BnBatch {
     int32_t n;
 };
 
-__device__ __forceinline__ int find_desc(const int32_t* start, int n, int b) {
-    int d = 0;
-#pragma unroll
-    for (int i = 1; i < CWN_MAX_NORM_DESCS; ++i)
-        if (i < n && b >= start[i]) d = i;
-    return d;
-}
-
 // grid (column chunk of 64, descriptor).  The GEMM epilogue left one fp64 partial per 32-row band
 // and column; lanes read consecutive columns (coalesced), the SIXTEEN waves take every sixteenth band
 // with eight loads in flight each: the 105 bands of a ZINC-128 dimension are one round trip (a dependent
@@ -60,7 +53,8 @@ __global__ __launch_bounds__(kFinThreads) void bn_finalize_kernel(BnBatch B) {
     const cwn_bn_desc& D = B.d[blockIdx.y];
     const int n = blockIdx.x * 64 + (threadIdx.x & 63);
     const int slice = threadIdx.x >> 6;
-    const int64_t Mv = D.m_dev != nullptr ? *D.m_dev : D.M;       // rows the statistics were taken over (D.M: capacity)
+    // rows the statistics were taken over (D.M: capacity); cwn::rows_vouched, written out: the helper changes this kernel's schedule
+    const int64_t Mv = D.m_dev != nullptr ? *D.m_dev : D.M;
     const int64_t bands = CWN_STAT_ROWS(Mv);
     const bool ok = n < D.N;
     const int nc = ok ? n : D.N - 1;
@@ -144,10 +138,10 @@ __device__ __forceinline__ void st_vec(float* p, const float (&v)[VEC]) {
 template <int VEC, int MODE>
 __global__ __launch_bounds__(kThreads) void norm_kernel(NormBatch B) {
     __shared__ float red[2][kRowsPerPass][kTPR * 4 + 4];
-    const int di = find_desc(B.blk_start, B.n, blockIdx.x);
+    const int di = cwn::group_of<CWN_MAX_NORM_DESCS>(B.blk_start, B.n, (int)blockIdx.x);
     const cwn_norm_desc& D = B.d[di];
     const int64_t row0 = (int64_t)(blockIdx.x - B.blk_start[di]) * kBand;
-    const int64_t Mv = D.m_dev != nullptr ? *D.m_dev : D.M;      // rows that exist (D.M: the capacity, bounds the addresses)
+    const int64_t Mv = cwn::rows_vouched(D.m_dev, D.M);      // rows that exist (D.M: the capacity, bounds the addresses)
     const int tc = threadIdx.x % kTPR, tr = threadIdx.x / kTPR;
     const int N = D.N;
     // (activation only) a live BatchNorm (cwn_bn_live.h): the affine is derived here from the producing launch's slot sums
@@ -318,12 +312,12 @@ constexpr int kFR = CWN_NORM_BWD_FUSED_MAX_ROWS / kFT;     // 8 rows per thread
 
 __global__ __launch_bounds__(kFT) void norm_bwd_fused_kernel(NormBatch B, int accumulate) {
     __shared__ float red[2][kFT / 64][4];
-    const int di = find_desc(B.blk_start, B.n, blockIdx.x);
+    const int di = cwn::group_of<CWN_MAX_NORM_DESCS>(B.blk_start, B.n, (int)blockIdx.x);
     const cwn_norm_desc& D = B.d[di];
     const int c = ((int)blockIdx.x - B.blk_start[di]) * 4;
     const bool has_norm = D.scale != nullptr, relu = D.relu != 0;
     const int64_t Mcap = D.M;
-    const int64_t M = D.m_dev != nullptr ? *D.m_dev : D.M;
+    const int64_t M = D.m_dev != nullptr ? *D.m_dev : D.M;    // (cwn::rows_vouched, written out: the helper changes this kernel's schedule)
     float scale[4] = {1.f, 1.f, 1.f, 1.f}, shift[4] = {0.f, 0.f, 0.f, 0.f}, mean[4] = {0.f, 0.f, 0.f, 0.f},
           rstd[4] = {0.f, 0.f, 0.f, 0.f};
     if (has_norm) {
@@ -408,7 +402,7 @@ int launch_norm(const cwn_norm_desc* descs, int n, cwn_stream_t stream_) {
     if (descs == nullptr || n <= 0 || n > CWN_MAX_NORM_DESCS) return CWN_ERR_BAD_ARG;
     NormBatch B{};
     B.n = n;
-    int64_t blocks = 0;
+    cwn::BlockFill fill(B.blk_start);
     bool vec = true;
     for (int i = 0; i < n; ++i) {
         const cwn_norm_desc& D = descs[i];
@@ -436,11 +430,9 @@ int launch_norm(const cwn_norm_desc* descs, int n, cwn_stream_t stream_) {
         vec = vec && D.N % 4 == 0 && D.ldz % 4 == 0 && (MODE == 0 || D.lddy % 4 == 0) &&
               (MODE == 1 || D.ldout % 4 == 0) && (D.dy_out == nullptr || D.lddy_out % 4 == 0);
         B.d[i] = D;
-        B.blk_start[i] = (int32_t)blocks;
-        blocks += (D.M + kBand - 1) / kBand;
-        if (blocks >= INT32_MAX) return CWN_ERR_TOO_LARGE;
+        if (!fill.push(i, (D.M + kBand - 1) / kBand)) return CWN_ERR_TOO_LARGE;
     }
-    for (int i = n; i <= CWN_MAX_NORM_DESCS; ++i) B.blk_start[i] = (int32_t)blocks;
+    const int64_t blocks = fill.close(n);
     if (blocks == 0) return CWN_OK;
     hipStream_t stream = (hipStream_t)stream_;
     if (vec) norm_kernel<4, MODE><<<dim3((unsigned)blocks), dim3(kThreads), 0, stream>>>(B);
@@ -485,7 +477,7 @@ extern "C" int cwn_norm_bwd_f32(const cwn_norm_desc* descs, int n, int accumulat
     if (descs == nullptr || n <= 0 || n > CWN_MAX_NORM_DESCS) return CWN_ERR_BAD_ARG;
     NormBatch B{};
     B.n = n;
-    int64_t blocks = 0;
+    cwn::BlockFill fill(B.blk_start);
     for (int i = 0; i < n; ++i) {
         const cwn_norm_desc& D = descs[i];
         if (D.M < 0 || D.N <= 0 || D.M > CWN_NORM_BWD_FUSED_MAX_ROWS) return CWN_ERR_BAD_ARG;
@@ -501,10 +493,9 @@ extern "C" int cwn_norm_bwd_f32(const cwn_norm_desc* descs, int n, int accumulat
             if (!al16(p)) return CWN_ERR_ALIGN;
         if (D.N % 4 != 0 || D.ldz % 4 != 0 || D.lddy % 4 != 0 || D.ldout % 4 != 0) return CWN_ERR_ALIGN;
         B.d[i] = D;
-        B.blk_start[i] = (int32_t)blocks;
-        blocks += D.M > 0 ? D.N / 4 : 0;
+        fill.push(i, D.M > 0 ? D.N / 4 : 0);     // (a workgroup per four columns; the total is not checked)
     }
-    for (int i = n; i <= CWN_MAX_NORM_DESCS; ++i) B.blk_start[i] = (int32_t)blocks;
+    const int64_t blocks = fill.close(n);
     if (blocks == 0) return CWN_OK;
     norm_bwd_fused_kernel<<<dim3((unsigned)blocks), dim3(kFT), 0, (hipStream_t)stream_>>>(B, accumulate);
     return hipGetLastError() == hipSuccess ? CWN_OK : CWN_ERR_LAUNCH;
@@ -638,10 +629,7 @@ struct AxpyBatch {
     int32_t n;
 };
 __global__ __launch_bounds__(kAxpyThreads) void axpy_eps_kernel(AxpyBatch B) {
-    int di = 0;
-#pragma unroll
-    for (int i = 1; i < CWN_AXPY_MAX_DESCS; ++i)
-        if (i < B.n && (int)blockIdx.x >= B.blk_start[i]) di = i;
+    const int di = cwn::group_of<CWN_AXPY_MAX_DESCS>(B.blk_start, B.n, (int)blockIdx.x);
     const cwn_axpy_desc& D = B.d[di];
     const float s = 1.0f + (D.eps != nullptr ? *D.eps : 0.f);
     const int64_t n4 = D.n / 4;
@@ -670,17 +658,15 @@ __global__ __launch_bounds__(kAxpyThreads) void axpy_eps_kernel(AxpyBatch B) {
 extern "C" int cwn_axpy_eps_f32(const cwn_axpy_desc* descs, int n, cwn_stream_t stream_) {
     if (descs == nullptr || n < 1 || n > CWN_AXPY_MAX_DESCS) return CWN_ERR_BAD_ARG;
     AxpyBatch B{};
-    int64_t blocks = 0;
+    cwn::BlockFill fill(B.blk_start);
     for (int i = 0; i < n; ++i) {
         const cwn_axpy_desc& D = descs[i];
         if (D.n < 0 || (D.n & 3) != 0 || (D.n > 0 && (D.y == nullptr || D.x == nullptr))) return CWN_ERR_BAD_ARG;
         if ((((uintptr_t)D.y) | ((uintptr_t)D.x)) & 15u) return CWN_ERR_ALIGN;
         B.d[i] = D;
-        B.blk_start[i] = (int32_t)blocks;
-        blocks += (D.n / 4 + kAxpyThreads * kAxpyPer - 1) / (kAxpyThreads * kAxpyPer);
-        if (blocks >= INT32_MAX) return CWN_ERR_TOO_LARGE;
+        if (!fill.push(i, (D.n / 4 + kAxpyThreads * kAxpyPer - 1) / (kAxpyThreads * kAxpyPer))) return CWN_ERR_TOO_LARGE;
     }
-    for (int i = n; i <= CWN_AXPY_MAX_DESCS; ++i) B.blk_start[i] = (int32_t)blocks;
+    const int64_t blocks = fill.close(n);
     B.n = n;
     if (blocks == 0) return CWN_OK;
     axpy_eps_kernel<<<dim3((unsigned)blocks), dim3(kAxpyThreads), 0, (hipStream_t)stream_>>>(B);
@@ -707,7 +693,7 @@ __global__ __launch_bounds__(256) void dropout_kernel(const float* __restrict__ 
                                                       int64_t ldout, cwn_dropout d, const int64_t* __restrict__ m_dev, int vec) {
     cwn::Dropout drop;
     drop.init(d);
-    const int64_t Mv = m_dev != nullptr ? (*m_dev < M ? *m_dev : M) : M;
+    const int64_t Mv = cwn::rows_capped(m_dev, M);
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     if (vec) {
         const int64_t nq = Mv * (N / 4);
@@ -755,6 +741,7 @@ __global__ __launch_bounds__(256) void loss_kernel(const float* __restrict__ pre
     __shared__ float part[256];
     __shared__ int cnt[256];
     // (a static batch: *n_dev complexes with `cols` predictions each are real, the rest of the n_cap elements is capacity)
+    // (open-coded: the count is scaled by `cols` before it meets the capacity -- no rows_* reader takes a product)
     const int64_t n = n_dev != nullptr ? (*n_dev * cols < n_cap ? *n_dev * cols : n_cap) : n_cap;
     if (kind == CWN_LOSS_CE) {
         // torch.nn.CrossEntropyLoss() (exp/train_utils.py:21-22, REDDIT-BINARY / the TU datasets): pred [rows, cols] logits, y the
@@ -887,7 +874,7 @@ __global__ __launch_bounds__(256) void embedding_bwd_kernel(const float* __restr
                                                             float* __restrict__ dW, int64_t n_cap, int cols,
                                                             int H, int64_t V, int src_f32, const int64_t* __restrict__ n_dev) {
     extern __shared__ float table[];          // [V][H]
-    const int64_t n_rows = n_dev != nullptr ? (*n_dev < n_cap ? *n_dev : n_cap) : n_cap;
+    const int64_t n_rows = cwn::rows_capped(n_dev, n_cap);
     const int64_t r0 = (int64_t)blockIdx.x * kEmbBand;
     if (r0 >= n_rows) return;                 // (uniform) a band past the batch's own rows
     const int64_t total = V * H;
@@ -946,7 +933,7 @@ __global__ __launch_bounds__(256) void embedding_bwd_cols_kernel(const float* __
                                                                  const int64_t* __restrict__ n_dev) {
     __shared__ __attribute__((aligned(16))) float rows[kEmbBand][H];
     const int tid = threadIdx.x, lane = tid & 63;
-    const int64_t n_rows = n_dev != nullptr ? (*n_dev < n_cap ? *n_dev : n_cap) : n_cap;
+    const int64_t n_rows = cwn::rows_capped(n_dev, n_cap);
     const int64_t r0 = (int64_t)blockIdx.x * kEmbBand;
     if (r0 >= n_rows) return;                 // (uniform) a band past the batch's own rows
     const int n = (int)((n_rows - r0) < kEmbBand ? (n_rows - r0) : kEmbBand);
@@ -1011,7 +998,7 @@ __global__ __launch_bounds__(256) void embedding_bwd_one_table_kernel(const floa
                                                                      const int64_t* __restrict__ n_dev) {
     __shared__ __attribute__((aligned(16))) float rows[kEmbBand][H];
     const int tid = threadIdx.x, lane = tid & 63;
-    const int64_t n_rows = n_dev != nullptr ? (*n_dev < n_cap ? *n_dev : n_cap) : n_cap;
+    const int64_t n_rows = cwn::rows_capped(n_dev, n_cap);
     const int64_t r0 = (int64_t)blockIdx.x * kEmbBand;
     if (r0 >= n_rows) return;                 // (uniform) a band past the batch's own rows
     const int n = (int)((n_rows - r0) < kEmbBand ? (n_rows - r0) : kEmbBand);

@@ -22,6 +22,7 @@
 #include "../../include/cwn_hip.h"
 #include "cwn_act.h"
 #include "cwn_check.h"
+#include "cwn_group.h"
 
 namespace {
 
@@ -115,11 +116,7 @@ __global__ __launch_bounds__(kThreads) void oriented_layer_kernel(OrientedArgs P
     const int64_t ldx = P.d.ldx;
     const float* __restrict__ x = P.d.x;
     const int64_t row0 = (int64_t)blockIdx.x * TM;
-    int64_t m = P.d.n;
-    if (P.d.m_dev != nullptr) {
-        const int64_t live = *P.d.m_dev;
-        m = live < m ? live : m;
-    }
+    const int64_t m = cwn::rows_capped(P.d.m_dev, (int64_t)P.d.n);
     if (row0 >= m) return;                        // (uniform: nothing of this tile exists)
 
     // ---- 1. the panel -------------------------------------------------------------------------------------------------
@@ -251,11 +248,7 @@ struct DzArgs {
 };
 
 __global__ __launch_bounds__(kThreads) void oriented_dz_kernel(DzArgs P) {
-    int64_t m = P.n;
-    if (P.m_dev != nullptr) {
-        const int64_t live = *P.m_dev;
-        m = live < m ? live : m;
-    }
+    const int64_t m = cwn::rows_capped(P.m_dev, (int64_t)P.n);
     const int64_t total = m * P.H;
     for (int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x; e < total; e += (int64_t)gridDim.x * kThreads) {
         const int64_t r = e / P.H;

@@ -21,6 +21,7 @@
 #include <stdlib.h>
 #include "cwn_tile.h"
 #include "cwn_bn_live.h"
+#include "cwn_group.h"
 
 namespace {
 
@@ -77,15 +78,12 @@ __device__ __forceinline__ void dense_stage_body(const BatchT& B) {
     __shared__ __attribute__((aligned(16))) double live_scratch[EX ? 512 : 256];
     uint16_t* const buf0 = reinterpret_cast<uint16_t*>(smem);
     uint16_t* const buf1 = reinterpret_cast<uint16_t*>(smem + kBufBytes);
-    int di = 0;
-#pragma unroll
-    for (int i = 1; i < CWN_MAX_DESCS; ++i)
-        if (i < B.n && (int)blockIdx.x >= B.blk_start[i]) di = i;
+    const int di = cwn::group_of<CWN_MAX_DESCS>(B.blk_start, B.n, (int)blockIdx.x);
     const cwn_stage_desc& D = B.d[di];
     const int64_t row0 = (int64_t)((int)blockIdx.x - B.blk_start[di]) * TM;
     // rows that exist (include/cwn_hip.h, "device-side row counts"): D.M is then the capacity of the buffers -- it bounds the
     // addresses below, so that no load waits for this one -- and Mv what is stored and counted
-    const int64_t Mv = D.m_dev != nullptr ? *D.m_dev : D.M;
+    const int64_t Mv = cwn::rows_vouched(D.m_dev, D.M);
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int ct = wave % S::kNCT, rt0 = (wave / S::kNCT) * kRT;
     const int l15 = lane & 15, kq = lane >> 4;
@@ -315,6 +313,7 @@ __global__ __launch_bounds__(kThreads, 4) void dense_stage_bwd_kernel(StageBwdBa
     // a live producer on their way to one coalesced atomic per column ([half][s1 | s2][F])
     __shared__ __attribute__((aligned(16))) float bn_scratch[256];
     uint16_t* const buf0 = reinterpret_cast<uint16_t*>(smem);
+    // (cwn::group_of, written out: through the helper this kernel's register allocation and schedule come out differently)
     int di = 0;
 #pragma unroll
     for (int i = 1; i < CWN_MAX_DESCS; ++i)
@@ -322,7 +321,7 @@ __global__ __launch_bounds__(kThreads, 4) void dense_stage_bwd_kernel(StageBwdBa
     const cwn_stage_bwd_desc& D = B.d[di];
     const bool first_block = (int)blockIdx.x == B.blk_start[di];
     const int64_t row0 = (int64_t)((int)blockIdx.x - B.blk_start[di]) * TM;
-    const int64_t Mv = D.m_dev != nullptr ? *D.m_dev : D.M;      // rows that exist (D.M: the capacity, bounds the addresses)
+    const int64_t Mv = cwn::rows_vouched(D.m_dev, D.M);      // rows that exist (D.M: the capacity, bounds the addresses)
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int ct = wave % S::kNCT, rt0 = (wave / S::kNCT) * kRT;
     const int l15 = lane & 15, kq = lane >> 4;
@@ -608,11 +607,11 @@ static int fill_stage_batch(StageBatch& B, const cwn_stage_desc* descs, int n, i
     if (descs == nullptr || n < 1 || n > CWN_MAX_DESCS || (F != 64 && F != 128)) return CWN_ERR_BAD_ARG;
     const int TM = 4096 / F;
     B.n = n;
-    blocks = 0;
+    cwn::BlockFill fill(B.blk_start);
     for (int i = 0; i < n; ++i) {
         const cwn_stage_desc& D = descs[i];
         if (D.M < 0) return CWN_ERR_BAD_ARG;
-        B.blk_start[i] = (int32_t)blocks;
+        const bool fits = fill.push(i, (D.M + TM - 1) / TM);      // (refused below, behind the descriptor's own checks)
         B.d[i] = D;
         if (D.M == 0) continue;
         if (D.X == nullptr || D.Y == nullptr || D.w_packed == nullptr) return CWN_ERR_BAD_ARG;
@@ -632,10 +631,9 @@ static int fill_stage_batch(StageBatch& B, const cwn_stage_desc* descs, int n, i
               al16(D.in_shift) && al16(D.in_scale2) && al16(D.in_shift2)))
             return CWN_ERR_ALIGN;
         if (((uintptr_t)D.col_sum & 7u) || ((uintptr_t)D.col_sumsq & 7u)) return CWN_ERR_ALIGN;
-        blocks += (D.M + TM - 1) / TM;
-        if (blocks >= INT32_MAX) return CWN_ERR_TOO_LARGE;
+        if (!fits) return CWN_ERR_TOO_LARGE;
     }
-    for (int i = n; i <= CWN_MAX_DESCS; ++i) B.blk_start[i] = (int32_t)blocks;
+    blocks = fill.close(n);
     static const int dbg = getenv("CWN_STAGE_DBG") ? atoi(getenv("CWN_STAGE_DBG")) : 0;
     B.dbg = dbg;
     return CWN_OK;
@@ -680,11 +678,11 @@ extern "C" int cwn_dense_stage_bwd_f32(const cwn_stage_bwd_desc* descs, int n, i
     const int TM = 4096 / F;
     StageBwdBatch B{};
     B.n = n;
-    int64_t blocks = 0;
+    cwn::BlockFill fill(B.blk_start);
     for (int i = 0; i < n; ++i) {
         const cwn_stage_bwd_desc& D = descs[i];
         if (D.M < 0) return CWN_ERR_BAD_ARG;
-        B.blk_start[i] = (int32_t)blocks;
+        const bool fits = fill.push(i, (D.M + TM - 1) / TM);      // (refused below, behind the descriptor's own checks)
         B.d[i] = D;
         if (D.M == 0) continue;
         if (D.dy == nullptr || D.z == nullptr || D.wt_packed == nullptr || D.dx == nullptr) return CWN_ERR_BAD_ARG;
@@ -704,10 +702,9 @@ extern "C" int cwn_dense_stage_bwd_f32(const cwn_stage_bwd_desc* descs, int n, i
         if (!(al16(D.dy) && al16(D.z) && al16(D.dz) && al16(D.dx) && al16(D.dx2) && al16(D.wt_packed) && al16(D.wt2_packed) &&
               al16(D.scale) && al16(D.shift) && al16(D.mean) && al16(D.rstd) && al16(D.s1) && al16(D.s2) && al16(D.acc1) && al16(D.acc2)))
             return CWN_ERR_ALIGN;
-        blocks += (D.M + TM - 1) / TM;
-        if (blocks >= INT32_MAX) return CWN_ERR_TOO_LARGE;
+        if (!fits) return CWN_ERR_TOO_LARGE;
     }
-    for (int i = n; i <= CWN_MAX_DESCS; ++i) B.blk_start[i] = (int32_t)blocks;
+    const int64_t blocks = fill.close(n);
     if (blocks == 0) return CWN_OK;
     return F == 128 ? launch_stage_bwd<128>(B, blocks, (hipStream_t)stream_) : launch_stage_bwd<64>(B, blocks, (hipStream_t)stream_);
 }

@@ -24,6 +24,7 @@
 #include <hip/hip_runtime.h>
 #include "../../include/cwn_hip.h"
 #include "cwn_check.h"
+#include "cwn_group.h"
 
 namespace {
 
@@ -36,12 +37,6 @@ constexpr int kChunkRows = 64;                     // rows of dx per workgroup
 constexpr int kSlab = 64;                          // columns of dW per workgroup
 constexpr int kStage = 64;                         // complexes staged at a time for dW
 constexpr size_t kLdsMax = 64 * 1024;              // W beyond it is read from global memory
-
-__device__ __forceinline__ int64_t live_count(const int64_t* m_dev, int64_t cap) {
-    if (m_dev == nullptr) return cap;
-    const int64_t live = *m_dev;
-    return live < 0 ? 0 : (live < cap ? live : cap);
-}
 
 // floats of one group's slice of the workspace: dW [K, H], then db padded to whole 16-byte vectors
 __host__ __device__ __forceinline__ int64_t slice_floats(int32_t H, int32_t K) { return (int64_t)K * H + ((K + 3) & ~3); }
@@ -65,7 +60,7 @@ __global__ __launch_bounds__(kThreads) void target_head_kernel(FwdArgs P) {
     extern __shared__ __attribute__((aligned(16))) float wlds[];     // [K][H] when kLdsW
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int H = P.H, K = P.K, nq = H >> 2;
-    const int64_t C = live_count(P.m_dev, P.C);
+    const int64_t C = cwn::rows_clamped(P.m_dev, (int64_t)P.C);
     const int64_t c0 = (int64_t)blockIdx.x * kFwdBlock;
     if (c0 >= C) return;                          // (uniform: before any barrier)
     if (kLdsW) {
@@ -133,7 +128,7 @@ __global__ __launch_bounds__(kThreads) void target_head_bwd_kernel(BwdArgs P) {
     __shared__ int owner[kChunkRows];                                     // row of the chunk -> its first complex, or -1
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int H = P.H, K = P.K, nq = H >> 2;
-    const int64_t C = live_count(P.m_dev, P.C);
+    const int64_t C = cwn::rows_clamped(P.m_dev, (int64_t)P.C);
     const int32_t* __restrict__ trow = P.target_row;
 
     if (blockIdx.x < P.dx_blocks) {
@@ -238,7 +233,7 @@ __global__ __launch_bounds__(kThreads) void target_head_bwd_kernel(BwdArgs P) {
 __global__ __launch_bounds__(kThreads) void target_head_sum_kernel(const float* __restrict__ ws, float* __restrict__ dW,
                                                                    float* __restrict__ db, const int64_t* m_dev, int64_t C, int32_t H,
                                                                    int32_t K) {
-    const int64_t live = live_count(m_dev, C);
+    const int64_t live = cwn::rows_clamped(m_dev, C);
     const int groups = (int)((live + kStage - 1) / kStage);
     const int64_t per = slice_floats(H, K);
     const int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x;

@@ -26,12 +26,19 @@
  *     any shape up to the capacity; the item-table kernels (cwn_layer_fused_f32, cwn_layer_bwd_own_f32) have always
  *     worked this way (their sizes live in the item table).  cwn_collate_tables / cwn_layer_items_build_dev /
  *     cwn_layer_bwd_items_build_dev produce the per-batch tables on the device.
- *     Who checks "*m_dev <= capacity": cwn_gemm_f32 (both kernels), cwn_gemm_tn_f32, cwn_layernorm_*, cwn_dropout_f32,
- *     cwn_loss_f32 / cwn_loss_cols_f32, cwn_csr_long_rows, cwn_embedding_bwd_f32, cwn_embed_front_f32,
- *     cwn_embed_front_bwd_f32, cwn_oriented_layer_f32 / cwn_oriented_dz_f32, cwn_target_head_f32 / _bwd_f32, cwn_update_chain_f32, cwn_linear_stats_f32 and cwn_linear_wide_f32 CLAMP the count to the capacity (a larger count behaves as the capacity); cwn_dense_stage_f32 /
- *     _ex / _bwd, cwn_bn_finalize_f32, cwn_norm_*, cwn_update_mlp_f32 / cwn_update_mlp3_f32 and cwn_aggregate_f32 / _f64 take
- *     the count AS IT IS -- there the caller's vouching is what keeps the stores inside the buffers (the collate guard,
- *     cwn_collate_guard, zeroes the counts of a batch beyond its capacities before any of them is read).
+ *     Who checks "*m_dev <= capacity": the rule lives in cwn_amd/csrc/cwn_group.h, as three readers, and every kernel
+ *     names the one it uses where it reads the count (a few kernels write the reader's expression out, and say so there;
+ *     cwn_linear_stats.hip still has its own copy of the clamp).
+ *     cwn::rows_clamped -- the count clamped to [0, capacity]: cwn_gemm_f32 (both kernels), cwn_linear_stats_f32,
+ *     cwn_linear_wide_f32, cwn_update_chain_f32, cwn_target_head_f32 / _bwd_f32, cwn_csr_build (e_dev), cwn_csr_long_rows
+ *     and the cochain count of cwn_flow_head_dev_f32 / _bwd_dev_f32.  cwn::rows_capped -- the count capped ABOVE only (a
+ *     larger count behaves as the capacity; a negative one bounds loops that run upwards from 0, so nothing is stored):
+ *     cwn_gemm_tn_f32, cwn_layernorm_*, cwn_dropout_f32, cwn_loss_f32 / cwn_loss_cols_f32, cwn_embedding_bwd_f32,
+ *     cwn_embed_front_f32, cwn_embed_front_bwd_f32, cwn_oriented_layer_f32 / cwn_oriented_dz_f32.  cwn::rows_vouched -- the
+ *     count AS IT IS: cwn_dense_stage_f32 / _ex / _bwd, cwn_bn_finalize_f32, cwn_norm_*, cwn_update_mlp_f32 /
+ *     cwn_update_mlp3_f32 and cwn_aggregate_f32 / _f64 -- there the caller's vouching is what keeps the stores inside the
+ *     buffers (the collate guard, cwn_collate_guard, zeroes the counts of a batch beyond its capacities before any of
+ *     them is read).
  *     tests/test_gpu_row_counts.py pins the contract per entry point at counts of 0, 1, the capacity and around every tile
  *     height.
  *   - OPERAND WINDOWS.  A dense operand [rows, width] with a row stride of its own (ldx, ldx2, ldw, ldy, lddz, lddx, ldout ...)
