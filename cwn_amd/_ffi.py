@@ -29,7 +29,7 @@ EXPORTS = ('cwn_abi_version', 'cwn_error_string', 'cwn_target_arch', 'cwn_csr_wo
            'cwn_target_head_f32', 'cwn_target_head_bwd_f32', 'cwn_target_head_bwd_workspace_bytes',
            'cwn_flow_head_f32', 'cwn_flow_head_bwd_f32', 'cwn_flow_head_workspace_floats',
            'cwn_flow_head_dev_f32', 'cwn_flow_head_bwd_dev_f32', 'cwn_table_advance',
-           'cwn_linear_many_f64', 'cwn_update_chain_f64', 'cwn_update_chain_f32', 'cwn_linear_stats_f32',
+           'cwn_linear_many_f64', 'cwn_update_chain_f64', 'cwn_update_chain_f32', 'cwn_update_branches_f32', 'cwn_linear_stats_f32',
            'cwn_linear_wide_f32',
            'cwn_aggregate_act_f32', 'cwn_aggregate_act_f64',
            'cwn_embed_pool_f32', 'cwn_embed_pool_f64', 'cwn_agnostic_head_f32', 'cwn_agnostic_head_f64',
@@ -401,6 +401,21 @@ class ChainDescF32(C.Structure):
     _fields_ = ChainDescF64._fields_ + [('m_dev', C.c_void_p)]
 
 
+# the float32 update branches (csrc/cwn_branches_f32.hip) = CWN_BRANCHES_F32_MAX_DIMS / _MAX_WIDTH / _TM / _MIN_BRANCHES /
+# _MAX_BRANCHES / _STAGES
+BRANCHES_F32_MAX_DIMS, BRANCHES_F32_MAX_WIDTH, BRANCHES_F32_TM = 4, 128, 32
+BRANCHES_F32_MIN_BRANCHES, BRANCHES_F32_MAX_BRANCHES, BRANCHES_F32_STAGES = 3, 4, 9
+
+
+class BranchesDescF32(C.Structure):
+    """cwn_branches_desc_f32: the three or four update networks and the combine of one dimension of a cwn_update_branches_f32
+    launch (stage 2k, 2k + 1: branch k; stage 2 nb: the combine)."""
+    _fields_ = [('ins', C.c_void_p * 4), ('out', C.c_void_p), ('W', C.c_void_p * 9), ('bias', C.c_void_p * 9),
+                ('scale', C.c_void_p * 9), ('shift', C.c_void_p * 9), ('n', C.c_int64), ('ld_in', C.c_int64 * 4),
+                ('ld_out', C.c_int64), ('F', C.c_int32), ('H', C.c_int32), ('act', C.c_int32), ('nb', C.c_int32),
+                ('m_dev', C.c_void_p)]
+
+
 class GemmTnDesc(C.Structure):
     _fields_ = [('dZ', C.c_void_p), ('X', C.c_void_p), ('X2', C.c_void_p), ('in_scale', C.c_void_p),
                 ('in_shift', C.c_void_p), ('in_scale2', C.c_void_p), ('in_shift2', C.c_void_p),
@@ -580,6 +595,8 @@ def lib():
     L.cwn_update_chain_f64.argtypes = [C.POINTER(ChainDescF64), C.c_int, C.c_void_p]
     L.cwn_update_chain_f32.restype = C.c_int
     L.cwn_update_chain_f32.argtypes = [C.POINTER(ChainDescF32), C.c_int, C.c_void_p]
+    L.cwn_update_branches_f32.restype = C.c_int
+    L.cwn_update_branches_f32.argtypes = [C.POINTER(BranchesDescF32), C.c_int, C.c_void_p]
     L.cwn_aggregate_act_f32.restype = C.c_int
     L.cwn_aggregate_act_f32.argtypes = [C.POINTER(AggActDesc), C.c_int, C.c_void_p]
     L.cwn_aggregate_act_f64.restype = C.c_int

@@ -15,8 +15,9 @@
 //   2. a stage is a panel times a weight on v_mfma_f32_16x16x4_f32 (exact fp32) with the operand roles and K-slab walk of
 //      cwn_gin_tile.h: A = 16 weight rows (output columns), B = 16 panel rows, K in slabs of 16 in which lane group
 //      g = lane >> 4 owns k = 4g .. 4g + 3 -- the panel fragment is one 16-byte LDS read, a lane's four accumulator
-//      registers are four consecutive output columns of one row.  (Its own product and not that header's: a weight here
-//      has a row stride -- the two halves of W4 -- and the combine continues an accumulator.)  Weights come straight from
+//      registers are four consecutive output columns of one row.  (The tile code is cwn_chain_tile.h, shared with
+//      cwn_branches_f32.hip; not cwn_gin_tile.h's product: a weight here has a row stride -- the two halves of W4 -- and the
+//      combine continues an accumulator.)  Weights come straight from
 //      global memory, row-major as torch.nn.Linear holds them, as 16-byte vectors where width and alignment allow.
 //   3. bias, affine and activation in the accumulator layout; the result goes to a panel, never to memory:
 //      pa -> ph -> pa (u), pb -> ph -> pb (b): the hidden panel is shared, a branch's result overwrites its input.
@@ -26,120 +27,17 @@
 // No atomics, no split of K across lanes that depends on anything but the widths: an output element is one chain of
 // products in a k order fixed by (F, H), so a row has the same bits alone or anywhere in any batch.
 // LDS (static): update_chain_f32 (3 x 32 x 132) elements = 50688 B in float32.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include "../../include/cwn_hip.h"
-#include "cwn_act.h"
+#include "cwn_chain_tile.h"
 #include "cwn_check.h"
 #include "cwn_group.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kMaxWidth = CWN_CHAIN_F32_MAX_WIDTH;
-constexpr int kTM = CWN_CHAIN_F32_TM;
-constexpr int kLdp = kMaxWidth + 4;               // panel pitch: 16-byte rows, 4 banks apart
-constexpr int kRT = kTM / 16;                     // row tiles of a product, all of them on every wave
-constexpr int kCT = kMaxWidth / 16 / kWaves;      // column tiles per wave (2)
-
-static_assert(kTM % 16 == 0 && kMaxWidth % (16 * kWaves) == 0, "whole MFMA tiles");
 
 struct ChainBatch {
     cwn_chain_desc_f32 d[CWN_CHAIN_F32_MAX_DIMS];
     int32_t blk_start[CWN_CHAIN_F32_MAX_DIMS + 1];
     int32_t n;
 };
-
-__device__ __forceinline__ int round16(int v) { return (v + 15) & ~15; }
-
-__device__ __forceinline__ void clear(f32x4 (&acc)[kCT][kRT]) {
-#pragma unroll
-    for (int ct = 0; ct < kCT; ++ct)
-#pragma unroll
-        for (int rt = 0; rt < kRT; ++rt) acc[ct][rt] = f32x4{0.f, 0.f, 0.f, 0.f};
-}
-
-// acc[ct][rt] += panel[rt * 16 + j][0 .. K rounded up to 16) . W[(wave + 4 ct) * 16 + j][0 .. K)^T   (W row-major [N, K], row
-// stride ldw; the panel holds zeros in its columns from K on)
-__device__ __forceinline__ void product(f32x4 (&acc)[kCT][kRT], const float* panel, const float* __restrict__ W, int ldw, int K,
-                                        int N, int wave, int j, int g) {
-    const int kp = round16(K), n_tiles = (N + 15) >> 4;
-    const bool vec = K % 4 == 0 && ldw % 4 == 0 && ((uintptr_t)W & 15) == 0;      // (uniform)
-    for (int k0 = 0; k0 < kp; k0 += 16) {
-        const int kk = k0 + 4 * g;                // this lane group's four k of the slab
-        float wf[kCT][4];
-#pragma unroll
-        for (int ct = 0; ct < kCT; ++ct) {
-            const int n = (wave + kWaves * ct) * 16 + j;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) wf[ct][t] = 0.f;
-            if (n >= N) continue;
-            if (vec) {                            // (K % 4 == 0: the four k are inside the row or all beyond it)
-                if (kk < K) {
-                    const float4 v = *reinterpret_cast<const float4*>(W + (int64_t)n * ldw + kk);
-                    wf[ct][0] = v.x; wf[ct][1] = v.y; wf[ct][2] = v.z; wf[ct][3] = v.w;
-                }
-            } else {
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-                    if (kk + t < K) wf[ct][t] = W[(int64_t)n * ldw + kk + t];
-            }
-        }
-        f32x4 xb[kRT];
-#pragma unroll
-        for (int rt = 0; rt < kRT; ++rt) xb[rt] = *reinterpret_cast<const f32x4*>(panel + (rt * 16 + j) * kLdp + kk);
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int ct = 0; ct < kCT; ++ct) {
-                if (wave + kWaves * ct >= n_tiles) continue;          // (wave-uniform)
-#pragma unroll
-                for (int rt = 0; rt < kRT; ++rt)
-                    acc[ct][rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[ct][t], xb[rt][t], acc[ct][rt], 0, 0, 0);
-            }
-    }
-}
-
-// act((z + bias) * scale + shift) of one output column (an absent operand is skipped, not multiplied by one)
-__device__ __forceinline__ float epilogue(float z, int n, const float* __restrict__ bias, const float* __restrict__ scale,
-                                          const float* __restrict__ shift, int act) {
-    if (bias != nullptr) z = z + bias[n];
-    if (scale != nullptr) z = z * scale[n];
-    if (shift != nullptr) z = z + shift[n];
-    return activate_rt(z, act);
-}
-
-// acc[ct][rt][q] = z[rt * 16 + j][(wave + 4 ct) * 16 + 4 g + q] -> panel, finished; the tiles below H rounded up to 16 cover
-// those columns once, the ones from H on as zeros (the next product's K slabs read them)
-__device__ __forceinline__ void to_panel(float* panel, const f32x4 (&acc)[kCT][kRT], int H, const float* bias, const float* scale,
-                                         const float* shift, int act, int wave, int j, int g) {
-    const int kp = round16(H);
-#pragma unroll
-    for (int ct = 0; ct < kCT; ++ct) {
-        const int n0 = (wave + kWaves * ct) * 16 + 4 * g;
-        if (n0 >= kp) continue;
-#pragma unroll
-        for (int rt = 0; rt < kRT; ++rt) {
-            f32x4 y;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) y[q] = n0 + q < H ? epilogue(acc[ct][rt][q], n0 + q, bias, scale, shift, act) : 0.f;
-            *reinterpret_cast<f32x4*>(panel + (rt * 16 + j) * kLdp + n0) = y;
-        }
-    }
-}
-
-// rows [row0, row0 + kTM) of x [.., F] (row stride ld) -> panel; rows from n on and columns [F, F rounded up to 16): zeros
-__device__ __forceinline__ void load_panel(float* panel, const float* __restrict__ x, int64_t ld, int64_t row0, int64_t n, int F,
-                                           int tid) {
-    const int kp = round16(F);
-    for (int i = tid; i < kTM * kp; i += kThreads) {
-        const int r = i / kp, c = i - r * kp;
-        panel[r * kLdp + c] = (c < F && row0 + r < n) ? x[(row0 + r) * ld + c] : 0.f;
-    }
-}
 
 __global__ __launch_bounds__(kThreads) void update_chain_f32_kernel(ChainBatch B) {
     __shared__ __attribute__((aligned(16))) float pa[kTM * kLdp];       // in_up, then u
@@ -178,6 +76,8 @@ __global__ __launch_bounds__(kThreads) void update_chain_f32_kernel(ChainBatch B
     product(acc, pa, D.W[4], 2 * H, H, H, wave, j, g);
     product(acc, pb, D.W[4] + H, 2 * H, H, H, wave, j, g);
 
+    // (written out, not cwn_chain_tile.h's to_out, which stands for the same text: with the call this kernel's registers
+    //  and assembly change -- tools/isa_diff.sh)
     float* __restrict__ out = D.out;
     const int64_t ld_out = D.ld_out;
     const bool out_vec = ((uintptr_t)out & 15) == 0 && ld_out % 4 == 0;

@@ -159,6 +159,30 @@ FUSED_CHAIN_F32 = _chain_f32_switch(os.environ.get('CWN_FUSED_CHAIN_F32'))
 def _chain_f32_on(regime: str) -> bool:
     on = FUSED_CHAIN_F32
     return regime in on if isinstance(on, (set, frozenset)) else bool(on)
+# The update / combine networks of a float32 CINppConv layer in inference -- three or four branches and the nb*H-wide
+# combine -- as ONE cwn_update_branches_f32 launch (csrc/cwn_branches_f32.hip: any width up to 128, any of the five
+# activations) where cwn_update_mlp3_f32 does not serve them.  A switch of its own, a set of regimes as FUSED_CHAIN_F32 is:
+#   'relu_width'  ReLU networks that cwn_update_mlp3_f32 does not take -- a width other than 64 / 128, a first layer with
+#                 F != H, four branches at any width -- instead of a grouped GEMM launch per stage + torch.cat + combine_nn;
+#   'act'         networks with elu / tanh / sigmoid / id at any width up to 128, instead of the torch modules.
+# CWN_FUSED_BRANCHES_F32=1 / =0: both / neither; unset: FUSED_BRANCHES_F32_DEFAULT, which holds the regimes in which the route
+# has measured faster than the one it replaces by more than the run-to-run spread of both (tools/bench_branches_f32.py,
+# profiles/branches_f32.md) with the whole suite passing.  True / False are read as both / neither.
+BRANCHES_F32_REGIMES = frozenset({'relu_width', 'act'})
+FUSED_BRANCHES_F32_DEFAULT = frozenset({'relu_width', 'act'})
+
+
+def _branches_f32_switch(value: Optional[str]):
+    """The regimes CWN_FUSED_BRANCHES_F32 = `value` turns on."""
+    return {'0': frozenset(), '1': BRANCHES_F32_REGIMES}.get(value, FUSED_BRANCHES_F32_DEFAULT)
+
+
+FUSED_BRANCHES_F32 = _branches_f32_switch(os.environ.get('CWN_FUSED_BRANCHES_F32'))
+
+
+def _branches_f32_on(regime: str) -> bool:
+    on = FUSED_BRANCHES_F32
+    return regime in on if isinstance(on, (set, frozenset)) else bool(on)
 CSR_REUSE = True              # blocked layer kernel: sort a batch's adjacencies once, later layers load the result
 # One workgroup per item and one item per CU at a time: the blocked kernel wins while the items fit the chip
 # a few times over (measured on ZINC-like batches, tools/range_of_use.sh, M cells/s blocked vs CSR path: 256
@@ -275,6 +299,7 @@ class ByModule:
 _BLOCKED_CACHE = ByModule()
 _MLP_CACHE = ByModule()            # layer module -> (ops.MlpLaunch, (start, dims, outputs), BatchNorm modules)
 _CHAIN_CACHE = ByModule()          # layer module -> {regime: (ops.ChainLaunch or None: declined, (start, dims), BatchNorm modules, STRUCT_EPOCH)}
+_BRANCHES_CACHE = ByModule()       # CINppConv module -> {regime: (ops.BranchesLaunch or None: declined, (start, dims), BatchNorm modules, STRUCT_EPOCH)}
 FUSED_OGB_FRONT = os.environ.get('CWN_FUSED_OGB_FRONT', '1') != '0'      # (A/B: '0' = the separate launches of the OGB encoders' front)
 _FRONT_CACHE = ByModule()          # embedding front module -> {id(boundary_index_1): (ops.FrontLaunch, (rings?, reduce))}
 
@@ -1244,7 +1269,9 @@ class SparseCINConv(torch.nn.Module):
         BatchNorm and the ReLU folded into the epilogue -- in ONE launch where `_one_launch` has a kernel for them, else
         as one grouped MFMA launch per update stage over every branch and dimension, then the combine: two branches as a
         grouped launch with torch.cat folded into the K-concatenation, three or four as torch.cat + combine_nn.  ReLU networks
-        at a width that kernel does not take go to `_dense_chain_f32` first (regime 'relu_width' of FUSED_CHAIN_F32).  No
+        at a width that kernel does not take go to `_dense_chain_f32` first (regime 'relu_width' of FUSED_CHAIN_F32); the three
+        or four ReLU branches of a CIN++ layer that `_one_launch` did not take go to `_dense_branches_f32` (regime
+        'relu_width' of FUSED_BRANCHES_F32) in front of the grouped launches.  No
         autograd, running statistics; returns None when it does not apply and the caller runs the torch modules instead."""
         from . import _ffi
         if torch.is_grad_enabled() or any(o.dtype != torch.float32 for o in outs):
@@ -1262,6 +1289,10 @@ class SparseCINConv(torch.nn.Module):
                 del _MLP_CACHE[self]
         if FUSED_UPDATE_MLP and not ops.GEMM_EXACT:      # ReLU at a width the one-launch kernel below does not take
             res = self._dense_chain_f32(plans, outs, start, regime='relu_width')
+            if res is None and self in _BRANCHES_CACHE:
+                # a CIN++ layer that has been through the dispatch below: its prepared launch (ops.BranchesLaunch) without
+                # reading the networks again -- what it holds are shapes `_one_launch` never takes
+                res = self._dense_branches_f32(plans, outs, start, regime='relu_width')
             if res is not None:
                 return res
         got = self._update_chains(plans, outs, start)
@@ -1291,6 +1322,10 @@ class SparseCINConv(torch.nn.Module):
             dims = [(list(outs[nb * k: nb * (k + 1)]), [s for st in flat[nb * k: nb * (k + 1)] for s in st] + combine[k],
                      [f for fs in folds[nb * k: nb * (k + 1)] for f in fs] + [cfolds[k]]) for k in range(len(active))]
             res = self._one_launch(dims, (start, len(plans), len(outs)))
+            if res is not None:
+                return res
+        if nb > 2 and FUSED_UPDATE_MLP and not ops.GEMM_EXACT:     # three or four ReLU branches the one-launch kernel above did not take
+            res = self._dense_branches_f32(plans, outs, start, regime='relu_width')
             if res is not None:
                 return res
         hs, dev = list(outs), outs[0].device
@@ -1353,7 +1388,8 @@ class SparseCINConv(torch.nn.Module):
         networks only).  In the 'act' regime a dimension whose message has no fused stream (plans[d] is None) runs its
         generic propagate first and joins the same launch, as in `_dense_f64`.  Inference only.  The launch is prepared
         once per layer (ops.ChainLaunch in _CHAIN_CACHE): per call only the rows are looked at.
-        None when it does not apply -- the regime is off, a recording autograd, CIN++, float64 or CPU features, LayerNorm or
+        None when it does not apply -- the regime is off, a recording autograd, CIN++ (three or four branches:
+        `CINppConv._dense_branches_f32`, a switch of its own), float64 or CPU features, LayerNorm or
         a training-mode BatchNorm, a passed-in network, a width above 128, more than 4 dimensions, ReLU at 64 / 128 --
         and the caller goes on as before."""
         if not _chain_f32_on(regime) or torch.is_grad_enabled() or type(self) is not SparseCINConv:
@@ -1422,6 +1458,10 @@ class SparseCINConv(torch.nn.Module):
                     norms.append(m)
                     sources += [m.weight, m.bias, m.running_mean, m.running_var, m.num_batches_tracked]
         return ops.ChainLaunch(dims, sources), norms
+
+    def _dense_branches_f32(self, plans, outs, start: int = 0, cochain_params=None, regime: str = 'act') -> Optional[List[Tensor]]:
+        """Hook of `_dense_eval` and `forward`: the three or four branches of a CIN++ layer in one launch (CINppConv), or None."""
+        return None
 
     def _dense_f64(self, plans, outs, start: int = 0, cochain_params=None) -> Optional[List[Tensor]]:
         """The update / combine networks of ALL dimensions of a float64 layer in ONE launch (ops.update_chain_f64,
@@ -1532,6 +1572,8 @@ class SparseCINConv(torch.nn.Module):
         dense = self._dense_eval(plans, outs, start_to_process)
         if dense is None:
             dense = self._dense_chain_f32(plans, outs, start_to_process, cochain_params)
+        if dense is None:
+            dense = self._dense_branches_f32(plans, outs, start_to_process, cochain_params)
         if dense is None:
             dense = self._dense_f64(plans, outs, start_to_process, cochain_params)
         if dense is None:
@@ -1694,8 +1736,9 @@ class CINppCochainConv(SparseCINCochainConv):
             return self.forward_unfused(cochain)
         return self.finish(*ops.aggregate_many(sts))
 
-    def forward_unfused(self, cochain: CochainMessagePassingParams):
-        """The reference's own sequence (mp/layers.py:243-260) through propagate() and the hooks."""
+    def aggregate_unfused(self, cochain: CochainMessagePassingParams):
+        """The three or four aggregated inputs of the update networks, self terms added, through propagate() and the hooks
+        (mp/layers.py:243-254), in the order of `finish`; zeros for an absent co-boundary index."""
         kw = dict(x=cochain.x, up_attr=cochain.kwargs['up_attr'], boundary_attr=cochain.kwargs['boundary_attr'])
         down_index = cochain.down_index
         if self.feed_down_attr:
@@ -1704,16 +1747,19 @@ class CINppCochainConv(SparseCINCochainConv):
         out_up = out_up + (1 + self.eps1) * cochain.x
         out_down = out_down + (1 + self.eps2) * cochain.x
         out_boundaries = out_boundaries + (1 + self.eps3) * cochain.x
-        parts = [self.update_up_nn(out_up), self.update_down_nn(out_down), self.update_boundaries_nn(out_boundaries)]
-        if self.update_coboundaries_nn is not None:
-            cob_index = getattr(cochain, 'coboundary_index', None)
-            cob_attr = getattr(cochain, 'coboundary_attr', None)
-            if cob_index is not None and cob_attr is not None:
-                out_cob = self.propagate_coboundary(cob_index, cob_attr, cochain.x.size(0))
-            else:
-                out_cob = ops.zeros_rows(cochain.x.size(0), cochain.x.size(1), cochain.x.device, _zero_dtype(cochain.x))
-            parts.append(self.update_coboundaries_nn(out_cob + (1 + self.eps4) * cochain.x))
-        return self.combine_nn(torch.cat(parts, dim=-1))
+        if self.update_coboundaries_nn is None:
+            return out_up, out_down, out_boundaries
+        cob_index = getattr(cochain, 'coboundary_index', None)
+        cob_attr = getattr(cochain, 'coboundary_attr', None)
+        if cob_index is not None and cob_attr is not None:
+            out_cob = self.propagate_coboundary(cob_index, cob_attr, cochain.x.size(0))
+        else:
+            out_cob = ops.zeros_rows(cochain.x.size(0), cochain.x.size(1), cochain.x.device, _zero_dtype(cochain.x))
+        return out_up, out_down, out_boundaries, out_cob + (1 + self.eps4) * cochain.x
+
+    def forward_unfused(self, cochain: CochainMessagePassingParams):
+        """The reference's own sequence (mp/layers.py:243-260) through propagate() and the hooks."""
+        return self.finish(*self.aggregate_unfused(cochain))
 
 
 class CINppConv(SparseCINConv):
@@ -1787,6 +1833,118 @@ class CINppConv(SparseCINConv):
         activations between the seven Linear layers stay in LDS, the combine is accumulated branch by branch."""
         mdims = [ops.Mlp3Dim(xs=xs, linears=[lin for lin, _ in stages], folds=fs) for xs, stages, fs in dims]
         return ops.update_mlp3(mdims) if ops.update_mlp3_applies(mdims) else None
+
+    @staticmethod
+    def _branch_net(lvl, wmax: int):
+        """(weights, biases, folds, activation) of one dimension's three or four update networks and its combine in the order
+        of ops.BranchDim, or None when they are not the stock Linear-norm-act structure with one of the five activations and
+        Identity / eval-mode BatchNorm norms, are not float32, or are wider than `wmax`."""
+        if type(lvl) is not CINppCochainConv:
+            return None
+        nets = [lvl.update_up_nn, lvl.update_down_nn, lvl.update_boundaries_nn]
+        if lvl.update_coboundaries_nn is not None:
+            nets.append(lvl.update_coboundaries_nn)
+        got = [_f64_stages(net, 2) for net in nets] + [_f64_stages(lvl.combine_nn, 1)]
+        if any(g is None for g in got) or len({g[1] for g in got}) != 1:
+            return None
+        stages = [st for g in got for st in g[0]]
+        if (any(lin.weight.dtype != torch.float32 or lin.out_features > wmax for lin, _ in stages)
+                or any(g[0][0][0].in_features > wmax for g in got[:-1])):
+            return None
+        folds = [_fold_norm(norm, lin.out_features) for lin, norm in stages]
+        if any(f is None for f in folds):
+            return None                  # LayerNorm, a training-mode BatchNorm
+        return [lin.weight for lin, _ in stages], [lin.bias for lin, _ in stages], folds, got[0][1]
+
+    def _dense_branches_f32(self, plans, outs, start: int = 0, cochain_params=None, regime: str = 'act') -> Optional[List[Tensor]]:
+        """The three or four update networks and the combine of ALL dimensions of a float32 CIN++ layer in ONE launch
+        (ops.update_branches_f32, csrc/cwn_branches_f32.hip) in one of the regimes of FUSED_BRANCHES_F32: 'relu_width' -- ReLU
+        networks that cwn_update_mlp3_f32 does not take (asked by `_dense_eval` behind `_one_launch` and in front of its
+        grouped launches) -- or 'act' -- networks with elu / tanh / sigmoid / id at any width up to 128 (asked by `forward`
+        behind `_dense_eval`, which reads ReLU networks only).  The parallel of `SparseCINConv._dense_chain_f32`: in the 'act'
+        regime a dimension whose message has no fused stream (plans[d] is None) runs its generic propagate first and joins
+        the same launch; the three outputs of the blocked propagate are taken as they come, [up, down, boundaries].  Inference
+        only.  The launch is prepared once per layer (ops.BranchesLaunch in _BRANCHES_CACHE): per call only the rows are
+        looked at.
+        None when it does not apply -- the regime is off, a recording autograd, float64 or CPU features, LayerNorm or a
+        training-mode BatchNorm, a passed-in network of another form, a width above 128, more than 4 dimensions, an unfused
+        dimension under a static batch, ReLU in the shapes of cwn_update_mlp3_f32 -- and the caller goes on as before.
+        Out of scope: float64 (the torch modules), training, the compiled binding; the message products of
+        `feed_down_attr` are upstream of this launch and unchanged."""
+        if not _branches_f32_on(regime) or torch.is_grad_enabled() or type(self) is not CINppConv:
+            return None
+        active = list(range(start, len(plans)))
+        unfused = [d for d in active if plans[d] is None]
+        if not active or len(active) > ops._ffi.BRANCHES_F32_MAX_DIMS:
+            return None
+        if len(outs) != sum(self._n_streams(plans[d]) for d in active if plans[d] is not None):
+            return None
+        if unfused and (regime != 'act' or cochain_params is None or _ffi_dyn()):
+            return None                  # (a static batch: the generic propagate is not part of its captured graph)
+        feats = list(outs) + [cochain_params[d].x for d in unfused]
+        if any(not isinstance(t, Tensor) or t.dtype != torch.float32 or not t.is_cuda for t in feats):
+            return None
+        key = (start, len(plans))
+        ents = _BRANCHES_CACHE.get(self)
+        if ents is None:
+            _BRANCHES_CACHE[self] = ents = {}
+        ent = ents.get(regime)
+        if ent is not None and (ent[1] != key or ent[3] != ops.STRUCT_EPOCH or (ent[0] is not None and not ent[0].current())):
+            ent = None
+        if ent is None:
+            got = self._branches_f32_launch(active, regime)
+            if got is None and any(isinstance(m, BN) and m.training for d in active for m in self.mp_levels[d].modules()):
+                return None              # (not remembered: eval() is no change of the module tree)
+            ent = ents[regime] = (None, key, [], ops.STRUCT_EPOCH) if got is None else (got[0], key, got[1], ops.STRUCT_EPOCH)
+        if ent[0] is None:
+            return None                  # (these networks have been read and are not this regime's)
+        launch, _, norms, _ = ent
+        if any(m.training for m in norms):
+            return None                  # batch statistics are no fixed affine
+        ins, k = [], 0
+        for d in active:
+            if plans[d] is None:
+                ins.append(self.mp_levels[d].aggregate_unfused(cochain_params[d]))
+            else:
+                m = self._n_streams(plans[d])
+                ins.append(tuple(outs[k:k + m]))
+                k += m
+        res = launch.run(ins)
+        if res is None and unfused:      # (an input of another width than its network: let torch say so)
+            return [self.mp_levels[d].finish(*xs) for d, xs in zip(active, ins)]
+        return res
+
+    def _branches_f32_launch(self, active, regime: str):
+        """(ops.BranchesLaunch, BatchNorm modules) of the networks of the dimensions `active` when they are `regime`'s, or
+        None: 'relu_width' -- all ReLU and not the shapes of cwn_update_mlp3_f32 (three branches, (F, F) first layers, one
+        width of 64 or 128 for every dimension); 'act' -- none of them ReLU."""
+        nets = [self._branch_net(self.mp_levels[d], ops._ffi.BRANCHES_F32_MAX_WIDTH) for d in active]
+        if any(net is None for net in nets):
+            return None
+        relu = [net[3] == 'relu' for net in nets]
+        if any(relu) != (regime == 'relu_width') or len(set(relu)) != 1:
+            return None
+        shapes = {tuple(net[0][0].shape) + (len(net[0]),) for net in nets}
+        if regime == 'relu_width' and shapes in ({(64, 64, 7)}, {(128, 128, 7)}):
+            return None                  # cwn_update_mlp3_f32's, whatever makes that launch decline
+        dims = []
+        for net in nets:
+            nb = (len(net[0]) - 1) // 2
+            x = net[0][0].new_empty(0, net[0][0].size(1))
+            dims.append(ops.BranchDim(ins=[x] * nb, weights=net[0], biases=net[1], folds=net[2], act=net[3]))
+        if not ops.update_branches_f32_applies(dims):
+            return None
+        sources, norms = [], []
+        for d in active:
+            lvl = self.mp_levels[d]
+            nns = [lvl.update_up_nn, lvl.update_down_nn, lvl.update_boundaries_nn, lvl.update_coboundaries_nn or [], lvl.combine_nn]
+            for m in [m for nn in nns for m in nn]:
+                if isinstance(m, Linear):
+                    sources += [m.weight, m.bias]
+                elif isinstance(m, BN):
+                    norms.append(m)
+                    sources += [m.weight, m.bias, m.running_mean, m.running_var, m.num_batches_tracked]
+        return ops.BranchesLaunch(dims, sources), norms
 
     def _dense_train(self, plans, outs, start: int = 0) -> Optional[List[Tensor]]:
         """Training mode: the update networks of EVERY stream and dimension (three or four chains of Linear ->

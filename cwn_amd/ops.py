@@ -2798,6 +2798,175 @@ class ChainLaunch:
 
 
 # ------------------------------------------------------------------------------------------------
+# The float32 update branches (csrc/cwn_branches_f32.hip): the three or four update networks and the combine of a CIN++
+# layer in float32 at any width up to 128, inference only
+# ------------------------------------------------------------------------------------------------
+# an operand of the float32 branches kernel
+_F32_BRANCH_ROWS = dict(dtypes=(torch.float32,), rows_got=True,
+                        hint='this kernel computes in fp32 only (a float64 CIN++ layer keeps the torch modules)')
+
+
+@dataclass
+class BranchDim:
+    """One dimension of `update_branches_f32`: the nb = 3 or 4 aggregated inputs [n, F] (self terms added) in the order of
+    torch.cat in mp/layers.py:255-260 -- up, down, boundaries, then the co-boundary branch; the weights and biases of the
+    2 nb + 1 Linear layers -- branch by branch its two, then combine_nn[0] [H, nb H]; per stage a (scale, shift) pair of [H]
+    tensors, either of them None (layers._fold_norm); the activation of all stages.  `out`: an output buffer [>= n, H] of
+    the caller's (only its first n rows are written), or None."""
+    ins: Sequence[Tensor]
+    weights: Sequence[Tensor]
+    biases: Sequence[Optional[Tensor]]
+    folds: Sequence[Tuple[Optional[Tensor], Optional[Tensor]]]
+    act: object = 'relu'
+    out: Optional[Tensor] = None
+
+
+def _branch_shapes(d: BranchDim) -> Optional[Tuple[int, int, int, int]]:
+    """(n, F, H, nb) when the shapes of `d` are those of a CINppConv dimension, else None."""
+    nb = len(d.ins)
+    if not _ffi.BRANCHES_F32_MIN_BRANCHES <= nb <= _ffi.BRANCHES_F32_MAX_BRANCHES:
+        return None
+    stages = 2 * nb + 1
+    ts = list(d.ins) + list(d.weights)
+    if (len(d.weights) != stages or len(d.biases) != stages or len(d.folds) != stages
+            or not all(isinstance(t, Tensor) and t.dim() == 2 for t in ts)):
+        return None
+    n, F = int(d.ins[0].size(0)), int(d.ins[0].size(1))
+    H = int(d.weights[0].size(0))
+    want = [(H, F), (H, H)] * nb + [(H, nb * H)]
+    if any(tuple(x.shape) != (n, F) for x in d.ins) or [tuple(w.shape) for w in d.weights] != want:
+        return None
+    if any(len(f) != 2 for f in d.folds):
+        return None
+    vecs = list(d.biases) + [t for f in d.folds for t in f]
+    if any(t is not None and tuple(t.shape) != (H,) for t in vecs):
+        return None
+    if d.out is not None and (d.out.dim() != 2 or d.out.size(0) < n or d.out.size(1) != H):
+        return None
+    return n, F, H, nb
+
+
+def _branch_tensors(d: BranchDim) -> list:
+    return list(d.ins) + [d.out] + list(d.weights) + list(d.biases) + [t for f in d.folds for t in f]
+
+
+def update_branches_f32_applies(dims: Sequence[BranchDim]) -> bool:
+    """Does cwn_update_branches_f32 take these dimensions?  1 to 4 of them, each with 3 or 4 branches, every tensor float32 on
+    the GPU with contiguous rows (the weights contiguous), 1 <= F, H <= 128, the shapes of a CINppConv dimension, a known
+    activation."""
+    if not 1 <= len(dims) <= _ffi.BRANCHES_F32_MAX_DIMS:
+        return False
+    wmax = _ffi.BRANCHES_F32_MAX_WIDTH
+    for d in dims:
+        shp = _branch_shapes(d)
+        if shp is None or not (1 <= shp[1] <= wmax and 1 <= shp[2] <= wmax):
+            return False
+        if not all(t is None or (t.dtype == torch.float32 and t.is_cuda and _rows_contiguous(t, t.dim())) for t in _branch_tensors(d)):
+            return False
+        if not all(w.is_contiguous() for w in d.weights):
+            return False
+        if isinstance(d.act, str) and d.act not in ACT_CODES:
+            return False
+    return True
+
+
+_BRANCH_SHAPES = ('1 to 4 dimensions of 3 or 4 branches with the shapes [H, F], [H, H] per branch and [H, nb H] of the combine, '
+                  f'1 <= F, H <= {_ffi.BRANCHES_F32_MAX_WIDTH}, contiguous weights, a known activation')
+
+
+def _branch_stages(D, d: BranchDim) -> None:
+    for s in range(len(d.weights)):
+        D.W[s], D.bias[s] = d.weights[s].data_ptr(), _ffi.ptr(d.biases[s])
+        D.scale[s], D.shift[s] = _ffi.ptr(d.folds[s][0]), _ffi.ptr(d.folds[s][1])
+
+
+def update_branches_f32(dims: Sequence[BranchDim]) -> List[Tensor]:
+    """act(aff(combine_nn[0](cat(update_up_nn(in_up), update_down_nn(in_down), update_boundaries_nn(in_b)
+    [, update_coboundaries_nn(in_cob)])))) of every dimension of a CINppConv layer (mp/layers.py:255-260) in ONE float32
+    launch at any widths 1 <= F, H <= 128 and with any of the five activations (csrc/cwn_branches_f32.hip: exact-fp32
+    MFMA, the branches one after the other through LDS, the combine one accumulator over them).  Returns the outputs
+    [n, H] per dimension (`out`, when given, has its first n rows written).  Inference only: nothing is recorded for
+    autograd.  A row's result depends on that row and the weights alone.  Inside `_ffi.dynamic_rows` a row count that is a
+    capacity is read from the device (include/cwn_hip.h, "Conventions").  ctypes only: the compiled binding does not carry
+    this launch.  Anything but float32 GPU tensors is a TypeError, shapes the launch does not take
+    (`update_branches_f32_applies`) a ValueError."""
+    descs, outs, dev = [], [], None
+    for i, d in enumerate(dims):
+        named = [(f'ins[{k}]', x, 2) for k, x in enumerate(d.ins)] + [(f'weights[{s}]', w, 2) for s, w in enumerate(d.weights)] + \
+                [(f'biases[{s}]', b, 1) for s, b in enumerate(d.biases)] + \
+                [(f'folds[{s}]', t, 1) for s, f in enumerate(d.folds) for t in f] + [('out', d.out, 2)]
+        for name, t, dim in named:
+            _rows_operand(t, f'dims[{i}].{name}', dim, **_F32_BRANCH_ROWS)
+    if not update_branches_f32_applies(dims):
+        raise ValueError('update_branches_f32: ' + _BRANCH_SHAPES)
+    for d in dims:
+        n, F, H, nb = _branch_shapes(d)
+        dev = d.ins[0].device
+        out = torch.empty(n, H, dtype=torch.float32, device=dev) if d.out is None else d.out[:n]
+        outs.append(out)
+        D = _ffi.BranchesDescF32(out=out.data_ptr(), n=n, ld_out=H if d.out is None else ld(d.out, H), F=F, H=H,
+                                 act=_act_code(d.act), nb=nb)
+        for k, x in enumerate(d.ins):
+            D.ins[k], D.ld_in[k] = x.data_ptr(), ld(x)
+        _branch_stages(D, d)
+        descs.append(D)
+    _ffi._set_dyn(descs, 'n')
+    _ffi.check(_ffi.lib().cwn_update_branches_f32((_ffi.BranchesDescF32 * len(descs))(*descs), len(descs), _ffi.stream_ptr(dev)),
+               'cwn_update_branches_f32')
+    return outs
+
+
+class BranchesLaunch:
+    """A prepared cwn_update_branches_f32 call for one layer, as ChainLaunch is for cwn_update_chain_f32: the weights, biases,
+    folds and activation of `dims` -- which `update_branches_f32` has taken -- filled in once; `run` fills in the rows of
+    this call and launches.  `sources`: every tensor the record was derived from (Linear weights and biases, the BatchNorm
+    tensors behind the folds); `current()` is false as soon as one of them was written in place or moved, the module tree
+    changed (STRUCT_EPOCH), or a raw-pointer writer ran (STATE_EPOCH)."""
+
+    def __init__(self, dims: Sequence[BranchDim], sources: Sequence[Tensor]):
+        self.n = len(dims)
+        self.dev = dims[0].ins[0].device
+        self.arr = (_ffi.BranchesDescF32 * self.n)()
+        self.shapes = []
+        self.keep = [(d.weights, d.biases, d.folds) for d in dims]
+        for D, d in zip(self.arr, dims):
+            _, F, H, nb = _branch_shapes(d)
+            self.shapes.append((F, H, nb))
+            D.F, D.H, D.ld_out, D.act, D.nb = F, H, H, _act_code(d.act), nb
+            _branch_stages(D, d)
+        self.marks = _marks(sources)
+        self.epochs = (STATE_EPOCH, STRUCT_EPOCH)
+        self.fn = _ffi.lib().cwn_update_branches_f32
+
+    def current(self) -> bool:
+        return self.epochs == (STATE_EPOCH, STRUCT_EPOCH) and _marks_current(self.marks)
+
+    def run(self, ins: Sequence[Sequence[Tensor]]) -> Optional[List[Tensor]]:
+        """None: these inputs are not what the launch takes (another branch count / width / dtype / device, rows that are not
+        contiguous) -- the caller then goes the long way, which says what is wrong."""
+        if len(ins) != self.n:
+            return None
+        outs = []
+        for D, xs, (F, H, nb) in zip(self.arr, ins, self.shapes):
+            if len(xs) != nb:
+                return None
+            n = xs[0].size(0) if xs[0].dim() == 2 else -1
+            for k, x in enumerate(xs):
+                if (x.dim() != 2 or x.size(0) != n or x.size(1) != F or x.dtype != torch.float32 or x.device != self.dev
+                        or not is_rowmajor(x)):
+                    return None
+                D.ins[k], D.ld_in[k] = x.data_ptr(), ld(x)
+            out = torch.empty(n, H, dtype=torch.float32, device=self.dev)
+            outs.append(out)
+            D.out, D.n = out.data_ptr(), n
+            D.m_dev = _ffi.dyn(n)
+        rc = self.fn(self.arr, self.n, _ffi.stream_ptr(self.dev))
+        if rc != 0:
+            _ffi.check(rc, 'cwn_update_branches_f32')
+        return outs
+
+
+# ------------------------------------------------------------------------------------------------
 # The message-passing-agnostic baseline (csrc/cwn_agnostic.hip): embed + activate + pool, and the head, inference only
 # ------------------------------------------------------------------------------------------------
 def _agnostic_dtype(named, what: str) -> torch.dtype:

@@ -30,7 +30,7 @@
  *     names the one it uses where it reads the count (a few kernels write the reader's expression out, and say so there;
  *     cwn_linear_stats.hip still has its own copy of the clamp).
  *     cwn::rows_clamped -- the count clamped to [0, capacity]: cwn_gemm_f32 (both kernels), cwn_linear_stats_f32,
- *     cwn_linear_wide_f32, cwn_update_chain_f32, cwn_target_head_f32 / _bwd_f32, cwn_csr_build (e_dev), cwn_csr_long_rows
+ *     cwn_linear_wide_f32, cwn_update_chain_f32, cwn_update_branches_f32, cwn_target_head_f32 / _bwd_f32, cwn_csr_build (e_dev), cwn_csr_long_rows
  *     and the cochain count of cwn_flow_head_dev_f32 / _bwd_dev_f32.  cwn::rows_capped -- the count capped ABOVE only (a
  *     larger count behaves as the capacity; a negative one bounds loops that run upwards from 0, so nothing is stored):
  *     cwn_gemm_tn_f32, cwn_layernorm_*, cwn_dropout_f32, cwn_loss_f32 / cwn_loss_cols_f32, cwn_embedding_bwd_f32,
@@ -1493,6 +1493,70 @@ typedef struct cwn_chain_desc_f32 {
     const int64_t* m_dev;      /* or NULL: rows that exist (n = capacity) */
 } cwn_chain_desc_f32;
 int cwn_update_chain_f32(const cwn_chain_desc_f32* descs_host, int n, cwn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The float32 update branches (csrc/cwn_branches_f32.hip): the update and combine networks of a CINppConv layer
+ * (mp/layers.py:255-260) in float32, inference only -- three or four two-stage branches and the nb*H-wide combine -- at ANY
+ * width 1 .. 128 and with any of the five activations, all dimensions of a layer in ONE launch.  Additive to ABI 24.
+ *
+ * cwn_update_mlp3_f32 is the fast form of this arithmetic at 64 / 128 with ReLU, three branches and an (F, F) first layer
+ * (a bf16 split on packed weights).  This launch is the one for everything else: hidden 48 of cin++-zinc-small.sh /
+ * cin++-molhiv-small.sh, a first layer over raw features, the 16 / 32 of a TU grid, four branches (the co-boundary stream)
+ * at any width, a model built with elu / tanh / sigmoid / id.
+ *
+ *     h_k = act(aff(act(aff(ins[k] W[2k]^T + bias[2k])) W[2k+1]^T + bias[2k+1]))     k = 0 .. nb-1     aff_i(z) = z * scale[i] + shift[i]
+ *     out = act(aff(cat(h_0 .. h_{nb-1}) W[2nb]^T + bias[2nb]))
+ *
+ *   - the branch order is that of torch.cat in mp/layers.py:255-260: up, down, boundaries, then the co-boundary branch
+ *     when nb == 4.  Stage 2k, 2k + 1: the two Linear layers of branch k; stage 2nb: the combine.  Stages beyond 2nb are
+ *     not looked at.
+ *   - ins[k] [n, F] with row stride ld_in[k] >= F; W[2k] [H, F], W[2k+1] [H, H], W[2nb] [H, nb*H], each row-major and
+ *     contiguous as torch.nn.Linear holds them; bias[i] / scale[i] / shift[i] [H], each NULL-able on its own (an absent
+ *     operand is skipped, not multiplied by one); act: one CWN_ACT_* code for all stages; out [n, H] with row stride
+ *     ld_out >= H.  out must not overlap an input or a weight (the caller vouches: not checked).
+ *   - OPERAND WINDOWS: inputs and out are read / written over their [n, width] window only; 16-byte loads and stores only
+ *     where pointer and stride allow, scalar ones otherwise.
+ *   - CWN_BRANCHES_F32_MIN_BRANCHES <= nb <= CWN_BRANCHES_F32_MAX_BRANCHES; 1 <= F, H <= CWN_BRANCHES_F32_MAX_WIDTH, any
+ *     value; 1 <= n_dims <= CWN_BRANCHES_F32_MAX_DIMS, nb may differ between the dimensions of a launch; a dimension with
+ *     n == 0 takes no workgroup and none of its pointers is looked at.
+ *   - a workgroup of 256 threads owns CWN_BRANCHES_F32_TM rows of one dimension; the tiles of all dimensions form one grid.
+ *     The branches run one after the other through two LDS panels of 32 x 132 floats (LDS does not grow with nb); the
+ *     combine is ONE accumulator in registers, continued over the branches: branch ascending, k ascending within a branch.
+ *   - arithmetic: as cwn_update_chain_f32 -- v_mfma_f32_16x16x4_f32, exact fp32, non-finite inputs propagate as in torch.
+ *     An output element is one chain of products whose k order depends on (F, H, nb) alone: a row has the same bits alone
+ *     or anywhere in any batch, in any dimension slot of the launch.
+ *   - m_dev: DEVICE-SIDE ROW COUNTS (n is the capacity); the count is CLAMPED to [0, n] (cwn::rows_clamped).  Rows in
+ *     [*m_dev, n) are never written and their rows of ins[k] are never read; a count of 0 writes nothing.
+ *   - no allocation, no synchronisation, no atomics.
+ * CWN_ERR_BAD_ARG: descs NULL, n_dims outside the range, n < 0, F or H outside [1, 128], an unknown act, nb outside [3, 4],
+ * and for n > 0 a NULL ins[k] / out / W[i] or a stride below its width.  CWN_ERR_ALIGN (n > 0): a pointer off 4 bytes
+ * (m_dev: 8).  CWN_ERR_TOO_LARGE: INT32_MAX tiles or more.  All checks precede the first HIP call.
+ * Not here: training (no backward), float64 (the torch modules), LayerNorm, widths above 128, the compiled torch binding
+ * (ctypes only); the message products of feed_down_attr are upstream of this launch.
+ * ------------------------------------------------------------------------------------------ */
+#define CWN_BRANCHES_F32_MAX_DIMS 4        /* dimensions of one cwn_update_branches_f32 launch */
+#define CWN_BRANCHES_F32_MAX_WIDTH 128     /* F and H of a dimension */
+#define CWN_BRANCHES_F32_TM 32             /* rows a workgroup owns */
+#define CWN_BRANCHES_F32_MIN_BRANCHES 3
+#define CWN_BRANCHES_F32_MAX_BRANCHES 4
+#define CWN_BRANCHES_F32_STAGES 9          /* 2 * MAX_BRANCHES + 1 */
+
+typedef struct cwn_branches_desc_f32 {
+    const float* ins[CWN_BRANCHES_F32_MAX_BRANCHES];     /* [n, F] each, row stride ld_in[k]; ins[3] unused when nb == 3 */
+    float* out;                                          /* [n, H] row stride ld_out */
+    const float* W[CWN_BRANCHES_F32_STAGES];
+    const float* bias[CWN_BRANCHES_F32_STAGES];          /* [H] or NULL, each */
+    const float* scale[CWN_BRANCHES_F32_STAGES];
+    const float* shift[CWN_BRANCHES_F32_STAGES];
+    int64_t n;
+    int64_t ld_in[CWN_BRANCHES_F32_MAX_BRANCHES];
+    int64_t ld_out;
+    int32_t F, H;
+    int32_t act;               /* CWN_ACT_*, the one activation of all stages */
+    int32_t nb;                /* branches: 3 or 4 */
+    const int64_t* m_dev;      /* or NULL: rows that exist (n = capacity) */
+} cwn_branches_desc_f32;
+int cwn_update_branches_f32(const cwn_branches_desc_f32* descs_host, int n_dims, cwn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * The activated two-operand message (csrc/cwn_aggregate_act.hip), float32 and float64, inference:
