@@ -96,6 +96,19 @@ class _CollatedAdjacency(csr.Adjacency):
         return []
 
 
+class _SlotAdjacency(csr.Adjacency):
+    """An upper / lower adjacency of a slot in mode 'csr': a plan over the slot's CAPACITY-sized entries, built with the address
+    of the slot's live entry count (`e_dev_ptr`).  Its transposes read the same entries and carry the same address, whoever
+    asks for them first -- the fill of a training step, or an autograd backward outside one (ops.aggregate_many), which
+    would otherwise build them over the entries that earlier batches left behind the live ones."""
+
+    def transposes(self):
+        todo = super().transposes()
+        for t in todo:
+            t.e_dev_ptr = self.e_dev_ptr
+        return todo
+
+
 class StaticBlockPlan:
     """The BlockPlan (cwn_amd/blockplan.py) of one slot of a static batch: item tables in fixed device buffers, rebuilt by the
     device builders after every fill.  Duck-types what the layer / model code asks a BlockPlan."""
@@ -398,9 +411,12 @@ class StaticBatch:
                                                 bufs[(d, 'bt_col')])
                 if self.mode == 'csr':
                     # the TRANSPOSE has hub rows on REDDIT-like complexes (a vertex of degree 300 is the boundary of 300 edges):
-                    # its long-row lists, which the collate does not bring, are written by the fill (cwn_csr_long_rows) when a
-                    # training step reads this plan -- without them the streaming backward walked every hub row with one lane
-                    # group (round 6: 54 against 37 us per backward aggregation launch)
+                    # its long-row lists, which the collate does not bring, are written by EVERY fill (cwn_csr_long_rows) --
+                    # without them the streaming backward walked every hub row with one lane group (round 6: 54 against 37 us
+                    # per backward aggregation launch).  Every fill, not only a training step's: handed a list, the aggregate
+                    # leaves every row above CWN_LONG_ROW to it, so a list that the current fill had not written dropped the
+                    # hub rows -- of the inference forward of a co-boundary stream (which reads this plan), of an autograd
+                    # backward outside a training step.  (Before the first fill: no entries, no long rows, empty lists.)
                     t = adj._t_src
                     t.long_rows = torch.zeros(csr.LONG_PARTS, t.long_cap, dtype=torch.int32, device=bi.device)
                     t.n_long = torch.zeros(csr.LONG_PARTS, dtype=torch.int32, device=bi.device)
@@ -410,7 +426,7 @@ class StaticBatch:
             if cb.upper_index is not None and d + 1 < D:
                 ui = cb.upper_index
                 if self.mode == 'csr':
-                    adj = csr.Adjacency(ui[1], ui[0], self.cap_cells[d], self.cap_cells[d], cb.shared_coboundaries, self.cap_cells[d + 1])
+                    adj = _SlotAdjacency(ui[1], ui[0], self.cap_cells[d], self.cap_cells[d], cb.shared_coboundaries, self.cap_cells[d + 1])
                     adj.e_dev_ptr = self.size_ptr(8 + self.k_of(d, 'upper_index'), j)       # the slot's live entry count
                     self._slot_adjs.setdefault(j, []).append(adj)
                     self._register(ui, adj)
@@ -419,7 +435,7 @@ class StaticBatch:
                                                           self.cap_cells[d + 1]))
             if self.mode == 'csr' and d > 0 and getattr(cb, 'lower_index', None) is not None:
                 li = cb.lower_index
-                adj = csr.Adjacency(li[1], li[0], self.cap_cells[d], self.cap_cells[d], cb.shared_boundaries, self.cap_cells[d - 1])
+                adj = _SlotAdjacency(li[1], li[0], self.cap_cells[d], self.cap_cells[d], cb.shared_boundaries, self.cap_cells[d - 1])
                 adj.e_dev_ptr = self.size_ptr(8 + self.k_of(d, 'lower_index'), j)
                 self._slot_adjs.setdefault(j, []).append(adj)
                 self._register(li, adj)
@@ -767,26 +783,27 @@ class StaticBatch:
             # the CSR plans of the upper / lower adjacencies (and, for a training step, their transposes) of ALL slots in
             # batched cwn_csr_build calls (<= 8 plans each: one launch sequence per eight plans, not per slot) over the
             # capacity-sized entries, every plan with the address of ITS slot's live entry count (cwn_csr_desc.e_dev)
+            # (a transpose that exists -- made by an earlier fill, or by a backward outside a training step -- is rebuilt with
+            #  its plan: it describes the entries the slot holds NOW; one that nobody has asked for is built on demand)
             todo = []
             for j in range(n):
                 for adj in self._slot_adjs.get(j, []):
                     todo.append(adj)
                     if self.build_backward:
                         adj.transposes()
-                        for t in (adj._t_src, adj._t_aux):
-                            if t is not None:
-                                t.e_dev_ptr = adj.e_dev_ptr
-                                todo.append(t)
+                    todo += [t for t in (adj._t_src, adj._t_aux) if t is not None]
             if todo:
                 csr.build_many(todo, validate=False, force=True)
-            if self.build_backward:
-                lists = [t for j in range(n) for t in self._slot_long.get(j, [])]
-                for i in range(0, len(lists), _ffi.CSR_MAX_DESCS):
-                    chunk = lists[i:i + _ffi.CSR_MAX_DESCS]
-                    arr = (_ffi.LongRowsDesc * len(chunk))(*[
-                        _ffi.LongRowsDesc(rowptr=t.rowptr.data_ptr(), n_rows=t.n_dst, m_dev=t.rows_dev_ptr, long_rows=t.long_rows.data_ptr(),
-                                          n_long=t.n_long.data_ptr(), long_cap=t.long_cap) for t in chunk])
-                    _ffi.check(L.cwn_csr_long_rows(arr, len(chunk), s), 'cwn_csr_long_rows')
+            # the long-row lists of the collated transposed boundary plans, whoever reads them after this fill (a training
+            # step's backward, an inference forward's co-boundary stream, an autograd backward outside a training step): the
+            # plans carry the lists, so every fill writes them for the row pointers it has just written
+            lists = [t for j in range(n) for t in self._slot_long.get(j, [])]
+            for i in range(0, len(lists), _ffi.CSR_MAX_DESCS):
+                chunk = lists[i:i + _ffi.CSR_MAX_DESCS]
+                arr = (_ffi.LongRowsDesc * len(chunk))(*[
+                    _ffi.LongRowsDesc(rowptr=t.rowptr.data_ptr(), n_rows=t.n_dst, m_dev=t.rows_dev_ptr, long_rows=t.long_rows.data_ptr(),
+                                      n_long=t.n_long.data_ptr(), long_cap=t.long_cap) for t in chunk])
+                _ffi.check(L.cwn_csr_long_rows(arr, len(chunk), s), 'cwn_csr_long_rows')
 
     # ---- the reference tables (tests) -----------------------------------------------------------------------------------
     def host_tables(self, idx: Sequence[int]) -> np.ndarray:

@@ -149,7 +149,11 @@ int cwn_csr_build(const cwn_csr_desc* descs_host, int n, void* workspace, size_t
  * the transpose of a REDDIT-like boundary has hub rows (a vertex of degree 300 is the boundary of 300 edges) that
  * cwn_aggregate_f32 then walked with one lane group each: its backward launch 54 against 37 us.  One workgroup per structure:
  * rows r < *m_dev (or n_rows) with rowptr[r + 1] - rowptr[r] > CWN_LONG_ROW go to sub-list 0 of long_rows, n_long[0] = their
- * number, n_long[1 ..] = 0; more than long_cap of them: the first long_cap (the others are walked the slow way). */
+ * number, n_long[1 ..] = 0.  The caller sizes long_cap to hold them ALL (E / CWN_LONG_ROW + 1 always does): with more than
+ * long_cap of them only the first long_cap are listed, and the others are computed by NOBODY -- cwn_aggregate_f32 / _f64,
+ * handed a list, leaves every row above CWN_LONG_ROW to it, so a long row that is not listed keeps whatever its row of `out`
+ * held.  For the same reason a list is handed to the aggregate only after this launch (or cwn_csr_build) has written it for
+ * the row pointers the aggregate reads; without one (NULL) every row is walked by its own lane group. */
 typedef struct cwn_long_rows_desc {
     const int32_t* rowptr;   /* [n_rows + 1] */
     int64_t n_rows;          /* capacity */
