@@ -31,7 +31,7 @@ EXPORTS = ('cwn_abi_version', 'cwn_error_string', 'cwn_target_arch', 'cwn_csr_wo
            'cwn_flow_head_dev_f32', 'cwn_flow_head_bwd_dev_f32', 'cwn_table_advance',
            'cwn_linear_many_f64', 'cwn_update_chain_f64', 'cwn_update_chain_f32', 'cwn_update_branches_f32', 'cwn_linear_stats_f32',
            'cwn_linear_wide_f32',
-           'cwn_aggregate_act_f32', 'cwn_aggregate_act_f64',
+           'cwn_aggregate_act_f32', 'cwn_aggregate_act_f64', 'cwn_aggregate_act_bwd_f32', 'cwn_aggregate_act_bwd_f64',
            'cwn_embed_pool_f32', 'cwn_embed_pool_f64', 'cwn_agnostic_head_f32', 'cwn_agnostic_head_f64',
            'cwn_gin_layer_f32', 'cwn_gine_layer_f32',
            'cwn_gemm_tn_f32', 'cwn_gemm_tn_workspace_bytes', 'cwn_gemm_tn_would_split', 'cwn_adam_f32', 'cwn_adam_dev_f32', 'cwn_loss_f32', 'cwn_loss_cols_f32', 'cwn_embedding_fwd_f32', 'cwn_embedding_bwd_f32', 'cwn_embed_front_f32', 'cwn_head_f32', 'cwn_head_bwd_f32', 'cwn_head_pool_floats', 'cwn_lift_create', 'cwn_lift_size', 'cwn_lift_copy', 'cwn_lift_destroy',
@@ -73,6 +73,18 @@ class AggActDesc(C.Structure):
 
 
 AggActDescF64 = AggActDesc
+
+
+class AggActBwdDesc(C.Structure):
+    """cwn_agg_act_bwd_desc and cwn_agg_act_bwd_desc_f64 (include/cwn_hip.h): one layout, every data pointer is a void*."""
+    _fields_ = [('rowptr', C.c_void_p), ('ig', C.c_void_p), ('iq', C.c_void_p),
+                ('g', C.c_void_p), ('P', C.c_void_p), ('Q', C.c_void_p), ('out', C.c_void_p),
+                ('long_rows', C.c_void_p), ('n_long', C.c_void_p),
+                ('n_dst', C.c_int64), ('F', C.c_int32), ('act', C.c_int32),
+                ('long_cap', C.c_int32), ('flags', C.c_int32)]
+
+
+AggActBwdDescF64 = AggActBwdDesc
 
 # = CWN_EMBED_POOL_MAX_K, CWN_AGNOSTIC_MAX_WIDTH, CWN_EMBED_POOL_CHUNK (csrc/cwn_agnostic.hip)
 EMBED_POOL_MAX_K, AGNOSTIC_MAX_WIDTH, EMBED_POOL_CHUNK = 128, 1024, 16
@@ -601,6 +613,10 @@ def lib():
     L.cwn_aggregate_act_f32.argtypes = [C.POINTER(AggActDesc), C.c_int, C.c_void_p]
     L.cwn_aggregate_act_f64.restype = C.c_int
     L.cwn_aggregate_act_f64.argtypes = [C.POINTER(AggActDescF64), C.c_int, C.c_void_p]
+    L.cwn_aggregate_act_bwd_f32.restype = C.c_int
+    L.cwn_aggregate_act_bwd_f32.argtypes = [C.POINTER(AggActBwdDesc), C.c_int, C.c_void_p]
+    L.cwn_aggregate_act_bwd_f64.restype = C.c_int
+    L.cwn_aggregate_act_bwd_f64.argtypes = [C.POINTER(AggActBwdDescF64), C.c_int, C.c_void_p]
     for fn in (L.cwn_embed_pool_f32, L.cwn_embed_pool_f64):
         fn.restype = C.c_int
         fn.argtypes = [C.POINTER(EmbedPoolDesc), C.c_int, C.c_void_p]
@@ -801,6 +817,18 @@ def aggregate_act(descs: Sequence[AggActDesc], device, dtype: torch.dtype = torc
     for i in range(0, len(descs), MAX_DESCS):
         chunk = descs[i:i + MAX_DESCS]
         arr = (AggActDesc * len(chunk))(*chunk)
+        check(fn(arr, len(chunk), s), name)
+
+
+def aggregate_act_bwd(descs: Sequence[AggActBwdDesc], device, dtype: torch.dtype = torch.float32) -> None:
+    """The backward of the activated message (csrc/cwn_aggregate_act_bwd.hip): one kernel launch for up to MAX_DESCS
+    descriptors, more are split into several calls.  Every operand of every descriptor has the one `dtype`.  Row counts
+    are host counts, as the forward's."""
+    fn, name = typed_entry('aggregate_act_bwd', dtype)
+    s = stream_ptr(device)
+    for i in range(0, len(descs), MAX_DESCS):
+        chunk = descs[i:i + MAX_DESCS]
+        arr = (AggActBwdDesc * len(chunk))(*chunk)
         check(fn(arr, len(chunk), s), name)
 
 

@@ -50,6 +50,30 @@ __device__ __forceinline__ real activate_rt(real z, int act) {
     }
 }
 
+// dy * act'(z) from the pre-activation z, by torch's backward formulas -- so a non-finite z or dy gives what torch gives:
+//   id       dy
+//   relu     dy unless z <= 0 (cwn_relu_bwd: a select, no product -- an infinite dy behind a closed gate is 0, not NaN)
+//   elu      z > 0 ? dy : dy * exp(z)             (alpha = 1; written so that a NaN z gives NaN, as torch's elu_backward
+//                                                  on the CPU does -- its blend keeps the exp branch unless z > 0)
+//   tanh     dy * (1 - y * y)                     y = activate<ACT>(z): the forward's bits
+//   sigmoid  dy * (y * (1 - y))
+// One text for float and double; expf / exp are picked by overload.
+__device__ __forceinline__ float cwn_exp(float z) { return expf(z); }
+__device__ __forceinline__ double cwn_exp(double z) { return exp(z); }
+
+template <int ACT, class real>
+__device__ __forceinline__ real activate_bwd(real z, real dy) {
+    if constexpr (ACT == CWN_ACT_RELU) return cwn_relu_bwd(z, dy);
+    else if constexpr (ACT == CWN_ACT_ELU) return z > real(0.0) ? dy : dy * cwn_exp(z);
+    else if constexpr (ACT == CWN_ACT_TANH) {
+        const real y = activate<ACT>(z);
+        return dy * (real(1.0) - y * y);
+    } else if constexpr (ACT == CWN_ACT_SIGMOID) {
+        const real y = activate<ACT>(z);
+        return dy * (y * (real(1.0) - y));
+    } else return dy;
+}
+
 // act'(z) as a function of out = act(z)
 __device__ __forceinline__ float act_grad(int act, float o) {
     switch (act) {

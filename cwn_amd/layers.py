@@ -113,7 +113,8 @@ def _cat_linear_act(nn) -> Optional[str]:
 
 
 # A coboundary message act(Linear(cat(x_j, up_attr))) with an activation other than ReLU as two per-cell products and one
-# cwn_aggregate_act_f32 / _f64 launch (csrc/cwn_aggregate_act.hip; inference only) instead of the generic propagate (two row
+# cwn_aggregate_act_f32 / _f64 launch (csrc/cwn_aggregate_act.hip; inference only unless ops.ACT_MESSAGE_BACKWARD is on, which
+# puts the recording autograd on the same launch and its backward on cwn_aggregate_act_bwd_f32 / _f64) instead of the generic propagate (two row
 # gathers, cat, a per-entry product, the activation, the segmented reduce).  True / False: for every dtype / for none
 # (CWN_FUSED_ACT_MESSAGE=1 / =0); a set of dtypes: for those -- the default, FUSED_ACT_MESSAGE_DEFAULT, holds the dtypes at
 # which the route has measured faster than the generic propagate by more than the run-to-run spread of both forms
@@ -768,9 +769,10 @@ class SparseCINCochainConv(CochainMessagePassing):
             return 'first'
         if _is_cat_linear_relu(self.msg_up_nn):
             return 'cat_linear_relu'
-        # the same split behind another activation: a launch without a backward and without a device-side row count, so
-        # a recording autograd and a static batch see the 'custom' network they saw before
-        if (FUSED_ACT_MESSAGE and not torch.is_grad_enabled() and not _ffi_dyn()
+        # the same split behind another activation: a launch without a device-side row count, whose backward
+        # (cwn_aggregate_act_bwd_f32 / _f64) is behind a switch of its own, so a static batch -- and, unless
+        # ops.ACT_MESSAGE_BACKWARD is on, a recording autograd -- see the 'custom' network they saw before
+        if (FUSED_ACT_MESSAGE and (ops.ACT_MESSAGE_BACKWARD or not torch.is_grad_enabled()) and not _ffi_dyn()
                 and _cat_linear_act(self.msg_up_nn) is not None and _act_message_on(self.msg_up_nn[1].weight.dtype)):
             return 'cat_linear_act'
         return 'custom'
@@ -971,9 +973,15 @@ class SparseCINConv(torch.nn.Module):
         fused = self._propagate_blocked(cochain_params, start_to_process)
         if fused is not None:
             return ['blocked'] * n, fused
+        # An activated message under a recording autograd (ops.ACT_MESSAGE_BACKWARD): its products are made by the level's
+        # own `_up_stream` (ops.gemm_many / _torch_products, differentiable) and its stream goes through ops.aggregate_many --
+        # not through the one node around the products and the aggregation, which has no backward for it, and so through
+        # neither the blocked training forward nor the deferred weight gradients, which belong to that node.
+        act_train = ops.ACT_MESSAGE_BACKWARD and torch.is_grad_enabled() and any(
+            self.mp_levels[dim]._up_kind() == 'cat_linear_act' for dim in range(start_to_process, n))
         specs, owner = [], []
         for dim in range(start_to_process, n):
-            sp = self.mp_levels[dim].gemm_specs(cochain_params[dim])
+            sp = [] if act_train else self.mp_levels[dim].gemm_specs(cochain_params[dim])
             specs += sp
             owner += [dim] * len(sp)
         plans = [None] * n

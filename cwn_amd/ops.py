@@ -206,6 +206,87 @@ def run_aggregate_act(specs: Sequence[AggActSpec], device) -> List[Tensor]:
     return [s.out for s in specs]
 
 
+# The backward of a stream with an activation (Stream.act) as descriptors of cwn_aggregate_act_bwd_f32 / _f64 over the
+# transposed plans (csrc/cwn_aggregate_act_bwd.hip): with it on, aggregate_many is differentiable for such streams and
+# layers.SparseCINCochainConv._up_kind() answers 'cat_linear_act' under a recording autograd too.  Off (the default, whatever
+# tools/bench_act_message_train.py measures: profiles/act_message_train.md) such a stream is inference only, as before.
+ACT_MESSAGE_BACKWARD = os.environ.get('CWN_ACT_MESSAGE_BACKWARD') == '1'
+
+
+@dataclass
+class AggActBwdSpec:
+    """One descriptor of cwn_aggregate_act_bwd_f32 / _f64: out[r] = sum_p g[ig[p]] * act'(P[r] + Q[iq[p]]) over the
+    transposed plan `adj` (rows = the rows of P).  `ig` / `iq` are int32 tensors in that plan's CSR order."""
+    adj: Adjacency
+    F: int
+    act: int
+    g: Tensor
+    ig: Tensor
+    P: Tensor
+    Q: Tensor
+    iq: Tensor
+    out: Optional[Tensor] = None
+
+    def desc(self) -> _ffi.AggActBwdDesc:
+        absent = self.adj.n_entries == 0
+        esize = 8 if self.g.dtype == torch.float64 else 4
+        small = ALLOW_SMALL_OPERANDS and all(t.numel() * esize < (1 << 32) for t in (self.g, self.Q))
+        return _ffi.AggActBwdDesc(
+            flags=AGG_SMALL_OPERANDS if small else 0,
+            rowptr=None if absent else self.adj.rowptr.data_ptr(),
+            ig=_ffi.ptr(self.ig), iq=_ffi.ptr(self.iq), g=_ffi.ptr(self.g), P=_ffi.ptr(self.P), Q=_ffi.ptr(self.Q),
+            out=self.out.data_ptr(),
+            long_rows=None if absent else _ffi.ptr(self.adj.long_rows),
+            n_long=None if absent else _ffi.ptr(self.adj.n_long),
+            long_cap=0 if absent else self.adj.long_cap,
+            n_dst=self.adj.n_dst, F=self.F, act=self.act)
+
+
+def run_aggregate_act_bwd(specs: Sequence[AggActBwdSpec], device) -> List[Tensor]:
+    """Raw launch of the activated message's backward: allocates missing outputs, ONE kernel per <= 8 descriptors of one
+    dtype.  Host row counts, as `run_aggregate_act`: it refuses to run under `_ffi.dynamic_rows`."""
+    if _ffi.DYN_ROWS:
+        raise _ffi.CwnError('cwn_aggregate_act_bwd_* has no device-side row count: it does not serve static batches')
+    for s in specs:
+        for name, t in (('g', s.g), ('P', s.P), ('Q', s.Q)):
+            if t.dtype != s.g.dtype or t.dtype not in _ffi.FLOAT_DTYPES or not t.is_contiguous() or t.size(1) != s.F:
+                raise TypeError(f'aggregate_act_bwd: {name} must be a contiguous float32 / float64 [*, {s.F}] matrix of the '
+                                f"stream's dtype (got {t.dtype}, {tuple(t.shape)})")
+        if s.P.size(0) != s.adj.n_dst:
+            raise ValueError(f'aggregate_act_bwd: P has {s.P.size(0)} rows, the transposed plan {s.adj.n_dst}')
+        if s.out is None:
+            s.out = torch.empty(s.adj.n_dst, s.F, dtype=s.g.dtype, device=device)
+    live = [s for s in specs if s.adj.n_dst > 0]
+    if live:
+        late = [s.adj for s in live if not s.adj.built]
+        if late:
+            from .csr import build_many
+            build_many(late)
+        wait_ready([s.adj for s in live])
+        by_dtype = {}
+        for s in live:
+            by_dtype.setdefault(s.g.dtype, []).append(s.desc())
+        for dt, descs in by_dtype.items():
+            _ffi.aggregate_act_bwd(descs, device, dt)
+    return [s.out for s in specs]
+
+
+def _act_backward_entries(act: int, z: Tensor, g: Tensor) -> Tensor:
+    """g * act'(z) entry by entry with tensor ops, by the formulas of cwn_act.h (activate_bwd): the per-ENTRY operand of
+    an activated stream ('perm' mode), which has no reduction."""
+    if act == _ffi.ACT_RELU:
+        return torch.where(z <= 0, torch.zeros_like(g), g)
+    if act == _ffi.ACT_ELU:
+        return torch.where(z > 0, g, g * torch.exp(z))
+    if act == _ffi.ACT_TANH:
+        y = torch.tanh(z)
+        return g * (1 - y * y)
+    if act == _ffi.ACT_SIGMOID:
+        y = torch.sigmoid(z)
+        return g * (y * (1 - y))
+    return g
+
+
 @dataclass
 class Stream:
     """One aggregation stream:  out = reduce_p msg(A[ia[p]], B[ib[p]])  (+ (1 + eps) * self_x).
@@ -220,7 +301,7 @@ class Stream:
     act      None, or an activation ('id' | 'relu' | 'elu' | 'tanh' | 'sigmoid', or its CWN_ACT_* code: ACT_CODES) applied
              to the message A + B: out = sum_p act(A[ia[p]] + B[ib[p]]) (+ self term).  Only with msg_op == MSG_A_PLUS_B,
              reduce == 'add' and a B as wide as A; the stream then runs on cwn_aggregate_act_f32 / _f64
-             (run_aggregate_act), inference only.
+             (run_aggregate_act); inference only unless ACT_MESSAGE_BACKWARD is on (run_aggregate_act_bwd).
     """
     adj: Optional[Adjacency]
     n_dst: int
@@ -296,6 +377,7 @@ def _aggregate_backward(streams, tensors, needs, gs, max_outs, device) -> List[O
     add kernels (48 of the ~100 framework launches of a ZINC training step)."""
     grads: List[Optional[Tensor]] = [None] * len(tensors)
     specs, slots = [], []
+    act_specs, act_slots = [], []    # streams with an activation: descriptors of the one cwn_aggregate_act_bwd_* launch
     ident = lambda t: (t.data_ptr(), tuple(t.shape), tuple(t.stride()))   # saved tensors are re-wrapped
     selfs = {}       # ident(x) -> [(slot, g, eps)] self-term contributions waiting for a host spec
     gathered = {}    # ident(x) -> index into specs of a gathered contribution to the same tensor
@@ -317,6 +399,30 @@ def _aggregate_backward(streams, tensors, needs, gs, max_outs, device) -> List[O
         if not adj.built:                       # (handed out under csr.deferred_builds, wanted after all)
             from .csr import ensure_built
             ensure_built(adj)
+        if getattr(st, 'act', None) is not None:
+            # out = sum act(A[ia] + B[ib]): g * act'(A + B) summed over the transposed plans, the pre-activation recomputed
+            # from the saved A and B -- nothing of size [E, F] is written unless an operand holds one row per ENTRY
+            code = _act_code(st.act)
+            F = g.size(1)
+            if (need_A and st.ia_mode == 'perm') or (need_B and st.ib_mode == 'perm'):
+                a_e = A if st.ia_mode == 'perm' else _ffi.gather_rows(A, adj.val)
+                b_e = B if st.ib_mode == 'perm' else _ffi.gather_rows(B, adj.aux_index)
+                g_e = _act_backward_entries(code, a_e + b_e, _ffi.gather_rows(g, adj.key))
+                if need_A and st.ia_mode == 'perm':
+                    grads[4 * k] = g_e
+                if need_B and st.ib_mode == 'perm':
+                    grads[4 * k + 1] = g_e
+            if need_A and st.ia_mode == 'col':
+                t = adj.t_src          # rows of A collect from the destinations they fed
+                act_specs.append(AggActBwdSpec(adj=t, F=F, act=code, g=g, ig=t.col, P=A, Q=B,
+                                               iq=t.aux if st.ib_mode == 'aux' else t.perm))
+                act_slots.append(4 * k)
+            if need_B and st.ib_mode == 'aux':
+                t = adj.t_aux          # keyed on the shared cell: col = destination, aux = source
+                act_specs.append(AggActBwdSpec(adj=t, F=F, act=code, g=g, ig=t.col, P=B, Q=A,
+                                               iq=t.aux if st.ia_mode == 'col' else t.perm))
+                act_slots.append(4 * k + 1)
+            continue
         if st.reduce == 'max':
             out_k = max_outs[sum(1 for s_ in streams[:k] if s_.reduce == 'max')]
             if op != MSG_A:
@@ -402,6 +508,9 @@ def _aggregate_backward(streams, tensors, needs, gs, max_outs, device) -> List[O
     if specs:
         for slot, o in zip(slots, run_aggregate(specs, device)):
             grads[slot] = o
+    if act_specs:
+        for slot, o in zip(act_slots, run_aggregate_act_bwd(act_specs, device)):
+            grads[slot] = o
     return grads
 
 
@@ -436,7 +545,7 @@ class _AggregateMany(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, streams: Tuple[Stream, ...], device, *tensors):
-        outs = run_aggregate(_AggregateMany.specs_of(streams, tensors), device)
+        outs = _run_streams(_AggregateMany.specs_of(streams, tensors), device)     # (activated streams: a launch of their own)
         ctx.streams, ctx.device = streams, device
         ctx.n_in = len(tensors)
         keep = [o for o, st in zip(outs, streams) if st.reduce == 'max']     # arg-max recovery in backward
@@ -471,6 +580,7 @@ class _AggregateMany(torch.autograd.Function):
         return aggregate(t, t.n_dst, by_entry, ia_mode='perm')
 
     @staticmethod
+    @torch.autograd.function.once_differentiable
     def backward(ctx, *gs):
         saved = ctx.saved_tensors
         tensors, max_outs = saved[:ctx.n_in], list(saved[ctx.n_in:])
@@ -497,8 +607,8 @@ def _run_streams(specs: Sequence, device) -> List[Tensor]:
 
 def aggregate_many(streams: Sequence[Stream]) -> List[Tensor]:
     """All streams in ONE kernel launch (per <= 8), differentiable w.r.t. A, B, self_x and eps.  Streams with an
-    activation (Stream.act) take a launch of their own (run_aggregate_act) and are inference only; the outputs come back
-    in stream order either way."""
+    activation (Stream.act) take a launch of their own forward (run_aggregate_act) and, with ACT_MESSAGE_BACKWARD on, one
+    backward (run_aggregate_act_bwd); with it off they are inference only.  The outputs come back in stream order either way."""
     device = None
     flat: List[Optional[Tensor]] = []
     for st in streams:
@@ -524,7 +634,7 @@ def aggregate_many(streams: Sequence[Stream]) -> List[Tensor]:
     if not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in flat)):
         # inference: no autograd node to build (Function.apply alone is ~15 us of host time)
         return _run_streams(_AggregateMany.specs_of(streams, flat), device)
-    if any(st.act is not None for st in streams):
+    if not ACT_MESSAGE_BACKWARD and any(st.act is not None for st in streams):
         raise NotImplementedError(_ACT_NO_GRAD)
     return list(_AggregateMany.apply(tuple(streams), device, *flat))
 

@@ -1633,6 +1633,79 @@ int cwn_aggregate_act_f32(const cwn_agg_act_desc* descs_host, int n, cwn_stream_
 int cwn_aggregate_act_f64(const cwn_agg_act_desc_f64* descs_host, int n, cwn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The backward of the activated two-operand message (csrc/cwn_aggregate_act_bwd.hip), float32 and float64:
+ *
+ *     out[r, :] = sum_{p in row r, in CSR order} g[ig[p], :] * act'( P[r, :] + Q[iq[p], :] )
+ *
+ * over a TRANSPOSED plan, whose rows are the cells of the operand being differentiated: P is that operand (its own
+ * row r), Q the other operand gathered per entry, g the gradient of the stream's output gathered through the
+ * destination index.  For dA of out = sum act(A[ia] + B[ib]): the plan keyed on the source cell, P = A, Q = B; for dB:
+ * the plan keyed on the shared cell, P = B, Q = A.  It is the shape of the ReLU stream's backward descriptor
+ * (CWN_MSG_A_MASK_RELU: A = g, B, self_pre) with act' in place of the mask.  Descriptors cwn_agg_act_bwd_desc /
+ * cwn_agg_act_bwd_desc_f64: one layout with float / double pointers.  There is no self term and no second operand
+ * form (in this stream both operands are product outputs), the reduction is add, and there is NO m_dev -- n_dst is a
+ * host count and every row below it exists: no static batch reaches this launch.
+ * dy * act'(z), by torch's backward formulas (so a non-finite z or dy gives what torch gives), z = P + Q:
+ *     CWN_ACT_ID       dy
+ *     CWN_ACT_RELU     dy unless z <= 0 (a select: 0 behind a closed gate whatever dy is; a NaN z hands dy on)
+ *     CWN_ACT_ELU      z > 0 ? dy : dy * exp(z)                       (alpha = 1; a NaN z gives NaN)
+ *     CWN_ACT_TANH     dy * (1 - y * y)                               y = act(z) with the forward's bits
+ *     CWN_ACT_SIGMOID  dy * (y * (1 - y))
+ * rowptr == NULL (absent plan): out = zeros, and g / P / Q / ig / iq are not looked at.  A row without entries gets
+ * zeros.  n_dst == 0 and n == 0 are legal.  Any F >= 1 (rows wider than one pass of a lane group are chunked).  One
+ * launch covers all n <= CWN_MAX_DESCS descriptors; the launcher validates every descriptor on the host before it
+ * launches, neither allocates nor synchronises.  The checks, in this order per descriptor, all before the first device
+ * call: CWN_ERR_BAD_ARG: n < 0 or n > CWN_MAX_DESCS, descs NULL with n > 0; F <= 0, n_dst < 0, out NULL with n_dst > 0;
+ * act outside CWN_ACT_ID .. CWN_ACT_SIGMOID; a non-NULL rowptr with a NULL ig / iq / g / P / Q.  CWN_ERR_TOO_LARGE:
+ * n_dst or the grid beyond int32.  CWN_ERR_ALIGN: a data pointer that misses the alignment of its element type.
+ * Arithmetic: one add in the element type for the pre-activation, as the forward's; expf / tanhf in float32 and exp /
+ * tanh in float64; the product g * act' and the accumulation are SEPARATE roundings (no fma) on every path; the
+ * accumulator starts at 0 and takes the entries in CSR order.  No atomics.  A row's bits depend on its entries, F and
+ * its own descriptor's operands (their alignment decides the vector width) alone -- not on the row's place in the grid,
+ * on n_dst or on the other descriptors of the launch.  Rows of at most CWN_LONG_ROW entries are folded sequentially by
+ * one lane group (with fewer than 8 feature lanes rows above 16 entries by the group's entry slots and a fixed tree, as
+ * in cwn_aggregate_act_*); longer rows listed in long_rows / n_long by a whole workgroup, contiguous chunks combined in
+ * chunk order.  With act = CWN_ACT_RELU / CWN_ACT_ID a row of at most 16 entries has the bits CWN_MSG_A_MASK_RELU /
+ * CWN_MSG_A give it.  CWN_AGG_SMALL_OPERANDS vouches for g and Q within 4 GiB of their bases.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct cwn_agg_act_bwd_desc {
+    const int32_t* rowptr;    /* [n_dst+1] of the transposed plan, or NULL (absent: zeros) */
+    const int32_t* ig;        /* [E] row of g per CSR position (the entry's destination) */
+    const int32_t* iq;        /* [E] row of Q per CSR position */
+    const float* g;           /* [rows_g, F] gradient of the stream's output */
+    const float* P;           /* [n_dst, F] the operand being differentiated */
+    const float* Q;           /* [rows_q, F] the other operand */
+    float* out;               /* [n_dst, F] */
+    const int32_t* long_rows; /* from cwn_csr_build, or NULL (every row is reduced by one lane group) */
+    const int32_t* n_long;    /* [CWN_LONG_PARTS] from cwn_csr_build, or NULL */
+    int64_t n_dst;            /* host count: there is no m_dev */
+    int32_t F;
+    int32_t act;              /* CWN_ACT_* */
+    int32_t long_cap;         /* capacity of one long-row sub-list (E / CWN_LONG_ROW + 1) */
+    int32_t flags;            /* CWN_AGG_* bits (0: none) */
+} cwn_agg_act_bwd_desc;
+
+typedef struct cwn_agg_act_bwd_desc_f64 {
+    const int32_t* rowptr;
+    const int32_t* ig;
+    const int32_t* iq;
+    const double* g;
+    const double* P;
+    const double* Q;
+    double* out;
+    const int32_t* long_rows;
+    const int32_t* n_long;
+    int64_t n_dst;
+    int32_t F;
+    int32_t act;
+    int32_t long_cap;
+    int32_t flags;
+} cwn_agg_act_bwd_desc_f64;
+
+int cwn_aggregate_act_bwd_f32(const cwn_agg_act_bwd_desc* descs_host, int n, cwn_stream_t stream);
+int cwn_aggregate_act_bwd_f64(const cwn_agg_act_bwd_desc_f64* descs_host, int n, cwn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * The message-passing-agnostic baseline (csrc/cwn_agnostic.hip), float32 and float64, inference:
  * MessagePassingAgnostic (mp/models.py:618-661), the control of the strongly-regular-graph experiment
  * (exp/scripts/cwn-sr-base.sh: hidden 256, ELU, float64), as two launches.
