@@ -33,7 +33,7 @@ EXPORTS = ('cwn_abi_version', 'cwn_error_string', 'cwn_target_arch', 'cwn_csr_wo
            'cwn_linear_wide_f32',
            'cwn_aggregate_act_f32', 'cwn_aggregate_act_f64', 'cwn_aggregate_act_bwd_f32', 'cwn_aggregate_act_bwd_f64',
            'cwn_embed_pool_f32', 'cwn_embed_pool_f64', 'cwn_agnostic_head_f32', 'cwn_agnostic_head_f64',
-           'cwn_gin_layer_f32', 'cwn_gine_layer_f32',
+           'cwn_gin_layer_f32', 'cwn_gine_layer_f32', 'cwn_gin_layer_dev_f32', 'cwn_gine_layer_dev_f32',
            'cwn_gemm_tn_f32', 'cwn_gemm_tn_workspace_bytes', 'cwn_gemm_tn_would_split', 'cwn_adam_f32', 'cwn_adam_dev_f32', 'cwn_loss_f32', 'cwn_loss_cols_f32', 'cwn_embedding_fwd_f32', 'cwn_embedding_bwd_f32', 'cwn_embed_front_f32', 'cwn_head_f32', 'cwn_head_bwd_f32', 'cwn_head_pool_floats', 'cwn_lift_create', 'cwn_lift_size', 'cwn_lift_copy', 'cwn_lift_destroy',
            'cwn_lift_many', 'cwn_lift_many_count', 'cwn_lift_many_lengths', 'cwn_lift_many_copy', 'cwn_lift_many_destroy',
            # the evaluation pass (csrc/cwn_metrics.hip)
@@ -627,6 +627,10 @@ def lib():
     L.cwn_gin_layer_f32.argtypes = [C.POINTER(GinDesc), C.c_void_p]
     L.cwn_gine_layer_f32.restype = C.c_int
     L.cwn_gine_layer_f32.argtypes = [C.POINTER(GineDesc), C.c_void_p]
+    L.cwn_gin_layer_dev_f32.restype = C.c_int
+    L.cwn_gin_layer_dev_f32.argtypes = [C.POINTER(GinDesc), C.c_void_p, C.c_void_p]
+    L.cwn_gine_layer_dev_f32.restype = C.c_int
+    L.cwn_gine_layer_dev_f32.argtypes = [C.POINTER(GineDesc), C.c_void_p, C.c_void_p]
     L.cwn_target_head_bwd_workspace_bytes.restype = C.c_size_t
     L.cwn_target_head_bwd_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32]
     L.cwn_adam_dev_f32.restype = C.c_int
@@ -969,6 +973,17 @@ def gin_layer(desc: 'GinDesc', device) -> None:
 def gine_layer(desc: 'GineDesc', device) -> None:
     """One GINEConv layer in one launch (csrc/cwn_gine.hip).  Host row counts, no m_dev, as `gin_layer`."""
     check(lib().cwn_gine_layer_f32(C.byref(desc), stream_ptr(device)), 'cwn_gine_layer_f32')
+
+
+def gin_layer_counted(desc: 'GinDesc', n_dev: int, device) -> None:
+    """`gin_layer` under a capacity (cwn_gin_layer_dev_f32): desc.n is the capacity, `n_dev` the address of the device int64
+    that holds the rows that exist.  The caller names the count: nothing is looked up in DYN_ROWS here."""
+    check(lib().cwn_gin_layer_dev_f32(C.byref(desc), n_dev, stream_ptr(device)), 'cwn_gin_layer_dev_f32')
+
+
+def gine_layer_counted(desc: 'GineDesc', n_dev: int, device) -> None:
+    """`gine_layer` under a capacity (cwn_gine_layer_dev_f32): desc.g.n is the capacity, as `gin_layer_counted`."""
+    check(lib().cwn_gine_layer_dev_f32(C.byref(desc), n_dev, stream_ptr(device)), 'cwn_gine_layer_dev_f32')
 
 
 def target_head_served(H: int, K: int) -> bool:

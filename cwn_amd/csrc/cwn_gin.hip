@@ -10,7 +10,9 @@
 // wave64s owns CWN_GIN_TM = 32 destination rows:
 //   1. every (row, column) of the tile is one work item: it folds the row's entries one after the other in CSR order,
 //      whatever the row's length (four entries' loads in flight, added in entry order), adds (1 + eps) * x and writes s into
-//      the LDS panel sp[32][132]; columns [w, w rounded up to 16) and rows past n hold zeros.
+//      the LDS panel sp[32][132]; columns [w, w rounded up to 16) and rows past n hold zeros.  (n: the host count, or in
+//      cwn_gin_layer_dev_f32 the device count clamped to the capacity -- live_rows, cwn_gin_tile.h; a workgroup whose first
+//      row is not below it returns before it reads anything, rows behind it are neither read nor written.)
 //   2. sp times W1 on v_mfma_f32_16x16x4_f32 (exact fp32) with the operand roles and K-slab walk of cwn_oriented.hip:
 //      A = 16 weight rows (output columns), B = 16 panel rows, K in slabs of 16 in which lane group g = lane >> 4 owns
 //      k = 4g .. 4g + 3 -- the panel fragment is one 16-byte LDS read, a lane's four accumulator registers are four
@@ -49,16 +51,16 @@ __device__ __forceinline__ float fold_entries(const float* __restrict__ x, int64
     return acc;
 }
 
-__global__ __launch_bounds__(kThreads) void gin_layer_kernel(GinArgs P) {
+__global__ __launch_bounds__(kThreads) void gin_layer_kernel(GinArgs P, const int64_t* __restrict__ n_dev) {
     __shared__ __attribute__((aligned(16))) float sp[kTM * kLdp];       // s, [kTM][kLdp]
     __shared__ __attribute__((aligned(16))) float hp[kTM * kLdp];       // h
     const int tid = threadIdx.x;
     const int w = P.d.w;
     const int64_t ldx = P.d.ldx;
     const float* __restrict__ x = P.d.x;
-    const int64_t n = P.d.n;
+    const int64_t n = live_rows(P, n_dev);        // (the host count, or the device count inside the capacity P.d.n)
     const int64_t row0 = (int64_t)blockIdx.x * kTM;
-    if (row0 >= n) return;                        // (uniform; the grid has no such workgroup)
+    if (row0 >= n) return;                        // (uniform; with a host count the grid has no such workgroup)
 
     // ---- 1. the panel of s ----------------------------------------------------------------------------------------------
     const int32_t* __restrict__ rowptr = P.d.rowptr;
@@ -78,7 +80,7 @@ __global__ __launch_bounds__(kThreads) void gin_layer_kernel(GinArgs P) {
     __syncthreads();
 
     // ---- 2, 3, 4. the two stages (cwn_gin_tile.h) ---------------------------------------------------------------------------
-    stages_from_panel(P, sp, hp, row0, tid);
+    stages_from_panel(P, sp, hp, row0, n, tid);
 }
 
 }  // namespace
@@ -88,6 +90,17 @@ extern "C" int cwn_gin_layer_f32(const cwn_gin_desc* desc, cwn_stream_t stream_)
     if (rc != CWN_OK) return rc;
     if (desc->n == 0) return CWN_OK;
     const GinArgs P = gin_args(*desc);
-    gin_layer_kernel<<<dim3(gin_blocks(P.d)), dim3(kThreads), 0, (hipStream_t)stream_>>>(P);
+    gin_layer_kernel<<<dim3(gin_blocks(P.d)), dim3(kThreads), 0, (hipStream_t)stream_>>>(P, nullptr);
+    return hipGetLastError() == hipSuccess ? CWN_OK : CWN_ERR_LAUNCH;
+}
+
+// The counted form: desc->n is the capacity (the grid, every address bound), *n_dev the rows that exist.
+extern "C" int cwn_gin_layer_dev_f32(const cwn_gin_desc* desc, const int64_t* n_dev, cwn_stream_t stream_) {
+    int rc = gin_check(desc);
+    if (rc == CWN_OK) rc = gin_count_check(desc->n, n_dev);
+    if (rc != CWN_OK) return rc;
+    if (desc->n == 0) return CWN_OK;
+    const GinArgs P = gin_args(*desc);
+    gin_layer_kernel<<<dim3(gin_blocks(P.d)), dim3(kThreads), 0, (hipStream_t)stream_>>>(P, n_dev);
     return hipGetLastError() == hipSuccess ? CWN_OK : CWN_ERR_LAUNCH;
 }

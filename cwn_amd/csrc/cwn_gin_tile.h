@@ -10,6 +10,7 @@
 #include "../../include/cwn_hip.h"
 #include "cwn_act.h"
 #include "cwn_check.h"
+#include "cwn_group.h"
 
 namespace {
 
@@ -93,12 +94,18 @@ __device__ __forceinline__ void zero_panel_padding(float* sp, int w, int kp1, in
     }
 }
 
+// The rows of a launch that exist: the host count d.n, or with a device count (the counted entries, cwn_gin_layer_dev_f32 /
+// cwn_gine_layer_dev_f32: d.n is then the CAPACITY that sized the grid) that count clamped to [0, d.n].  Read once per
+// workgroup, before anything else; every row test of the fold and of stages_from_panel is against it.
+__device__ __forceinline__ int64_t live_rows(const GinArgs& P, const int64_t* __restrict__ n_dev) {
+    return cwn::rows_clamped(n_dev, P.d.n);
+}
+
 // The two stages behind the panel of s (complete in sp, the workgroup synchronised): h = act((s W1^T + b1) * scale1 + shift1)
-// into hp, out = act_post(act((h W2^T + b2) * scale2 + shift2)) to memory.
-__device__ __forceinline__ void stages_from_panel(const GinArgs& P, const float* sp, float* hp, int64_t row0, int tid) {
+// into hp, out = act_post(act((h W2^T + b2) * scale2 + shift2)) to memory, rows below `n` (live_rows) alone.
+__device__ __forceinline__ void stages_from_panel(const GinArgs& P, const float* sp, float* hp, int64_t row0, int64_t n, int tid) {
     const int w = P.d.w, H = P.d.H;
     const int kp1 = (w + 15) & ~15, kp2 = (H + 15) & ~15;
-    const int64_t n = P.d.n;
     const int lane = tid & 63, wave = tid >> 6, j = lane & 15, g = lane >> 4;
     const int act = P.d.act;
     f32x4 acc[kCT][kRT];
@@ -174,6 +181,13 @@ inline int gin_check(const cwn_gin_desc* desc) {
     for (const void* p : ptrs)
         if (!al4(p)) return CWN_ERR_ALIGN;
     if ((D.n + kTM - 1) / kTM >= INT32_MAX) return CWN_ERR_TOO_LARGE;
+    return CWN_OK;
+}
+
+// The device count of a counted entry, behind the descriptor's own checks: required where there are rows, 8-byte aligned.
+inline int gin_count_check(int64_t n, const int64_t* n_dev) {
+    if (n > 0 && n_dev == nullptr) return CWN_ERR_BAD_ARG;
+    if (((uintptr_t)n_dev & 7) != 0) return CWN_ERR_ALIGN;
     return CWN_OK;
 }
 

@@ -57,7 +57,7 @@ __device__ __forceinline__ float fold_entries(const float* __restrict__ x, int64
     return acc;
 }
 
-__global__ __launch_bounds__(kThreads) void gine_layer_kernel(GineArgs A) {
+__global__ __launch_bounds__(kThreads) void gine_layer_kernel(GineArgs A, const int64_t* __restrict__ n_dev) {
     __shared__ __attribute__((aligned(16))) float sp[kTM * kLdp];       // s, [kTM][kLdp]
     __shared__ __attribute__((aligned(16))) float hp[kTM * kLdp];       // h
     const GinArgs& P = A.g;
@@ -66,9 +66,9 @@ __global__ __launch_bounds__(kThreads) void gine_layer_kernel(GineArgs A) {
     const int64_t ldx = P.d.ldx, lde = A.lde;
     const float* __restrict__ x = P.d.x;
     const float* __restrict__ e = A.e;
-    const int64_t n = P.d.n;
+    const int64_t n = live_rows(P, n_dev);        // (the host count, or the device count inside the capacity P.d.n)
     const int64_t row0 = (int64_t)blockIdx.x * kTM;
-    if (row0 >= n) return;                        // (uniform; the grid has no such workgroup)
+    if (row0 >= n) return;                        // (uniform; with a host count the grid has no such workgroup)
 
     // ---- 1. the panel of s ----------------------------------------------------------------------------------------------
     const int32_t* __restrict__ rowptr = P.d.rowptr;
@@ -89,24 +89,44 @@ __global__ __launch_bounds__(kThreads) void gine_layer_kernel(GineArgs A) {
     __syncthreads();
 
     // ---- 2, 3, 4. the two stages (cwn_gin_tile.h) ---------------------------------------------------------------------------
-    stages_from_panel(P, sp, hp, row0, tid);
+    stages_from_panel(P, sp, hp, row0, n, tid);
 }
 
-}  // namespace
-
-extern "C" int cwn_gine_layer_f32(const cwn_gine_desc* desc, cwn_stream_t stream_) {
+// The checks of a cwn_gine_desc, before any HIP call: those of its cwn_gin_desc first.
+inline int gine_check(const cwn_gine_desc* desc) {
     if (desc == nullptr) return CWN_ERR_BAD_ARG;
     const int rc = gin_check(&desc->g);
     if (rc != CWN_OK) return rc;
     if (desc->g.rowptr != nullptr && (desc->e == nullptr || desc->eidx == nullptr || desc->lde < desc->g.w || desc->n_e < 0))
         return CWN_ERR_BAD_ARG;
     if (!al4(desc->e) || !al4(desc->eidx)) return CWN_ERR_ALIGN;
-    if (desc->g.n == 0) return CWN_OK;
+    return CWN_OK;
+}
+
+inline int gine_launch(const cwn_gine_desc* desc, const int64_t* n_dev, cwn_stream_t stream_) {
     GineArgs A{};
     A.g = gin_args(desc->g);
     A.e = desc->e;
     A.eidx = desc->eidx;
     A.lde = desc->lde;
-    gine_layer_kernel<<<dim3(gin_blocks(desc->g)), dim3(kThreads), 0, (hipStream_t)stream_>>>(A);
+    gine_layer_kernel<<<dim3(gin_blocks(desc->g)), dim3(kThreads), 0, (hipStream_t)stream_>>>(A, n_dev);
     return hipGetLastError() == hipSuccess ? CWN_OK : CWN_ERR_LAUNCH;
+}
+
+}  // namespace
+
+extern "C" int cwn_gine_layer_f32(const cwn_gine_desc* desc, cwn_stream_t stream_) {
+    const int rc = gine_check(desc);
+    if (rc != CWN_OK) return rc;
+    if (desc->g.n == 0) return CWN_OK;
+    return gine_launch(desc, nullptr, stream_);
+}
+
+// The counted form: desc->g.n is the capacity (the grid, every address bound), *n_dev the rows that exist.
+extern "C" int cwn_gine_layer_dev_f32(const cwn_gine_desc* desc, const int64_t* n_dev, cwn_stream_t stream_) {
+    int rc = gine_check(desc);
+    if (rc == CWN_OK) rc = gin_count_check(desc->g.n, n_dev);
+    if (rc != CWN_OK) return rc;
+    if (desc->g.n == 0) return CWN_OK;
+    return gine_launch(desc, n_dev, stream_);
 }

@@ -2145,11 +2145,26 @@ FUSED_GIN_DEFAULT = True
 FUSED_GIN = {'0': False, '1': True}.get(os.environ.get('CWN_FUSED_GIN'), FUSED_GIN_DEFAULT)
 
 
-def _gin_fused_stages(nn, eps, x):
+# Under a static batch (_ffi.DYN_ROWS: x has the slot's capacity as its row count) the same layers as ONE counted launch,
+# cwn_gin_layer_dev_f32 / cwn_gine_layer_dev_f32: the kernels of the host-count entries with the slot's live row count read on
+# the device.  CWN_FUSED_GIN_STATIC=1 / =0 turns the route on / off (FUSED_GIN / FUSED_GINE must be on as well); without it
+# FUSED_GIN_STATIC_DEFAULT decides, by the project's rule: on only where StaticForward with the counted launches has
+# measured faster than StaticForward with the generic route of the same commit by more than the larger p10 .. p90 spread of
+# the two (tools/bench_gin_static.py, profiles/gin_static.md: rounds of ten epochs over fresh permutations, the forms
+# alternating in one process; EmbedGIN with hidden 128 and 4 layers on 128 ZINC-like molecules 187.3 against 238.9 us per
+# batch, spread 2.5 us, 7.2 kernels against 39.2; RingGIN with 16 layers on 32 rings of 32 305.4 against 766.6 us, spread
+# 8.9 us, 20.2 kernels against 149.2).
+FUSED_GIN_STATIC_DEFAULT = True
+FUSED_GIN_STATIC = {'0': False, '1': True}.get(os.environ.get('CWN_FUSED_GIN_STATIC'), FUSED_GIN_STATIC_DEFAULT)
+
+
+def _gin_fused_stages(nn, eps, x, static: bool = False):
     """([(W, b, scale, shift)] * 2, activation name) of a GINConv's / GINEConv's network when its layer can be ONE launch
-    (the route's own switch aside), else None: autograd off, x float32 on the GPU, no static batch, `nn` a stock Sequential
-    of two (Linear, norm, activation) groups whose norms fold, widths within 128."""
-    if torch.is_grad_enabled() or not isinstance(x, Tensor) or not x.is_cuda or x.dtype != torch.float32 or _ffi_dyn():
+    (the route's own switch aside), else None: autograd off, x float32 on the GPU, no static batch (`static`: the caller
+    brings a device count, a static batch is what it serves), `nn` a stock Sequential of two (Linear, norm, activation)
+    groups whose norms fold, widths within 128."""
+    if (torch.is_grad_enabled() or not isinstance(x, Tensor) or not x.is_cuda or x.dtype != torch.float32
+            or (_ffi_dyn() and not static)):
         return None
     got = _f64_stages(nn, 2)
     if got is None or not (eps.is_cuda and eps.dtype == torch.float32):
@@ -2172,6 +2187,8 @@ class GINConv(torch.nn.Module):
       'fused'    autograd off, float32 on the GPU, `nn` a stock Sequential of two (Linear, norm, activation) groups whose
                  norms fold (eval-mode BatchNorm1d or Identity), widths within 128, FUSED_GIN on, no static batch:
                  csr.cached_adjacency + ONE ops.gin_layer launch.
+      'fused_counted'  the same layer under a static batch (a slot of static_batch.StaticBatch, mode 'csr'), FUSED_GIN_STATIC
+                 on as well and a device count behind x's row count: the slot's plan + ONE ops.gin_layer_counted launch.
       'generic'  everything else (training, float64, LayerNorm, a custom nn, CPU tensors): on the GPU ops.aggregate with the
                  self term folded in (differentiable, float32 and float64), then `self.nn`; on the CPU index_add_, then
                  `self.nn`.
@@ -2198,8 +2215,25 @@ class GINConv(torch.nn.Module):
         """([(W, b, scale, shift)] * 2, activation name) when the whole layer is ONE cwn_gin_layer_f32 launch, else None."""
         return _gin_fused_stages(self.nn, self.eps, x) if FUSED_GIN else None
 
+    def counted_stages(self, x):
+        """(stages, activation name, address of the device count) when, under a static batch, the whole layer is ONE
+        cwn_gin_layer_dev_f32 launch, else None: FUSED_GIN_STATIC and FUSED_GIN on, a network that folds, and a count behind
+        x's row count (_ffi.dyn).  Without a count the answer is None -- the generic route, never a launch over the capacity."""
+        if not (FUSED_GIN_STATIC and FUSED_GIN and _ffi_dyn() and isinstance(x, Tensor)):
+            return None
+        n_dev = ops._ffi.dyn(x.size(0))
+        got = _gin_fused_stages(self.nn, self.eps, x, static=True) if n_dev is not None else None
+        return None if got is None else (got[0], got[1], n_dev)
+
     def forward(self, x: Tensor, edge_index: Optional[Tensor], out: Optional[Tensor] = None, act_post: str = 'id') -> Tensor:
         n = x.size(0)
+        counted = self.counted_stages(x)
+        if counted is not None:
+            self.last_route = 'fused_counted'
+            adj = None
+            if edge_index is not None and edge_index.numel():
+                adj = cached_adjacency(edge_index, n, n)
+            return ops.gin_layer_counted(x, adj, self.eps, counted[0], counted[1], act_post=act_post, out=out, n_dev=counted[2])
         fused = self.fused_stages(x)
         if fused is not None:
             self.last_route = 'fused'
@@ -2255,6 +2289,8 @@ class GINEConv(torch.nn.Module):
       'fused'    autograd off, float32 on the GPU, `nn` a stock Sequential of two (Linear, norm, activation) groups whose
                  norms fold (eval-mode BatchNorm1d or Identity), widths within 128, the edge features float32, on the GPU
                  and as wide as x, FUSED_GINE on, no static batch: csr.cached_adjacency + ONE ops.gine_layer launch.
+      'fused_counted'  the same layer under a static batch, FUSED_GIN_STATIC on as well and a device count behind x's row
+                 count: the slot's plan (with its shared-coboundary index) + ONE ops.gine_layer_counted launch.
       'generic'  everything else: on the GPU ops.aggregate with the message relu(A + B) and the self term folded in
                  (differentiable with respect to x, the edge features and eps, float32 and float64), then `self.nn`; on
                  the CPU, and where the aggregation does not take the operands (edge features of another width, which
@@ -2282,6 +2318,18 @@ class GINEConv(torch.nn.Module):
         got = _gin_fused_stages(self.nn, self.eps, x) if FUSED_GINE else None
         return got if got is not None and ops.gine_layer_applies(x, edge, got[0]) else None
 
+    def counted_stages(self, x, edge=None):
+        """(stages, activation name, address of the device count) when, under a static batch, the whole layer is ONE
+        cwn_gine_layer_dev_f32 launch, else None: FUSED_GIN_STATIC and FUSED_GINE on, a network that folds, edge features the
+        launch takes, and a count behind x's row count (_ffi.dyn).  Without a count: None -- the generic route."""
+        if not (FUSED_GIN_STATIC and FUSED_GINE and _ffi_dyn() and isinstance(x, Tensor)):
+            return None
+        n_dev = ops._ffi.dyn(x.size(0))
+        got = _gin_fused_stages(self.nn, self.eps, x, static=True) if n_dev is not None else None
+        if got is None or not ops.gine_layer_applies(x, edge, got[0]):
+            return None
+        return got[0], got[1], n_dev
+
     def forward(self, x: Tensor, edge_index: Optional[Tensor], edge_attr=None, out: Optional[Tensor] = None,
                 act_post: str = 'id') -> Tensor:
         n = x.size(0)
@@ -2290,6 +2338,12 @@ class GINEConv(torch.nn.Module):
         if has_edges and edge is None:
             raise ValueError('GINEConv: edge_index has entries and edge_attr is None')
         aux = (edge_attr.index, edge.size(0)) if mode == 'aux' and has_edges else (None, 0)
+        counted = self.counted_stages(x, edge)
+        if counted is not None:
+            self.last_route = 'fused_counted'
+            adj = cached_adjacency(edge_index, n, n, *aux) if has_edges else None
+            return ops.gine_layer_counted(x, adj, edge, self.eps, counted[0], counted[1], act_post=act_post, out=out,
+                                          edge_mode=mode, n_dev=counted[2])
         fused = self.fused_stages(x, edge)
         if fused is not None:
             self.last_route = 'fused'

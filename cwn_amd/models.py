@@ -7,7 +7,7 @@ pin the whole stack against golden vectors of the reference model.  `SparseCIN` 
 mp/models.py:120-260 for non-embedded inputs (REDDIT-like config).  The readout
 (`pool_complex`, mp/nn.py:50-60) runs on the same segmented-reduce kernel as propagate.
 """
-from typing import List
+from typing import List, Optional
 
 import os
 import weakref
@@ -1043,10 +1043,50 @@ def _pooled_head_fused(model, pooled):
     return ops.agnostic_head([pooled], model.lin1.weight, model.lin1.bias, model.lin2.weight, model.lin2.bias, model.nonlinearity)
 
 
+def _slot_plan(data):
+    """The plan of a static batch's slot when `data` is that slot's batch, else None."""
+    from .static_batch import StaticBlockPlan
+    plan = data.block_plan() if hasattr(data, 'block_plan') else None
+    return plan if isinstance(plan, StaticBlockPlan) else None
+
+
+def static_head_refusal(model) -> Optional[str]:
+    """Why the pooled head of a graph baseline (readout, act(lin1), lin2) is not served on a static batch, or None: there it
+    is ONE ops.head launch over the slot's `ptr` table, which computes relu(lin1) on widths that are multiples of 4."""
+    H = int(model.lin1.out_features)
+    if hasattr(model, 'jump'):
+        return ('JumpingKnowledge models are not served on static batches (the head launch reads ONE matrix of layer outputs, not '
+                'their concatenation or maximum)')
+    if model.nonlinearity != 'relu':
+        return (f"the nonlinearity of its pooled head is {model.nonlinearity!r}: the head launch of a static batch (cwn_head_f32) "
+                "computes ReLU only")
+    if H % 4 != 0 or int(model.lin1.in_features) % 4 != 0:
+        return (f'its hidden width {H} is no multiple of 4: the head launch of a static batch (cwn_head_f32) wants K % 4 == 0')
+    return None
+
+
+def _slot_head(model, x, plan):
+    """Readout over the vertices, relu(lin1) and lin2 of a graph baseline on a slot of a static batch as ONE ops.head launch
+    over the slot's `ptr` table (the launch the SparseCIN family's head takes there, with one dimension): the table is
+    rewritten by every fill, where a CSR plan keyed on the slot's capacity-sized `batch` vector (global_pool) would be that
+    of the batch the slot held when the plan was built.  Inference only, without dropout."""
+    why = static_head_refusal(model)
+    if why is None and (torch.is_grad_enabled() or model.training):
+        why = 'it runs in inference only there (model.eval() under torch.no_grad())'
+    if why is None and (x.dtype != torch.float32 or x.size(0) != int(plan.cell_ptr[0][-1])):
+        why = f'its vertex features are {tuple(x.shape)} {x.dtype}, not the float32 rows of the slot'
+    if why is not None:
+        raise NotImplementedError(f'{model!r} on a static batch: {why}')
+    return ops.head([x], [plan.cell_ptr_device(0, x.device)], plan.C, [model.lin1.weight], [model.lin1.bias], model.lin2.weight,
+                    model.lin2.bias, mean_readout=model.readout == 'mean')
+
+
 class _GINStack(torch.nn.Module):
     """What GIN0, GIN, GIN0WithJK and GINWithJK (mp/graph_models.py) share: conv1 and convs of layers.GINConv over
     Linear -> BatchNorm -> act -> Linear -> BatchNorm -> act, an optional JumpingKnowledge, the readout per graph,
-    act(lin1) -> dropout -> lin2.  In inference on the GPU every layer is one launch (layers.FUSED_GIN), JumpingKnowledge
+    act(lin1) -> dropout -> lin2.  On a slot of a static batch (StaticForward, mode 'csr', no JumpingKnowledge) the readout
+    and the head are ONE ops.head launch over the slot's `ptr` table (_slot_head).  In inference on the GPU every layer is
+    one launch (layers.FUSED_GIN), JumpingKnowledge
     'cat' costs nothing (layer l writes columns [l H, (l + 1) H) of one buffer and layer l + 1 reads them in place) and the
     head of the models without JumpingKnowledge is one ops.agnostic_head launch over the one pooled matrix."""
 
@@ -1107,6 +1147,9 @@ class _GINStack(torch.nn.Module):
                 xs.append(x)
             if jump is not None:
                 x = jump(xs)
+        plan = _slot_plan(data)
+        if plan is not None:
+            return _slot_head(self, x, plan)
         x = self.pooling_fn(x, batch, size)
         out = self._head_fused(x)
         if out is not None:
@@ -1205,8 +1248,9 @@ class EmbedGIN(torch.nn.Module):
     cochain's rows -- read through the shared-coboundary index (cell_mp.IndexedRows), computed once for all layers -- the
     readout over the vertices, act(lin1) and lin2.  Same constructor arguments, attributes and state_dict keys as the
     reference (the embeddings appear as `v_embed_init.*` and as `init_conv.v_embed_init.*`).  In inference on the GPU
-    every layer is one launch where layers.FUSED_GINE is on and the head one ops.agnostic_head launch; on the CPU the
-    front, the layers and the head are plain torch."""
+    every layer is one launch where layers.FUSED_GINE is on and the head one ops.agnostic_head launch; on a slot of a
+    static batch (StaticForward, mode 'csr') the readout and the head are ONE ops.head launch over the slot's `ptr` table
+    (_slot_head); on the CPU the front, the layers and the head are plain torch."""
 
     def __init__(self, atom_types, bond_types, out_size, num_layers, hidden, dropout_rate: float = 0.5, nonlinearity='relu',
                  readout='sum', train_eps=False, apply_dropout_before='lin2', init_reduce='sum', embed_edge=False,
@@ -1279,6 +1323,9 @@ class EmbedGIN(torch.nn.Module):
         edge_attr = params.kwargs['up_attr'] if edge_index is not None else None      # no edges (:584-586): the self term alone
         for conv in self.convs:
             x = conv(x, edge_index, edge_attr)
+        plan = _slot_plan(data)
+        if plan is not None:
+            return _slot_head(self, x, plan)
         batch = data.nodes.batch
         size = getattr(data, 'num_complexes', None)
         if size is None:

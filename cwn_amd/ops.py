@@ -3227,9 +3227,46 @@ def gin_layer(x: Tensor, adj: Optional[Adjacency], eps, stages, act, act_post='i
     return out
 
 
-def _gin_descriptor(op: str, entry: str, rows: dict, layer: str, x, eps, stages, act, act_post, out):
+# an operand of the counted entries
+_GIN_COUNTED_ROWS = dict(_GIN_ROWS, what='gin_layer_counted: ', hint='cwn_gin_layer_dev_f32 computes in fp32 only')
+
+
+def _count_address(op: str, n_dev, device) -> int:
+    """`n_dev` of a counted launch as an address: a device int64 tensor of one element on `device`, or the address itself."""
+    if isinstance(n_dev, Tensor):
+        if n_dev.dtype != torch.int64 or n_dev.numel() != 1 or n_dev.device != device:
+            raise TypeError(f'{op}: n_dev is a {str(n_dev.dtype).replace("torch.", "")} tensor of {n_dev.numel()} element(s) on '
+                            f'{n_dev.device}: it must be one int64 on {device}')
+        return n_dev.data_ptr()
+    if isinstance(n_dev, int) and not isinstance(n_dev, bool) and n_dev > 0:
+        return n_dev
+    raise TypeError(f'{op}: n_dev is {type(n_dev).__name__}: a device int64 tensor of one element, or its address')
+
+
+def gin_layer_counted(x: Tensor, adj: Optional[Adjacency], eps, stages, act, act_post='id', out: Optional[Tensor] = None, *,
+                      n_dev) -> Tensor:
+    """`gin_layer` over a CAPACITY-sized x with the rows that exist counted on the device (cwn_gin_layer_dev_f32): the launch a
+    static batch takes.  x.size(0) is the capacity; `n_dev`, a device int64 tensor of one element or its address, holds the
+    live count, which the kernel clamps to [0, capacity].  Rows of `out` from the count on are left as they are; rows of x
+    from the count on, the plan's rowptr behind rowptr[count] and the entries behind it are never read.  A live row has the
+    bits `gin_layer` gives it on the operands trimmed to the count.  `adj` is a plan over the capacity whose first
+    rowptr[count] entries are the plan of the live rows (a csr-mode slot's plan, rebuilt per fill).  The operand checks,
+    inference only, float32 on the GPU, widths 1 .. 128 and the TypeError for anything else are those of `gin_layer`; this op
+    runs inside and outside `_ffi.dynamic_rows`."""
+    x, out, d = _gin_descriptor('gin_layer_counted', 'cwn_gin_layer_dev_f32', _GIN_COUNTED_ROWS, 'layers.GINConv', x, eps, stages,
+                                act, act_post, out, counted=True)
+    addr = _count_address('gin_layer_counted', n_dev, x.device)
+    if d is None:
+        return out
+    _gin_plan(d, 'gin_layer_counted', adj, int(x.size(0)))
+    _ffi.gin_layer_counted(d, addr, x.device)
+    return out
+
+
+def _gin_descriptor(op: str, entry: str, rows: dict, layer: str, x, eps, stages, act, act_post, out, counted: bool = False):
     """The operand checks that gin_layer and gine_layer share, and the cwn_gin_desc without its plan: (x, out, descriptor);
-    the descriptor is None when there is nothing to launch (no rows)."""
+    the descriptor is None when there is nothing to launch (no rows).  `counted`: the caller is a counted op, which brings its
+    own device count and therefore runs under `_ffi.dynamic_rows` too."""
     x = _rows_operand(x, 'x', 2, **rows)
     if len(stages) != 2 or any(len(s) != 4 for s in stages):
         raise ValueError(f'{op}: stages is [(W1, b1, scale1, shift1), (W2, b2, scale2, shift2)]')
@@ -3247,7 +3284,7 @@ def _gin_descriptor(op: str, entry: str, rows: dict, layer: str, x, eps, stages,
         raise RuntimeError(f'{op} is inference only ({entry} has no backward) and an operand requires a gradient '
                            f'while autograd is recording: run it under torch.no_grad(), or use {layer}, whose '
                            'generic route is differentiable')
-    if _ffi.DYN_ROWS:
+    if _ffi.DYN_ROWS and not counted:
         raise RuntimeError(f'{op} takes host row counts: it does not run under _ffi.dynamic_rows (a static batch)')
     named = [tuple(None if t is None else t.contiguous() for t in s) for s in named]
     if not gin_layer_applies(x, named):
@@ -3312,36 +3349,60 @@ def gine_layer(x: Tensor, adj: Optional[Adjacency], edge: Optional[Tensor], eps,
     index the plan was built from, as a torch_geometric caller hands edge_attr: edge.size(0) == adj.n_entries.  Everything
     else -- `eps`, `stages`, `act`, `act_post`, `out`, inference only, float32 on the GPU, widths up to 128, TypeError and
     never a fallback for another dtype or device -- is as in `gin_layer`."""
+    return _gine('gine_layer', 'cwn_gine_layer_f32', _GINE_ROWS, x, adj, edge, eps, stages, act, act_post, out, edge_mode, None)
+
+
+def gine_layer_counted(x: Tensor, adj: Optional[Adjacency], edge: Optional[Tensor], eps, stages, act, act_post='id',
+                       out: Optional[Tensor] = None, edge_mode: str = 'aux', *, n_dev) -> Tensor:
+    """`gine_layer` over a CAPACITY-sized x with the rows that exist counted on the device (cwn_gine_layer_dev_f32), as
+    `gin_layer_counted` is of `gin_layer`: x.size(0) is the capacity, `n_dev` a device int64 tensor of one element or its
+    address.  `edge` is capacity-sized too (edge.size(0) == adj.n_aux, or adj.n_entries with edge_mode='perm'); the rows of it
+    that only entries behind rowptr[count] name are never read."""
+    if n_dev is None:
+        raise TypeError('gine_layer_counted: n_dev is NoneType: a device int64 tensor of one element, or its address')
+    return _gine('gine_layer_counted', 'cwn_gine_layer_dev_f32', _GINE_COUNTED_ROWS, x, adj, edge, eps, stages, act, act_post, out,
+                 edge_mode, n_dev)
+
+
+_GINE_COUNTED_ROWS = dict(_GINE_ROWS, what='gine_layer_counted: ', hint='cwn_gine_layer_dev_f32 computes in fp32 only')
+
+
+def _gine(op: str, entry: str, rows: dict, x, adj, edge, eps, stages, act, act_post, out, edge_mode, n_dev):
+    """gine_layer (n_dev None) and gine_layer_counted: one body."""
     if edge_mode not in ('aux', 'perm'):
-        raise ValueError(f"gine_layer: edge_mode {edge_mode!r}: 'aux' or 'perm'")
-    edge = _rows_operand(edge, 'edge', 2, **_GINE_ROWS)
-    x, out, d = _gin_descriptor('gine_layer', 'cwn_gine_layer_f32', _GINE_ROWS, 'layers.GINEConv', x, eps, stages, act, act_post,
-                                out)
+        raise ValueError(f"{op}: edge_mode {edge_mode!r}: 'aux' or 'perm'")
+    edge = _rows_operand(edge, 'edge', 2, **rows)
+    x, out, d = _gin_descriptor(op, entry, rows, 'layers.GINEConv', x, eps, stages, act, act_post, out,
+                                counted=n_dev is not None)
     has_edges = adj is not None and adj.n_entries > 0
     if has_edges:
         if edge is None:
-            raise ValueError('gine_layer: the adjacency has entries and edge is None')
+            raise ValueError(f'{op}: the adjacency has entries and edge is None')
         if torch.is_grad_enabled() and edge.requires_grad:
-            raise RuntimeError('gine_layer is inference only (cwn_gine_layer_f32 has no backward) and edge requires a gradient '
+            raise RuntimeError(f'{op} is inference only ({entry} has no backward) and edge requires a gradient '
                                'while autograd is recording: run it under torch.no_grad(), or use layers.GINEConv, whose '
                                'generic route is differentiable')
         if edge.size(1) != x.size(1) or edge.device != x.device:
-            raise ValueError(f'gine_layer: edge is {tuple(edge.shape)} on {edge.device}: its width must be that of x '
+            raise ValueError(f'{op}: edge is {tuple(edge.shape)} on {edge.device}: its width must be that of x '
                              f'{tuple(x.shape)} on {x.device} (another width runs through layers.GINEConv\'s generic route)')
         if edge_mode == 'aux':
             if adj.aux is None:
-                raise ValueError("gine_layer: edge_mode='aux' needs an adjacency built with a shared-cell index (aux_index)")
+                raise ValueError(f"{op}: edge_mode='aux' needs an adjacency built with a shared-cell index (aux_index)")
             if edge.size(0) != adj.n_aux:
-                raise ValueError(f"gine_layer: edge_mode='aux': edge has {edge.size(0)} rows, the plan's shared cells are {adj.n_aux}")
+                raise ValueError(f"{op}: edge_mode='aux': edge has {edge.size(0)} rows, the plan's shared cells are {adj.n_aux}")
         elif edge.size(0) != adj.n_entries:
-            raise ValueError(f"gine_layer: edge_mode='perm': edge has {edge.size(0)} rows, the plan has {adj.n_entries} entries")
+            raise ValueError(f"{op}: edge_mode='perm': edge has {edge.size(0)} rows, the plan has {adj.n_entries} entries")
+    addr = None if n_dev is None else _count_address(op, n_dev, x.device)
     if d is None:
         return out
     D = _ffi.GineDesc(g=d)
-    if _gin_plan(D.g, 'gine_layer', adj, int(x.size(0))):
+    if _gin_plan(D.g, op, adj, int(x.size(0))):
         D.e, D.lde, D.n_e = edge.data_ptr(), ld(edge), int(edge.size(0))
         D.eidx = (adj.aux if edge_mode == 'aux' else adj.perm).data_ptr()
-    _ffi.gine_layer(D, x.device)
+    if addr is None:
+        _ffi.gine_layer(D, x.device)
+    else:
+        _ffi.gine_layer_counted(D, addr, x.device)
     return out
 
 

@@ -155,14 +155,53 @@ from .static_batch import StaticBatch            # noqa: E402
 from .train import TrainStep                     # noqa: E402
 
 
+def refuse_unsupported_graph_baseline(model: torch.nn.Module, who: str, static: Optional['StaticBatch'] = None,
+                                      training: bool = False) -> None:
+    """The graph baselines (models.GIN0 / GIN / GIN0WithJK / GINWithJK / RingGIN / EmbedGIN) on a static batch: served in
+    inference, in mode 'csr' -- every GINConv / GINEConv reads the slot's upper-adjacency plan, rebuilt per fill -- as float32
+    models whose layers fold into the counted launches (layers.FUSED_GIN_STATIC) or run the generic route, and whose pooled
+    head is ONE cwn_head_f32 launch over the slot's `ptr` table.  Everything else is refused here, by model and reason."""
+    from . import layers as L, models as M
+    if not isinstance(model, (M._GINStack, M.RingGIN, M.EmbedGIN)):
+        return
+    name = type(model).__name__
+
+    def no(why: str):
+        raise NotImplementedError(f'{who}: {name} is not served by a static batch: {why}; use collated batches with model(batch)')
+    if training:
+        no('the graph baselines are served in inference only (StaticForward): their BatchNorm in training mode would take its '
+           'statistics over the capacity rows of a slot, and the GIN layers have no counted backward')
+    if static is not None and static.mode != 'csr':
+        no(f"mode={static.mode!r} carries size-only stand-ins for the upper adjacencies, which the GIN layers read as CSR plans: "
+           "build the StaticBatch with mode='csr'")
+    for pname, t in list(model.named_parameters()) + list(model.named_buffers()):
+        if t.is_floating_point() and t.dtype != torch.float32:
+            no(f'{pname} is {t.dtype}: float64 models are not served (the counted launches and the head are float32)')
+    if not isinstance(model, M.RingGIN):
+        why = M.static_head_refusal(model)
+        if why is not None:
+            no(why)
+    for cname, conv in model.named_modules():
+        if isinstance(conv, (L.GINConv, L.GINEConv)):
+            got = L._f64_stages(conv.nn, 2)
+            # (the structure alone: a BatchNorm folds once the model is in eval(), which StaticForward.replay insists on)
+            folds = lambda lin, norm: isinstance(norm, torch.nn.Identity) or (
+                isinstance(norm, L.BN) and norm.running_mean is not None and norm.num_features == lin.out_features)
+            if got is None or not all(folds(lin, norm) for lin, norm in got[0]):
+                no(f'the network of {cname} does not fold into a layer launch (LayerNorm, or a custom nn: a stock Sequential of '
+                   'two (Linear, BatchNorm1d or Identity, activation) groups does)')
+
+
 def refuse_unsupported_layers(model: torch.nn.Module, who: str, static: Optional['StaticBatch'] = None, training: bool = False) -> None:
     """A static batch in mode 'blocked' carries, per slot, what SparseCINConv's blocked kernels read (item tables, the collated
     CSR of the boundary adjacencies for the backward) -- not a CSR plan of the UPPER / LOWER adjacencies, which the streaming
     aggregation of other layers (CINppConv, CINConv, OrientedConv) reads: those layers are refused there.  In mode 'csr'
     (round 5) the fill rebuilds those plans on the device (cwn_csr_desc.e_dev) and every layer's streaming path runs inside the
     captured graph -- except, in TRAINING, CINConv / EdgeCINConv: their per-entry BatchNorm takes its statistics with framework
-    reductions over the capacity rows of a slot, which would count rows the batch does not have."""
+    reductions over the capacity rows of a slot, which would count rows the batch does not have.  The graph baselines (the GIN
+    family) have rules of their own: refuse_unsupported_graph_baseline."""
     from .layers import CINConv, CINppConv, EdgeCINConv, OrientedConv
+    refuse_unsupported_graph_baseline(model, who, static, training)
     if static is not None and static.mode == 'csr':
         kinds = (CINConv, EdgeCINConv) if training else ()
         why = 'their per-entry BatchNorm(train) statistics are framework reductions over the capacity rows of a slot'
@@ -245,6 +284,7 @@ class StaticForward:
     a parameter (or, through ops.STATE_EPOCH, a raw-pointer writer such as a TrainStep) has changed them."""
 
     def __init__(self, model: torch.nn.Module, static: StaticBatch):
+        refuse_unsupported_graph_baseline(model, 'StaticForward', static)    # (names the model: ahead of the float32 check)
         ops.require_float32_model(model, 'StaticForward')
         refuse_unsupported_layers(model, 'StaticForward', static)
         self.model, self.sb = model, static

@@ -5,11 +5,15 @@ ZINC regression, mean absolute error on a held-out split.
 
 The loop is plain autograd with torch.optim.Adam over collated ComplexBatch inputs: EmbedGIN's one-launch layer
 (cwn_gine_layer_f32, layers.FUSED_GINE) takes host row counts, so the static batches of the other molecular examples do not
-reach it.  Training runs every layer through the differentiable route (one aggregation launch with the message relu(A + B)
+apply to its training (StaticTrainStep refuses the GIN family: its BatchNorm would take statistics over a slot's capacity rows).
+Training runs every layer through the differentiable route (one aggregation launch with the message relu(A + B)
 forward, its transposed launches backward, the torch modules of the network); the evaluation pass runs one launch per layer.
+With --static-eval the validation pass is device-resident instead: the held-out molecules packed once, a
+StaticBatch(mode='csr') + StaticForward replaying ONE captured graph per group of slots, evaluate.evaluate for the metric --
+every layer the counted launch where layers.FUSED_GIN_STATIC (CWN_FUSED_GIN_STATIC=1) is on, the generic route otherwise.
 The synthetic targets are random, so the curve shows the loop, not a chemistry result.
 
-    python examples/train_embed_gin.py [--graphs N] [--epochs E] [--layers 4] [--hidden 128]   (needs an MI355X)
+    python examples/train_embed_gin.py [--graphs N] [--epochs E] [--layers 4] [--hidden 128] [--static-eval]   (needs an MI355X)
 """
 import argparse
 import math
@@ -42,6 +46,7 @@ def main():
     ap.add_argument('--layers', type=int, default=4)
     ap.add_argument('--hidden', type=int, default=128)
     ap.add_argument('--lr', type=float, default=1e-3)
+    ap.add_argument('--static-eval', action='store_true', help='validate through StaticForward + evaluate.evaluate')
     args = ap.parse_args()
     dev = torch.device('cuda', 0)
     pool = zinc_like_complexes(args.graphs, seed=0, max_ring=6)
@@ -52,6 +57,17 @@ def main():
                      init_reduce='sum', embed_edge=True).to(dev)
     opt = torch.optim.Adam(model.parameters(), lr=args.lr)
     gen = torch.Generator().manual_seed(0)
+    static = None
+    if args.static_eval:
+        import numpy as np
+        from cwn_amd.evaluate import Evaluator, evaluate
+        from cwn_amd.packed import PackedComplexes
+        from cwn_amd.static_batch import StaticBatch
+        from cwn_amd.static_graph import StaticForward
+        packed = PackedComplexes(val, dev, max_dim=1, with_csr=True)
+        val_batches = [np.arange(lo, min(lo + args.batch, len(val))) for lo in range(0, len(val), args.batch)]
+        forward = StaticForward(model, StaticBatch(packed, args.batch, slots=min(4, len(val_batches)), mode='csr'))
+        static = (forward, val_batches, Evaluator('mae'))
     for epoch in range(args.epochs):
         model.train()
         t0 = time.perf_counter()
@@ -67,13 +83,17 @@ def main():
         if not all(math.isfinite(l) for l in losses):
             raise SystemExit(f'epoch {epoch}: a non-finite loss')
         model.eval()
-        err, count = 0.0, 0
-        with torch.no_grad():
-            for b in batches_of(val, args.batch, dev):
-                err += float((model(b).view(-1) - b.y.view(-1)).abs().sum())
-                count += b.y.numel()
+        if static is not None:
+            mae, _ = evaluate(static[0], static[1], static[2], 'regression')
+        else:
+            err, count = 0.0, 0
+            with torch.no_grad():
+                for b in batches_of(val, args.batch, dev):
+                    err += float((model(b).view(-1) - b.y.view(-1)).abs().sum())
+                    count += b.y.numel()
+            mae = err / count
         routes = {c.last_route for c in model.convs}
-        print(f'epoch {epoch}: train loss {sum(losses) / len(losses):.4f}, validation MAE {err / count:.4f} '
+        print(f'epoch {epoch}: train loss {sum(losses) / len(losses):.4f}, validation MAE {mae:.4f} '
               f'({len(losses)} steps in {dt * 1e3:.1f} ms; evaluation layers: {", ".join(sorted(routes))})')
     csr.check_errors(dev)
 

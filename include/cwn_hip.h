@@ -31,7 +31,8 @@
  *     cwn_linear_stats.hip still has its own copy of the clamp).
  *     cwn::rows_clamped -- the count clamped to [0, capacity]: cwn_gemm_f32 (both kernels), cwn_linear_stats_f32,
  *     cwn_linear_wide_f32, cwn_update_chain_f32, cwn_update_branches_f32, cwn_target_head_f32 / _bwd_f32, cwn_csr_build (e_dev), cwn_csr_long_rows
- *     and the cochain count of cwn_flow_head_dev_f32 / _bwd_dev_f32.  cwn::rows_capped -- the count capped ABOVE only (a
+ *     the cochain count of cwn_flow_head_dev_f32 / _bwd_dev_f32 and the n_dev of cwn_gin_layer_dev_f32 /
+ *     cwn_gine_layer_dev_f32.  cwn::rows_capped -- the count capped ABOVE only (a
  *     larger count behaves as the capacity; a negative one bounds loops that run upwards from 0, so nothing is stored):
  *     cwn_gemm_tn_f32, cwn_layernorm_*, cwn_dropout_f32, cwn_loss_f32 / cwn_loss_cols_f32, cwn_embedding_bwd_f32,
  *     cwn_embed_front_f32, cwn_embed_front_bwd_f32, cwn_oriented_layer_f32 / cwn_oriented_dz_f32.  cwn::rows_vouched -- the
@@ -1918,6 +1919,29 @@ typedef struct cwn_gine_desc {
     int64_t n_e;               /* host count of the rows of e */
 } cwn_gine_desc;
 int cwn_gine_layer_f32(const cwn_gine_desc* desc_host, cwn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The counted GIN layers (csrc/cwn_gin.hip, csrc/cwn_gine.hip), float32, inference.  Additive to ABI 24.
+ *
+ * cwn_gin_layer_f32 and cwn_gine_layer_f32 with a DEVICE-SIDE ROW COUNT, for a capacity-sized batch inside a captured
+ * graph (a static batch): the SAME two kernels, which take the count as a pointer beside their arguments (the host-count
+ * entries pass NULL), as cwn_flow_head_dev_f32 is the counted form of cwn_flow_head_f32.
+ *
+ *   - desc->n (g.n for GINE) is the CAPACITY: it sizes the grid and bounds every address.
+ *   - n_dev: a device int64.  A workgroup reads live = clamp(*n_dev, 0, n) once (cwn::rows_clamped, csrc/cwn_group.h) and
+ *     tests every row against it.  A workgroup whose first row is at or beyond `live` returns before it reads anything else.
+ *   - Rows [live, n) of out are never written; live == 0 (a count <= 0) writes nothing; a count above n is n.
+ *   - Rows [live, n) of x, rowptr[r] for r > live, the col / eidx positions behind rowptr[live] and the rows of e that only
+ *     they name are never read: they may hold anything, NaN included.  (The plan over the live rows is a plan of
+ *     cwn_csr_build: col[p] in [0, live) for p < rowptr[live].)
+ *   - The bits of a live row are those cwn_gin_layer_f32 / cwn_gine_layer_f32 give for that row on the operands trimmed to
+ *     `live` rows: they depend neither on the count, nor on the capacity, nor on what lies behind the count.
+ * Every check of the host-count entry applies unchanged, with its codes, and comes first.  Then: n_dev NULL with n > 0 is
+ * CWN_ERR_BAD_ARG; n_dev off 8 bytes is CWN_ERR_ALIGN.  n == 0: CWN_OK, nothing is launched (n_dev may be NULL).  All checks
+ * precede the first HIP call; the launchers neither allocate nor synchronise.
+ * ------------------------------------------------------------------------------------------ */
+int cwn_gin_layer_dev_f32(const cwn_gin_desc* desc_host, const int64_t* n_dev, cwn_stream_t stream);
+int cwn_gine_layer_dev_f32(const cwn_gine_desc* desc_host, const int64_t* n_dev, cwn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Device-side batching (collate): build the arrays of a ComplexBatch from a dataset that is
