@@ -57,14 +57,14 @@ FUSED_NORM_BACKWARD = False
 # apply launch, dz written once on the way.  False: cwn_norm_bwd_apply_f32 + a plain transposed-weight GEMM (A/B, tests).
 FUSED_NORM_APPLY = os.environ.get('CWN_FUSED_NORM_APPLY') != '0'
 # A BatchNorm without a launch of its own (include/cwn_hip.h: cwn_bn_live; round 4): the stage launch adds its workgroups'
-# column sums into 8 fp64 slot rows, every workgroup of the NEXT launch (the following stage, or the activation of the
+# column sums into CWN_BN_SLOTS (= _ffi.BN_SLOTS, 4) fp64 slot rows, every workgroup of the NEXT launch (the following stage, or the activation of the
 # layer's last stage) derives the affine from them in its prologue and its first workgroup writes what the backward reads and
 # the running statistics -- the 12 cwn_bn_finalize_f32 launches of a ZINC training step (5.9 us each) are gone.  Needs every
 # stage on cwn_dense_stage_f32 (width 64 / 128, packed blocks); CWN_LIVE_BN=0 restores the finalize launches (whose per-band
 # partials summed in band order are the bit-reproducible form).
 LIVE_BN = os.environ.get('CWN_LIVE_BN', '1') != '0'
 # ... and the REDUCE half of its backward (cwn_bn_bwd_live): the backward-stage launch that produces a stage's dy adds the
-# column sums of dyh, dyh * xhat into 8 fp32 slot rows from its epilogue (the tile still in registers, one coalesced atomic
+# column sums of dyh, dyh * xhat into CWN_BN_SLOTS fp32 slot rows from its epilogue (the tile still in registers, one coalesced atomic
 # instruction per 64 columns and workgroup); the launch that consumes them sums the slots in its prologue.  8 of the 12
 # cwn_norm_bwd_reduce_f32 launches of a ZINC step go (the combine stages' dy comes from autograd: theirs stay).  Round 3
 # tried this with one atomic per column and lane group straight into s1 / s2 -- 110 k four-lane atomic instructions onto 256

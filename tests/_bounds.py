@@ -231,6 +231,165 @@ def equivariant(got_graded, got_plain, row_grade, col_grade, what: str) -> None:
     assert torch.equal(g, want), f'{what}: {bad} elements change under power-of-two grading'
 
 
+def grade_ratio(N: int) -> torch.Tensor:
+    """Per column |mean| / spread = 2^(5n mod 13), 1 ... 4096, negative in every third column."""
+    n = torch.arange(N)
+    return torch.ldexp(torch.ones(N), (5 * n) % 13) * torch.where(n % 3 == 2, -1.0, 1.0)
+
+
+def graded_z(g, M: int, N: int, rows: bool = False) -> torch.Tensor:
+    """A pre-activation [M, N] as a graded Linear leaves it: column n has spread grade_cols(N)[n] and mean grade_ratio(N)[n]
+    spreads; with `rows` the deviations carry grade_rows(M) as well (the column's mean then stands far above most of them)."""
+    d = torch.randn(M, N, generator=g)
+    if rows:
+        d = d * grade_rows(M)[:, None]
+    return (d + grade_ratio(N)[None, :]) * grade_cols(N)[None, :]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# normalisation: BatchNorm1d(train) as csrc/cwn_norm.hip, cwn_bn_live.h and the stage kernels state it, LayerNorm as
+# csrc/cwn_layernorm.hip does.  A c is, as everywhere above, a magnitude times the number of roundings that can reach it.
+# ---------------------------------------------------------------------------------------------------------------------------
+F64_IN_F32 = 2.0 ** -29          # one float64 rounding in units of a float32 one
+
+
+def col_sum(x: Tracked, steps) -> Tracked:
+    """The sum over the rows, bounded order-free as segment_sum is: the sources' c plus steps(rows) times the sum of their |v|
+    (steps = FMA: rows; any order of any tree, LDS partials, slots and atomics included)."""
+    return Tracked(x.v.sum(0), x.c.sum(0) + steps(x.v.size(0)) * x.v.abs().sum(0))
+
+
+@dataclass
+class BnStats:
+    M: int
+    mean: Tracked         # [N]: the float64 mean rounded to float32
+    var: Tracked          # [N]: the biased variance (never stored; `fp64` is what reaches rstd and the running variance of it)
+    rstd: Tracked         # [N]: 1 / sqrt(var + eps) rounded to float32
+    fp64: torch.Tensor    # [N]: the float64 arithmetic's own error in var (sum y^2 / M - mean^2 cancels), in float32 units
+
+
+def bn_stats(z, eps: float, steps) -> BnStats:
+    """Column mean over the M rows, biased variance and rstd of a float32 matrix z (an input: what the launch itself stored).
+    The kernels sum y and y^2 in float64 and finalize in float64, so each of the three is the exact value rounded ONCE -- plus
+    what float64 loses in sum y^2 / M - mean^2: (depth + 2) float64 roundings of E y^2 + 2 |mean| E|y|, which at
+    |mean| / spread = 4096 is 2^24 times the variance.  depth = the additions one term can pass through: at most steps(M), and
+    in every form at most 64 inside its workgroup's row tile (32 or 64 rows) plus one per 32-row band of the matrix, whatever
+    the order between the tiles (band partials summed by the finalize launch, or atomics into the slots)."""
+    zv = _d(z)
+    M = zv.size(0)
+    mean = zv.mean(0)
+    var = ((zv - mean) ** 2).mean(0)
+    w = F64_IN_F32 * (min(steps(M), 64 + (M + 31) // 32) + 2)
+    fp64 = w * ((zv * zv).mean(0) + 2 * mean.abs() * zv.abs().mean(0))
+    e = float(torch.tensor(eps, dtype=torch.float32))                     # eps as the descriptor holds it
+    rstd = 1.0 / torch.sqrt(var + e)
+    return BnStats(M, Tracked(mean, mean.abs() + w * zv.abs().mean(0)), Tracked(var, var.abs() + fp64),
+                   Tracked(rstd, rstd.abs() * (1 + 2 * F64_IN_F32) + fp64 * rstd ** 3 / 2), fp64)
+
+
+def bn_affine(z, st: BnStats, gamma, beta):
+    """(scale, shift, y) of the folded affine: scale = gamma rstd, shift = beta - mean scale, y = z scale + shift, every
+    operation a float32 one (a contraction into an fma only removes a rounding)."""
+    one = torch.ones_like(st.mean.v)
+    scale = mul(inp(one if gamma is None else gamma), st.rstd)
+    shift = sub(inp(0 * one if beta is None else beta), mul(st.mean, scale))
+    return scale, shift, add(mul(inp(z), scale), shift)
+
+
+def bn_running(prev, new: Tracked, momentum: float) -> Tracked:
+    """(1 - momentum) prev + momentum new in float32; 1 - momentum is itself a rounded float32 difference."""
+    m = float(torch.tensor(momentum, dtype=torch.float32))
+    return add(mul(scalar(1.0 - m, abs(1.0 - m)), inp(prev)), mul(scalar(m), new))
+
+
+def bn_unbiased(st: BnStats, roundings: int) -> Tracked:
+    """var M / (M - 1) (M = 1: var) as the running variance takes it: ONE rounding where float64 forms it (cwn_bn_finalize_f32),
+    three where (float) var meets a float32 quotient (cwn_bn_live.h)."""
+    f = st.M / (st.M - 1.0) if st.M > 1 else 1.0
+    v = st.var.v * f
+    return Tracked(v, st.fp64 * f + roundings * v.abs())
+
+
+def sign_disputed(y: Tracked, unit: float = UNIT32) -> torch.Tensor:
+    """The entries where float32 and float64 may disagree about the sign of y: |v| <= 4 unit c.  ReLU is 1-Lipschitz, so the
+    forward result stays gated there; a test zeroes the incoming GRADIENT there before the launch, so that neither side's
+    column sums depend on the disputed mask."""
+    return y.v.abs() <= 4 * unit * y.c
+
+
+def bn_backward(z, dyh, st: BnStats, scale: Tracked, steps, form: str = 'apply'):
+    """(dz, s1, s2) of BatchNorm1d(train) behind dyh = dy [y > 0] (an input: the mask is settled by the caller; or Tracked):
+    xhat = (z - mean) rstd, s1 = sum dyh, s2 = sum dyh xhat (order-free), 1 / M a rounded float32 reciprocal, and
+        'apply'  dz = scale (dyh - s1 / M - xhat s2 / M)                        cwn_norm_bwd_apply_f32, cwn_norm_bwd_f32, bnb
+        'stage'  dz = scale dyh + a0 + a1 (z - mean), a0 = -scale (s1 / M), a1 = -scale (rstd (s2 / M))    cwn_dense_stage_bwd_f32"""
+    dyh = dyh if isinstance(dyh, Tracked) else inp(dyh)          # (Tracked: a gradient whose mask is disputed in places)
+    xc = sub(inp(z), st.mean)
+    xhat = mul(xc, st.rstd)
+    s1, s2 = col_sum(dyh, steps), col_sum(mul(dyh, xhat), steps)
+    inv = scalar(1.0 / st.M, 1.0 / st.M)
+    if form == 'apply':
+        dz = mul(scale, sub(sub(dyh, mul(s1, inv)), mul(xhat, mul(s2, inv))))
+    else:
+        a0, a1 = mul(scale, mul(s1, inv)), mul(scale, mul(st.rstd, mul(s2, inv)))
+        dz = sub(sub(mul(scale, dyh), a0), mul(a1, xc))
+    return dz, s1, s2
+
+
+def _ln_centered(x: torch.Tensor, off: torch.Tensor, steps):
+    """x - mu along the rows as the LayerNorm kernels reach it: e = x - m with m a float32 mean that is off by at most `off`
+    ([M, 1], a magnitude), then e - mean_N(e).  Whatever m is, e - mean(e) = x - mu exactly, so m's own error never enters:
+    what does is one rounding of every e (|e| <= |x - mu| + off), the N-term sum of them and the rounding of the difference.
+    Returns (x - mu tracked, the bound of |e|, the c of e, the c of mean_N(e))."""
+    N = x.size(1)
+    d = x - x.mean(1, keepdim=True)
+    mag = d.abs() + off
+    c_cc = mag.mean(1, keepdim=True) * (1 + steps(N)) + off
+    return Tracked(d, mag + c_cc + d.abs()), mag, mag, c_cc
+
+
+def ln_forward(z, gamma, beta, eps: float, steps, relu: bool):
+    """cwn_layernorm_act_f32: two-pass row statistics in float32 with the second pass's correction of the mean.  Returns a
+    dict of Tracked: y (before the activation), out, mean, rstd."""
+    x = _d(z)
+    N = x.size(1)
+    mu = x.mean(1, keepdim=True)
+    off = RIGOROUS * UNIT32 * (steps(N) + 1) * x.abs().mean(1, keepdim=True)        # the first pass: an N-term sum and a division
+    xc, mag, c_e, c_cc = _ln_centered(x, off, steps)
+    var = (xc.v ** 2).mean(1, keepdim=True)
+    c_var = (2 * mag * c_e + mag * mag).mean(1, keepdim=True) + steps(N) * (mag * mag).mean(1, keepdim=True) + 2 * var \
+        + 2 * off * c_cc + off * off
+    e = float(torch.tensor(eps, dtype=torch.float32))
+    rstd = 1.0 / torch.sqrt(var + e)
+    t_rstd = Tracked(rstd, (c_var + var + e) * rstd ** 3 / 2 + 2 * rstd)             # var + eps, sqrtf, the division
+    one = torch.ones(N, dtype=torch.float64)
+    y = add(mul(mul(xc, t_rstd), inp(one if gamma is None else gamma)), inp(0 * one if beta is None else beta))
+    return dict(y=y, out=act(y, 'relu') if relu else y, mean=Tracked(mu[:, 0], (c_cc + mu.abs())[:, 0]),
+                rstd=Tracked(rstd[:, 0], t_rstd.c[:, 0]))
+
+
+def ln_backward(z, dyh, gamma, fwd: dict, steps):
+    """cwn_layernorm_bwd_f32 behind dyh = dy [out > 0] (an input): g = dyh gamma, d = z - mean (the STORED float32 mean, off by
+    what `fwd['mean']` allows), c = mean_N(d), k1 = mean_N(g), k2 = rstd (sum g d - c sum g) / N, xhat = (d - c) rstd,
+    dz = rstd (g - k1 - xhat k2); dbeta = sum_m dyh, dgamma = sum_m dyh xhat (order-free).  Returns (dz, dgamma, dbeta)."""
+    x, dyh = _d(z), inp(dyh)
+    M, N = x.shape
+    off = (RIGOROUS * UNIT32 * fwd['mean'].c)[:, None]
+    xc, mag, c_e, c_cc = _ln_centered(x, off, steps)
+    rstd = Tracked(fwd['rstd'].v[:, None], fwd['rstd'].c[:, None])
+    g = dyh if gamma is None else mul(dyh, inp(gamma))
+    rs = lambda t: t.sum(1, keepdim=True)
+    sg = Tracked(rs(g.v), rs(g.c) + steps(N) * rs(g.v.abs()))
+    k1 = Tracked(sg.v / N, sg.c / N + sg.v.abs() / N)
+    T = rs(g.v * xc.v)
+    c_T = rs(g.c * mag + g.v.abs() * c_e + g.v.abs() * mag) + steps(N) * rs(g.v.abs() * mag) \
+        + c_cc * sg.v.abs() + off * sg.c + off * sg.v.abs() + T.abs()
+    k2v = rstd.v * T / N
+    k2 = Tracked(k2v, (c_T * rstd.v + T.abs() * rstd.c) / N + 2 * k2v.abs())
+    xhat = mul(xc, rstd)
+    dz = mul(rstd, sub(sub(g, k1), mul(xhat, k2)))
+    return dz, col_sum(mul(dyh, xhat), steps), col_sum(dyh, steps)
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # torch emulations (the CPU twins of the kernels' arithmetic)
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -252,3 +411,101 @@ def split_product(X, W, terms: int = 6) -> torch.Tensor:
     for a, b in (order if terms == 6 else order[3:]):
         out = out + a @ b.t()
     return out
+
+
+def _f32(x) -> torch.Tensor:
+    return torch.tensor(x, dtype=torch.float32)
+
+
+BN_ALTERED = ('sums_fp32', 'squares_fp32', 'capacity', 'biased_running', 'shift_mean')
+
+
+def bn_forward_twin(z, gamma, beta, eps, running_mean, running_var, momentum, alter=None, cap=None, live=False):
+    """cwn_bn_finalize_f32 + cwn_norm_act_f32 (no activation) in torch on the CPU: float64 column sums of y and of float64
+    squares, float64 finalize, one rounding to the float32 rstd, the float32 folded affine.  `live`: the running variance as
+    cwn_bn_live.h forms it (float32 var times a float32 quotient).  `alter` (BN_ALTERED), each a way to get it wrong:
+      sums_fp32       both column sums accumulated in float32
+      squares_fp32    y * y formed in float32 ahead of a float64 sum
+      capacity        1 / M from `cap`, the rows the buffer holds, not the rows that exist
+      biased_running  the running variance fed the biased variance
+      shift_mean      shift = beta - mean' scale with mean' the column sum over `cap` while scale and rstd use M"""
+    z = z.detach().cpu().float()
+    M = z.size(0)
+    zd = z.double()
+    if alter == 'sums_fp32':
+        s, sq = z.sum(0).double(), (z * z).sum(0).double()
+    elif alter == 'squares_fp32':
+        s, sq = zd.sum(0), (z * z).double().sum(0)
+    else:
+        s, sq = zd.sum(0), (zd * zd).sum(0)
+    Md = float(cap if alter == 'capacity' else M)
+    mean = s / Md
+    var = (sq / Md - mean * mean).clamp(min=0.0)
+    rstd = (1.0 / torch.sqrt(var + _f32(eps).double())).float()
+    scale = gamma * rstd
+    mean_shift = (s / float(cap)) if alter == 'shift_mean' else mean
+    shift = beta - mean_shift.float() * scale
+    out = z * scale + shift
+    mom = _f32(momentum)
+    grow = 1.0 if (M <= 1 or alter == 'biased_running') else None
+    if live:
+        unb = var.float() * (_f32(float(M)) / _f32(float(M - 1)) if grow is None else _f32(1.0))
+    else:
+        unb = (var * (M / (M - 1.0) if grow is None else 1.0)).float()
+    rm = (1.0 - mom) * running_mean + mom * mean.float()
+    rv = (1.0 - mom) * running_var + mom * unb
+    return dict(out=out, scale=scale, shift=shift, mean=mean.float(), rstd=rstd, running_mean=rm, running_var=rv)
+
+
+def bn_backward_twin(z, dyh, scale, mean, rstd, form='apply', alter=None):
+    """The BatchNorm backward of bn_backward's two forms in float32 torch; sums in torch's float32 order.  `alter`:
+      drop_xhat_term  the xhat s2 / M term left out of the column with the smallest grade
+      dgamma_short    s2 without the last row"""
+    z, dyh = z.detach().cpu().float(), dyh.detach().cpu().float()
+    M, N = z.shape
+    xc = z - mean
+    xhat = xc * rstd
+    s1, p = dyh.sum(0), dyh * xhat
+    s2 = p[:-1].sum(0) if alter == 'dgamma_short' else p.sum(0)
+    inv = _f32(1.0) / _f32(float(M))
+    keep = torch.ones(N)
+    if alter == 'drop_xhat_term':
+        keep[int(grade_cols(N).argmin())] = 0.0
+    if form == 'apply':
+        dz = scale * (dyh - s1 * inv - xhat * (s2 * inv) * keep)
+    else:
+        a0, a1 = -scale * (s1 * inv), -scale * (rstd * (s2 * inv))
+        dz = scale * dyh + a0 + a1 * keep * xc
+    return dz, s1, s2
+
+
+def ln_forward_twin(z, gamma, beta, eps, relu, alter=None):
+    """cwn_layernorm_act_f32 in float32 torch.  alter = 'no_correction': the second pass does not take the mean of the
+    deviations out again (plain two-pass statistics around a rounded mean)."""
+    z = z.detach().cpu().float()
+    fN = _f32(float(z.size(1)))
+    mean = z.sum(1, keepdim=True) / fN
+    d = z - mean
+    c = d.sum(1, keepdim=True) / fN
+    var = (d * d).sum(1, keepdim=True) / fN - c * c
+    if alter == 'no_correction':
+        c, var = torch.zeros_like(c), (d * d).sum(1, keepdim=True) / fN
+    var = var.clamp(min=0.0)
+    rstd = 1.0 / torch.sqrt(var + _f32(eps))
+    y = (d - c) * rstd
+    y = y if gamma is None else y * gamma
+    y = y if beta is None else y + beta
+    return dict(out=torch.relu(y) if relu else y, mean=(mean + c)[:, 0], rstd=rstd[:, 0])
+
+
+def ln_backward_twin(z, dyh, gamma, mean, rstd):
+    """cwn_layernorm_bwd_f32 in float32 torch behind dyh = dy [out > 0]: (dz, dgamma, dbeta)."""
+    z, dyh = z.detach().cpu().float(), dyh.detach().cpu().float()
+    fN = _f32(float(z.size(1)))
+    d = z - mean[:, None]
+    g = dyh if gamma is None else dyh * gamma
+    rs = lambda t: t.sum(1, keepdim=True)
+    c, k1 = rs(d) / fN, rs(g) / fN
+    k2 = rstd[:, None] * (rs(g * d) - c * rs(g)) / fN
+    xhat = (d - c) * rstd[:, None]
+    return rstd[:, None] * (g - k1 - xhat * k2), (dyh * xhat).sum(0), dyh.sum(0)

@@ -301,3 +301,152 @@ def test_what_the_old_parameter_gate_makes_of_the_alterations():
     assert _old_gate('eps_over_bc2', 2) <= 0.5
     for alt in ('eps_in_root', 'decoupled_wd', 'bias_at_t_minus_1'):
         assert _old_gate(alt, 2) > 50, alt
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# normalisation (tests/_norm_cases.py): the gates of tests/test_gpu_norm_componentwise.py over the float32 torch twins of
+# csrc/cwn_norm.hip, cwn_bn_live.h, the stage backward and csrc/cwn_layernorm.hip
+# ---------------------------------------------------------------------------------------------------------------------------
+from tests import _norm_cases as NC          # noqa: E402
+
+BN_SHAPES = [(M, N) for M in (33, 70, 300) for N in (64, 100)]
+BN_IDS = [f'{M}x{N}' for M, N in BN_SHAPES]
+FWD = ('out', 'mean', 'rstd', 'running_mean', 'running_var')
+
+
+def _bn_twin(c, live=False, **kw):
+    t = B.bn_forward_twin(c.z, c.gamma, c.beta, c.eps, c.rm0, c.rv0, NC.MOM, live=live, **kw)
+    t['out'] = torch.relu(t['out']) if c.relu else t['out']
+    return t
+
+
+def _bn_cpu32(c):
+    return c.cpu32()
+
+
+def test_grade_ratio_and_graded_z():
+    r = B.grade_ratio(40)
+    m, e = torch.frexp(r.abs())
+    assert bool((m == 0.5).all()) and int(e.min()) - 1 == 0 and int(e.max()) - 1 == 12
+    assert bool((r[2::3] < 0).all()) and bool((r[0::3] > 0).all()) and bool((r[1::3] > 0).all())
+    assert [int(x) for x in r[:4].abs()] == [1, 32, 1024, 4]
+    z = B.graded_z(torch.Generator().manual_seed(0), 300, 40)
+    ratio = (z.double().mean(0) / z.double().std(0)).abs() / r.abs()
+    assert float(ratio.min()) > 0.8 and float(ratio.max()) < 1.25                  # the column means stand grade_ratio spreads off
+    spread = z.double().std(0) / B.grade_cols(40)
+    assert float(spread.min()) > 0.8 and float(spread.max()) < 1.25
+
+
+def test_sign_disputed_marks_what_a_rounding_can_flip():
+    y = B.Tracked(torch.tensor([1.0, 3e-7, -3e-7, 0.0, -1.0], dtype=torch.float64), torch.ones(5, dtype=torch.float64))
+    assert B.sign_disputed(y).tolist() == [False, False, False, True, False]           # 4 * 2^-24 = 2.4e-7
+    y.c *= 2
+    assert B.sign_disputed(y).tolist() == [False, True, True, True, False]
+
+
+@pytest.mark.parametrize('rows', [False, True], ids=['cols', 'rows'])
+@pytest.mark.parametrize('M,N', BN_SHAPES, ids=BN_IDS)
+def test_batchnorm_twins_pass_both_gates(M, N, rows):
+    """The kernels' arithmetic in float32 torch -- finalize and live form of the forward, both forms of the backward -- is
+    inside (R) and (E); tests/_product.gate calls the same correct `out` a failure (the [cw] lines), which is why no test used
+    such inputs.  The disputed ReLU signs stay under their cap on the reference alone."""
+    c = NC.BnCase(M, N, rows=rows)
+    assert c.share() <= NC.DISPUTED_CAP
+    cpu = _bn_cpu32(c)
+    for live in (False, True):
+        t = _bn_twin(c, live=live)
+        what = f'batchnorm twin {"live" if live else "finalize"} {c.what}'
+        NC.hold(t, lambda s: c.fwd(s, 3 if live else 1), cpu, FWD, what)
+        NC.hold(t, c.fwd, None, ('scale', 'shift'), what)
+    for form in ('apply', 'stage'):
+        dz, s1, s2 = B.bn_backward_twin(c.z, c.dyh, t['scale'], t['mean'], t['rstd'], form)
+        NC.hold(dict(dz=dz, s1=s1, s2=s2), lambda s: c.bwd(s, form), cpu, ('dz', 's1', 's2'), f'batchnorm twin backward {form} {c.what}')
+
+
+def test_batchnorm_twin_at_one_row():
+    """M = 1: variance 0, rstd = eps^-1/2, y = beta after a cancellation of ~1e3; torch refuses the batch, so (R) alone, and the
+    backward without ReLU (a third of the signs are disputed)."""
+    c = NC.BnCase(1, 64, relu=False)
+    t = _bn_twin(c)
+    NC.hold(t, c.fwd, None, FWD + ('scale', 'shift'), 'batchnorm twin M=1')
+    dz, s1, s2 = B.bn_backward_twin(c.z, c.dyh, t['scale'], t['mean'], t['rstd'])
+    NC.hold(dict(dz=dz, s1=s1, s2=s2), c.bwd, None, ('dz', 's1', 's2'), 'batchnorm twin backward M=1')
+    share = float(B.sign_disputed(c.fwd(B.FMA)['y']).double().mean())
+    print(f'[cw] M=1: {100 * share:.3g}% of the ReLU signs would be disputed')
+    assert share > NC.DISPUTED_CAP
+
+
+def _verdicts(got, ref_of, cpu, names, what):
+    figs = NC.hold(got, ref_of, cpu, names, what, assert_=False)
+    for name, fig in figs.items():
+        print(f'[mutant] {what}: {name} caught by {NC.caught_by(fig)}')
+    return figs
+
+
+@pytest.mark.parametrize('alter', B.BN_ALTERED)
+@pytest.mark.parametrize('M,N', BN_SHAPES, ids=BN_IDS)
+def test_altered_batchnorm_forward_fails(M, N, alter):
+    """Every wrong forward of BN_ALTERED is refused on the column-graded operands by the result it damages: float32 column
+    sums and float32 squares by rstd, out and the running variance; a count taken from the capacity by everything; a biased
+    running variance by the running variance alone; a shift from another mean by out alone.
+    With the ROWS graded as well the spread of a column is that of its largest rows and |mean| / spread falls to ~1: there
+    float32 squares pass both gates in places -- printed, a limit of the inputs, not asserted."""
+    cap = (M + 63) // 64 * 64 if M % 64 else M + 64
+    for rows in (False, True):
+        c = NC.BnCase(M, N, rows=rows)
+        figs = _verdicts(_bn_twin(c, alter=alter, cap=cap), c.fwd, _bn_cpu32(c), FWD, f'{alter} {c.what}')
+        damaged = {'sums_fp32': ('rstd', 'out', 'running_var'), 'squares_fp32': ('rstd', 'out', 'running_var'), 'capacity': FWD,
+                   'biased_running': ('running_var',), 'shift_mean': ('out',)}[alter]
+        if not rows:
+            for name in damaged:
+                assert not NC.passes(figs[name]), (alter, name, figs[name])
+        elif all(NC.passes(f) for f in figs.values()):
+            print(f'[mutant] {alter} {c.what}: passes BOTH gates on every result -- beyond the method with these inputs')
+        for name in set(FWD) - set(damaged):          # ... and nothing else is blamed
+            if alter not in ('sums_fp32', 'squares_fp32'):
+                assert NC.passes(figs[name]), (alter, name, figs[name])
+
+
+@pytest.mark.parametrize('alter', ['drop_xhat_term', 'dgamma_short'])
+@pytest.mark.parametrize('M,N', BN_SHAPES, ids=BN_IDS)
+def test_altered_batchnorm_backward_fails(M, N, alter):
+    """The xhat s2 / M term left out of the smallest-grade column, and s2 short of its last row: refused by dz (and s2).  Without
+    ReLU: in the smallest-grade column eps outweighs the variance (2^-24 against 1e-5), y is beta there, and under ReLU a
+    negative beta masks the whole column -- the alteration then changes nothing (printed for the ReLU cases)."""
+    for relu in (False, True):
+        c = NC.BnCase(M, N, relu=relu)
+        t = _bn_twin(c)
+        for form in ('apply', 'stage'):
+            dz, s1, s2 = B.bn_backward_twin(c.z, c.dyh, t['scale'], t['mean'], t['rstd'], form, alter=alter)
+            figs = _verdicts(dict(dz=dz, s1=s1, s2=s2), lambda s: c.bwd(s, form), _bn_cpu32(c), ('dz', 's1', 's2'), f'{alter} {form} {c.what}')
+            if not relu:
+                assert not NC.passes(figs['dz']), (alter, form, figs['dz'])
+                assert NC.passes(figs['s1']) and NC.passes(figs['s2']) == (alter == 'drop_xhat_term')
+            elif all(NC.passes(f) for f in figs.values()):
+                col = int(B.grade_cols(N).argmin())
+                assert alter == 'drop_xhat_term' and not bool(c.mask[:, col].any()), 'passes both gates with a live column'
+                print(f'[mutant] {alter} {form} {c.what}: no effect, column {col} is masked entirely')
+
+
+LN_SHAPES = [(M, N) for M in (33, 70) for N in (3, 100, 160, 260)]
+LN_NAMES = ('out', 'mean', 'rstd', 'dz', 'dgamma', 'dbeta')
+
+
+def _ln_twin(c, alter=None):
+    t = B.ln_forward_twin(c.z, c.gamma, c.beta, NC.EPS, c.relu, alter=alter)
+    dz, dg, db = B.ln_backward_twin(c.z, c.dy * (t['out'] > 0) if c.relu else c.dy, c.gamma, t['mean'], t['rstd'])
+    t.update(dz=dz, dgamma=dg, dbeta=db)
+    return t
+
+
+@pytest.mark.parametrize('M,N', LN_SHAPES, ids=[f'{M}x{N}' for M, N in LN_SHAPES])
+def test_layernorm_twin_passes_and_without_the_correction_fails(M, N):
+    """cwn_layernorm's two-pass statistics with the second pass's correction of the mean are inside both gates on rows that
+    stand up to 4096 spreads off zero; without the correction `out` leaves (R) at ratios 20 - 2000.  F.layer_norm in float32
+    on the CPU is itself that far out on these rows (its ratio is the (E) limit's base), so (E) does not see it: (R) does."""
+    c = NC.LnCase(M, N)
+    assert c.share() <= NC.DISPUTED_CAP
+    ref_of = lambda s: {**c.fwd(s), **c.bwd(s)}
+    NC.hold(_ln_twin(c), ref_of, c.torch32(), LN_NAMES, f'layernorm twin {c.what}')
+    figs = _verdicts(_ln_twin(c, alter='no_correction'), ref_of, c.torch32(), LN_NAMES, f'no_correction {c.what}')
+    assert figs['out'][0] > B.RIGOROUS, figs['out']
