@@ -812,28 +812,27 @@ def aggregate(descs: Sequence[AggDesc], device, dtype: torch.dtype = torch.float
         check(fn(arr, len(chunk), s), name)
 
 
+def _aggregate_act(stem: str, struct, descs: Sequence, device, dtype: torch.dtype) -> None:
+    fn, name = typed_entry(stem, dtype)
+    s = stream_ptr(device)
+    for i in range(0, len(descs), MAX_DESCS):
+        chunk = descs[i:i + MAX_DESCS]
+        arr = (struct * len(chunk))(*chunk)
+        check(fn(arr, len(chunk), s), name)
+
+
 def aggregate_act(descs: Sequence[AggActDesc], device, dtype: torch.dtype = torch.float32) -> None:
     """The activated two-operand message (csrc/cwn_aggregate_act.hip): one kernel launch for up to MAX_DESCS descriptors,
     more are split into several calls.  Every operand of every descriptor has the one `dtype`.  Row counts are host
     counts: the descriptor has no m_dev, so nothing is looked up in DYN_ROWS."""
-    fn, name = typed_entry('aggregate_act', dtype)
-    s = stream_ptr(device)
-    for i in range(0, len(descs), MAX_DESCS):
-        chunk = descs[i:i + MAX_DESCS]
-        arr = (AggActDesc * len(chunk))(*chunk)
-        check(fn(arr, len(chunk), s), name)
+    _aggregate_act('aggregate_act', AggActDesc, descs, device, dtype)
 
 
 def aggregate_act_bwd(descs: Sequence[AggActBwdDesc], device, dtype: torch.dtype = torch.float32) -> None:
     """The backward of the activated message (csrc/cwn_aggregate_act_bwd.hip): one kernel launch for up to MAX_DESCS
     descriptors, more are split into several calls.  Every operand of every descriptor has the one `dtype`.  Row counts
     are host counts, as the forward's."""
-    fn, name = typed_entry('aggregate_act_bwd', dtype)
-    s = stream_ptr(device)
-    for i in range(0, len(descs), MAX_DESCS):
-        chunk = descs[i:i + MAX_DESCS]
-        arr = (AggActBwdDesc * len(chunk))(*chunk)
-        check(fn(arr, len(chunk), s), name)
+    _aggregate_act('aggregate_act_bwd', AggActBwdDesc, descs, device, dtype)
 
 
 def gemm(descs: Sequence[GemmDesc], device) -> None:

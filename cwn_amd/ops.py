@@ -180,15 +180,10 @@ class AggActSpec:
             n_dst=self.n_dst, F=self.F, act=self.act)
 
 
-def run_aggregate_act(specs: Sequence[AggActSpec], device) -> List[Tensor]:
-    """Raw launch of the activated message (no autograd): allocates missing outputs, ONE kernel per <= 8 descriptors of one
-    dtype.  Row counts are host counts: the launch has no device-side row count, so it refuses to run under
-    `_ffi.dynamic_rows` (no static batch reaches it)."""
-    if _ffi.DYN_ROWS:
-        raise _ffi.CwnError('cwn_aggregate_act_* has no device-side row count: it does not serve static batches')
+def _run_act_specs(specs: Sequence, device, launch) -> List[Tensor]:
+    """What run_aggregate_act and run_aggregate_act_bwd do once their operands are checked: allocate missing outputs, build
+    the plans handed out late, wait for those built on the side stream, and `launch` the descriptors dtype by dtype."""
     for s in specs:
-        if s.dtype is not None and s.dtype not in _ffi.FLOAT_DTYPES:
-            raise TypeError(f'aggregate_act computes in float32 or float64, not {s.dtype}')
         if s.out is None:
             s.out = torch.empty(s.n_dst, s.F, dtype=s.resolve_dtype(), device=device)
     live = [s for s in specs if s.n_dst > 0]
@@ -202,8 +197,20 @@ def run_aggregate_act(specs: Sequence[AggActSpec], device) -> List[Tensor]:
         for s in live:
             by_dtype.setdefault(s.resolve_dtype(), []).append(s.desc())
         for dt, descs in by_dtype.items():
-            _ffi.aggregate_act(descs, device, dt)
+            launch(descs, device, dt)
     return [s.out for s in specs]
+
+
+def run_aggregate_act(specs: Sequence[AggActSpec], device) -> List[Tensor]:
+    """Raw launch of the activated message (no autograd): allocates missing outputs, ONE kernel per <= 8 descriptors of one
+    dtype.  Row counts are host counts: the launch has no device-side row count, so it refuses to run under
+    `_ffi.dynamic_rows` (no static batch reaches it)."""
+    if _ffi.DYN_ROWS:
+        raise _ffi.CwnError('cwn_aggregate_act_* has no device-side row count: it does not serve static batches')
+    for s in specs:
+        if s.dtype is not None and s.dtype not in _ffi.FLOAT_DTYPES:
+            raise TypeError(f'aggregate_act computes in float32 or float64, not {s.dtype}')
+    return _run_act_specs(specs, device, _ffi.aggregate_act)
 
 
 # The backward of a stream with an activation (Stream.act) as descriptors of cwn_aggregate_act_bwd_f32 / _f64 over the
@@ -226,6 +233,13 @@ class AggActBwdSpec:
     Q: Tensor
     iq: Tensor
     out: Optional[Tensor] = None
+
+    @property
+    def n_dst(self) -> int:
+        return self.adj.n_dst
+
+    def resolve_dtype(self) -> torch.dtype:
+        return self.g.dtype
 
     def desc(self) -> _ffi.AggActBwdDesc:
         absent = self.adj.n_entries == 0
@@ -254,21 +268,7 @@ def run_aggregate_act_bwd(specs: Sequence[AggActBwdSpec], device) -> List[Tensor
                                 f"stream's dtype (got {t.dtype}, {tuple(t.shape)})")
         if s.P.size(0) != s.adj.n_dst:
             raise ValueError(f'aggregate_act_bwd: P has {s.P.size(0)} rows, the transposed plan {s.adj.n_dst}')
-        if s.out is None:
-            s.out = torch.empty(s.adj.n_dst, s.F, dtype=s.g.dtype, device=device)
-    live = [s for s in specs if s.adj.n_dst > 0]
-    if live:
-        late = [s.adj for s in live if not s.adj.built]
-        if late:
-            from .csr import build_many
-            build_many(late)
-        wait_ready([s.adj for s in live])
-        by_dtype = {}
-        for s in live:
-            by_dtype.setdefault(s.g.dtype, []).append(s.desc())
-        for dt, descs in by_dtype.items():
-            _ffi.aggregate_act_bwd(descs, device, dt)
-    return [s.out for s in specs]
+    return _run_act_specs(specs, device, _ffi.aggregate_act_bwd)
 
 
 def _act_backward_entries(act: int, z: Tensor, g: Tensor) -> Tensor:

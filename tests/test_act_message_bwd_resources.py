@@ -2,6 +2,7 @@
 tests/test_act_message_resources.py reads the forward's (no GPU): both element types, both addressing forms, and in each
 of them every (vector width, activation) form -- they are dispatched inside the kernel -- without a spill or scratch."""
 import os
+import re
 import sys
 
 import pytest
@@ -11,6 +12,10 @@ sys.path.insert(0, os.path.join(ROOT, 'tools'))
 from kernel_resources import kernels, READELF      # noqa: E402
 
 LIB = os.path.join(ROOT, 'cwn_amd', 'libcwn_hip.so')
+
+# (vgpr_count, sgpr_count) each kernel took as a text of its own, by <element type, 32-bit row offsets> as the mangled name
+# spells them: the body shared with the other direction (csrc/cwn_aggregate_act_body.h) costs no register
+PINNED = {'IfLb0': (95, 76), 'IfLb1': (95, 74), 'IdLb0': (110, 102), 'IdLb1': (96, 99)}
 
 
 @pytest.fixture(scope='module')
@@ -31,6 +36,8 @@ def test_act_message_bwd_kernels_neither_spill_nor_use_scratch(table):
         # the long-row partials: 256 lanes x 16 bytes
         assert v['group_segment_fixed_size'] == 256 * 16, (name, v)
         assert v['vgpr_count'] <= 128, (name, v)        # four waves of a workgroup per SIMD at the least
+        vgpr, sgpr = PINNED[re.search(r'kernel(I[fd]Lb[01])E', name).group(1)]
+        assert v['vgpr_count'] <= vgpr and v['sgpr_count'] <= sgpr, (name, v)
 
 
 def test_the_forward_kernels_are_still_their_own(table):
