@@ -380,17 +380,20 @@ __device__ __forceinline__ float4 head_group_sum(const cwn_head_dim& D, int64_t 
 }
 
 
+// (the row partials of phase 1 and the slice partials of phase 2 share their floats: the first are all read, into `pooled`,
+// behind a barrier before the second are written.  With a buffer each, K = 2048 asked for 72 KiB and was refused.)
 __host__ __device__ constexpr size_t head_lds_floats(int K, int H2) {
-    return (size_t)CWN_HEAD_MAX_DIMS * kPartFloats + (size_t)CWN_HEAD_MAX_DIMS * K + (size_t)CWN_HEAD_MAX_DIMS * 4 * kHeadThreads + H2;
+    return (size_t)CWN_HEAD_MAX_DIMS * kPartFloats + (size_t)CWN_HEAD_MAX_DIMS * K + H2;
 }
+static_assert(head_lds_floats(4 * kHeadThreads, kHeadThreads) * sizeof(float) <= 64 * 1024, "the head's LDS at its widest K and H2");
 
 __global__ __launch_bounds__(kHeadThreads) void head_kernel(HeadArgs A) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int K = A.K, H2 = A.H2, nd = A.n_dims;
     float* const part = sm;                                                    // [3][NG][K]
+    float* const hpart = part;                                                 // [3][S][H2], S * H2 <= 4 * 512 = kPartFloats: phase 2, over `part`
     float* const pooled = part + CWN_HEAD_MAX_DIMS * kPartFloats;              // [3][K]
-    float* const hpart = pooled + CWN_HEAD_MAX_DIMS * K;                       // [3][S][H2], S * H2 <= 4 * 512
-    float* const sbuf = hpart + CWN_HEAD_MAX_DIMS * 4 * kHeadThreads;          // [H2]
+    float* const sbuf = pooled + CWN_HEAD_MAX_DIMS * K;                        // [H2]
     const int tid = threadIdx.x;
     const int64_t c = blockIdx.x;
     cwn::Dropout drop;
@@ -417,7 +420,9 @@ __global__ __launch_bounds__(kHeadThreads) void head_kernel(HeadArgs A) {
 #pragma unroll
     for (int d = 0; d < CWN_HEAD_MAX_DIMS; ++d) big = big || (r1[d] - r0[d] > kHeadChunk);
     if (from_partials || big) {
-        float* const tmp = hpart;                          // [NG][K] group partials of one chunk (phase 2 has not begun)
+        // [NG][K] group partials of one chunk, in the LAST dimension's floats of `part`: a dimension's own sum is stored (below)
+        // behind the barrier that ends its last chunk, and no chunk of a later dimension follows the last one's
+        float* const tmp = part + (size_t)(CWN_HEAD_MAX_DIMS - 1) * kPartFloats;
         for (int d = 0; d < CWN_HEAD_MAX_DIMS; ++d) {
             const int64_t nch = (r1[d] - r0[d] + kHeadChunk - 1) / kHeadChunk;
             float acc[4] = {0.f, 0.f, 0.f, 0.f};           // columns tid, tid + 512, ... (K <= 2048)
@@ -692,12 +697,12 @@ __global__ __launch_bounds__(kHeadThreads) void head_bwd_kernel(HeadBwdArgs A) {
         int64_t r0 = A.d[d].cell_ptr[c], r1 = A.d[d].cell_ptr[c + 1];
         r0 = r0 < 0 ? 0 : (r0 > A.d[d].n_cells ? A.d[d].n_cells : r0);
         r1 = r1 < r0 ? r0 : (r1 > A.d[d].n_cells ? A.d[d].n_cells : r1);
-        if (tid < K) {
+        for (int k = tid; k < K; k += kHeadThreads) {                       // (K <= 2048: up to four columns a thread)
             float v = 0.f;
-            for (int q = 0; q < S; ++q) v += part[(size_t)q * K + tid];       // fixed order
-            if (dpos == CWN_HEAD_DROP_LIN1) v *= drop.mul1(((uint64_t)d * (uint64_t)A.C + (uint64_t)c) * (uint64_t)K + (uint64_t)tid);
+            for (int q = 0; q < S; ++q) v += part[(size_t)q * K + k];         // fixed order
+            if (dpos == CWN_HEAD_DROP_LIN1) v *= drop.mul1(((uint64_t)d * (uint64_t)A.C + (uint64_t)c) * (uint64_t)K + (uint64_t)k);
             if (A.mean_readout) v = v / (float)(r1 - r0 > 0 ? r1 - r0 : 1);
-            dp[tid] = v;
+            dp[k] = v;
         }
         __syncthreads();
         // 4. every row of the complex gets it (this workgroup: its chunk of the rows; a concatenation: every block to its matrix)

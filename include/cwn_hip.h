@@ -2186,7 +2186,8 @@ int cwn_head_f32(const cwn_head_dim* dims_host, int n_dims, int64_t C, int32_t K
  *     dx_d[r] = W1_d^T dh_d  [/ cells of the complex]   for every row r of the complex   (dx == NULL: not wanted)
  * The weight gradients are sums over the complexes and go through cwn_gemm_tn_f32 on the [C, .] matrices:
  * dW1_d = dh_d^T pooled_d, db1_d = column sums of dh_d, dW2 = g_out^T s, db2 = column sums of g_out.
- * w1 is lin1s[d].weight in its own [H2, K] layout (16-B aligned); same size limits as the forward. */
+ * w1 is lin1s[d].weight in its own [H2, K] layout (16-B aligned).  The forward's sizes: K % 4 == 0, 4 <= K <= 2048 (the whole
+ * range: a thread of the 512 finishes columns k, k + 512, ... of dpooled), H2 % 4 == 0, 4 <= H2 <= 512; CWN_ERR_BAD_ARG beyond. */
 typedef struct cwn_head_bwd_dim {
     const float* h;             /* [C, H2] pre-activation saved by the forward */
     const float* w1;            /* [H2, K] */

@@ -728,25 +728,39 @@ def test_embed_pool_and_agnostic_head(K, H, O, act, mean):
 
 
 @pytest.mark.parametrize('mean', [False, True], ids=['sum', 'mean'])
-@pytest.mark.parametrize('K,H2,O', [(64, 128, 2), (20, 12, 3)])
+@pytest.mark.parametrize('K,H2,O', [(64, 128, 2), (20, 12, 3), (640, 128, 2), (2048, 8, 1)])
 def test_head(K, H2, O, mean):
-    """cwn_head_f32: pool per complex (sum / mean, one empty complex), relu(lin1_d) per dimension, their sum, lin2."""
+    """cwn_head_f32: pool per complex (sum / mean, one empty complex), relu(lin1_d) per dimension, their sum, lin2.  K = 640
+    and 2048: a thread of the 512 holds more than one column of a chunked or a partials sum.  A sixth complex of 300 cells per
+    dimension is summed chunk by chunk -- inside the head launch, or by the pooling launch ahead of it (HEAD_POOL_SPLIT '4') --
+    while the small ones take the one-pass form: the same bits from both launches."""
+    from tests._readout_bwd import HEAD_SIZES
+    assert tuple(s[:-1] for s in HEAD_SIZES) == SIZES
     g = torch.Generator().manual_seed(K + H2 + O + mean)
     gi, gh, go = B.grade_inner(K), B.grade_inner(H2), B.grade_cols(O)
-    ptrs = [_ptr(s) for s in SIZES]
-    Cn = len(SIZES[0])
+    ptrs = [_ptr(s) for s in HEAD_SIZES]
+    Cn = len(HEAD_SIZES[0])
     xp = [_rand(g, int(p[-1]), K) * B.grade_rows(int(p[-1]))[:, None] for p in ptrs]
     W1, b1 = [_rand(g, H2, K) / K ** 0.5 for _ in ptrs], [0.3 * _rand(g, H2) for _ in ptrs]
     W2, b2 = _rand(g, O, H2) / H2 ** 0.5, 0.3 * _rand(g, O)
     x = [t * gi[None, :] for t in xp]
     W1g, b1g, W2g, b2g = [W * gh[:, None] / gi[None, :] for W in W1], [b * gh for b in b1], W2 * go[:, None] / gh[None, :], b2 * go
 
-    def launch(x, W1, b1, W2, b2):
-        with torch.no_grad():
-            return ops.head(_dev(*x), _dev(*ptrs), Cn, _dev(*W1), _dev(*b1), W2.to(DEV), b2.to(DEV), mean_readout=mean, want_pooled=True)
+    def launch(x, W1, b1, W2, b2, split=None):
+        prev = ops.HEAD_POOL_SPLIT
+        ops.HEAD_POOL_SPLIT = prev if split is None else split
+        try:
+            with torch.no_grad():
+                return ops.head(_dev(*x), _dev(*ptrs), Cn, _dev(*W1), _dev(*b1), W2.to(DEV), b2.to(DEV), mean_readout=mean, want_pooled=True)
+        finally:
+            ops.HEAD_POOL_SPLIT = prev
     out, pooled = launch(x, W1g, b1g, W2g, b2g)
     what = f'head K={K} H2={H2} O={O} {"mean" if mean else "sum"}'
     _form(what, 'cwn_head_f32 (ops.head has no other route)')
+    out_s, pooled_s = launch(x, W1g, b1g, W2g, b2g, split='4')
+    assert torch.equal(out_s, out), what + ': the pooling launch ahead of the head changes the prediction'
+    for d in range(3):
+        assert torch.equal(pooled_s[d], pooled[d]), f'{what}: the pooling launch ahead of the head changes pooled dim {d}'
 
     def tracked(s):
         ps = [B.segment_sum(B.inp(x[d]), _complex_of(ptrs[d]), Cn, mean=mean) for d in range(3)]
@@ -755,7 +769,7 @@ def test_head(K, H2, O, mean):
     ps32 = []
     for d in range(3):
         p = torch.zeros(Cn, K).index_add_(0, _complex_of(ptrs[d]), x[d])
-        ps32.append(p / torch.tensor(SIZES[d]).clamp(min=1)[:, None] if mean else p)
+        ps32.append(p / torch.tensor(HEAD_SIZES[d]).clamp(min=1)[:, None] if mean else p)
     out32 = sum(torch.relu(ps32[d] @ W1g[d].t() + b1g[d]) for d in range(3)) @ W2g.t() + b2g
     for d in range(3):
         B.check(pooled[d], lambda s: tracked(s)[0][d], B.FMA, ps32[d], f'{what} pooled dim {d}')
